@@ -26,6 +26,8 @@ After the timed region (never part of `value`):
                       argmax differs, clips with identical note lists, note-level precision / recall (`parity`, `meets_north_star_parity`);
   * parity-grade leg -- the same workload in precision "fp16x3", the fast mode that meets the north star's tolerance
                       (`parity_grade`: clips/s, its own roofline fraction against 2.5 PF / 3, max |dlogit| vs the exact fp32 mode);
+  * --dump-outputs DIR -- what the LAST timed step handed back, written as DIR/<name>.npy (float32 / float64; see dump_outputs) so that
+                      two builds can be compared output for output on identical, seeded inputs;
   * trained-like leg -- the numeric modes on seeded synthetic singing with the head fitted to it (`trained_like`: frames, identical note
                       lists, note F1 against the clips' ground truth: what 16-bit operands cost when decisions have margins);
   * cpu_baseline   -- the oracle on the host cores, SURVEY.md §8(d) protocol (rank 0, N = 1 only).
@@ -69,6 +71,35 @@ PMC_TRAFFIC_FILE = os.path.join(ROOT, "profiles", "r06_pmc_hbm_traffic.json")
 def synth_wav(B, L, seed=1986):
     g = torch.Generator().manual_seed(seed)
     return (0.1 * torch.randn(B, L, generator=g)).clamp_(-1, 1)
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays, limit=DUMP_LIMIT_BYTES, seed=0):
+    """`arrays`: name -> numpy array whose first axis is the clip.  Writes out_dir/<name>.npy for each.  When they hold more than
+    `limit` bytes together, every array keeps the same fixed, seeded sample of clips, whose indices go to clip_index.npy."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    n = next(iter(arrays.values())).shape[0]
+    per_clip = sum(a.nbytes for a in arrays.values()) / n
+    if per_clip * n > limit:
+        keep = max(1, int(limit // (per_clip + 8)))
+        idx = np.sort(np.random.default_rng(seed).choice(n, keep, replace=False))
+        arrays = {k: a[idx] for k, a in arrays.items()}
+        arrays["clip_index"] = idx.astype(np.float64)
+    for k, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (k, a.dtype)
+        np.save(os.path.join(out_dir, k + ".npy"), np.ascontiguousarray(a))
+    return sorted(arrays)
+
+
+def frame_fields(frames, T):
+    """Decoded frames (int32 words: p_on f32 bits, p_off f32 bits, octave, pitch class) -> four per-clip arrays (clips, T)."""
+    import numpy as np
+    fr = frames.cpu().numpy().view(np.int32).reshape(-1, T, 4)
+    return {"frame_p_on": fr[..., 0].view(np.float32).copy(), "frame_p_off": fr[..., 1].view(np.float32).copy(),
+            "frame_octave": fr[..., 2].astype(np.float64), "frame_pitch_class": fr[..., 3].astype(np.float64)}
 
 
 def host_topology():
@@ -290,12 +321,18 @@ def main():
                     "given (the collective stays outside the graph either way).  Before it is used, one replay is compared bit for bit with an "
                     "eager forward; a capture that fails or differs falls back to eager launches and config.launch says so")
     ap.add_argument("--no-graph", dest="graph", action="store_false", help="launch every step eagerly (the mode of rounds 1-5)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step returned to DIR/<name>.npy (rank 0; float32 / float64, at most "
+                    "64 MB, a seeded sample of clips beyond that): logits (clips, frames, 20) and the decoded frames' four fields; at N > 1 the "
+                    "gathered rows (--gather) of the whole global batch")
     ap.add_argument("--cpu-worker", default=None, help=argparse.SUPPRESS)   # internal: one process of cpu_baseline.by_procs
     args = ap.parse_args()
     if args.cpu_worker:
         return cpu_worker(args.cpu_worker)
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ and "RANK" not in os.environ:
         # Plain `python bench.py --gpus N`: start N fresh ranks (one process per GPU, as speechbrain/core.py:1150-1169 expects them:
         # RANK / LOCAL_RANK in the environment before anything touches a device) and relay rank 0's JSON line.  This process has
@@ -435,6 +472,17 @@ def main():
     elapsed = res["elapsed"]
     out = res["out"]
     assert out.shape[0] == n_total
+    if args.dump_outputs and rank == 0:
+        # the last timed step ran on lane (K - 1) mod streams; its buffers are copied here, before any later leg reuses them
+        torch.cuda.synchronize()
+        if gather_frames:
+            dumped = frame_fields(out, T)
+        else:
+            dumped = {"logits": out.detach().float().cpu().numpy().reshape(n_total, T, 20)}
+            if world == 1:
+                dumped.update(frame_fields(frames_l[(args.steps - 1) % ns], T))
+        names = dump_outputs(args.dump_outputs, dumped)
+        print(f"[bench] last timed step's outputs -> {args.dump_outputs}: {', '.join(names)}", file=sys.stderr)
     # a step is >= ~110 kernels: anything faster than this did not run the work
     if 1e3 * elapsed / args.steps < 0.05:
         raise SystemExit("[bench] implausible step time: the timed region did not execute the step")

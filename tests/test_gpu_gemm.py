@@ -177,9 +177,10 @@ def test_split_operand_persistent_kernel(variant, name, prec, M, N, K, conv, act
     assert err < {2: 3e-5, 3: 4e-6}[prec] * max(1.0, (K / 768) ** 0.5), (name, variant, err)
 
 
-def run_gemm_pairs(prec, M, N, K, conv, act, out_kind, bias=True, seed=0, want_ref=True):
-    """gemm_x3q_kernel through svt_debug_gemm_pairs: the fp32 A is converted to pair rows inside the hook, the result comes back as fp32."""
-    lib = _lib.load()
+def run_gemm_pairs(prec, M, N, K, conv, act, out_kind, bias=True, seed=0, want_ref=True, lib=None):
+    """gemm_x3q_kernel through svt_debug_gemm_pairs: the fp32 A is converted to pair rows inside the hook, the result comes back as fp32.
+    `lib`: the build to run it in (default: the shipped bf16 library)."""
+    lib = lib or _lib.load()
     g = torch.Generator().manual_seed(seed)
     if conv:
         T_in, T_out, st, cin = conv
@@ -197,7 +198,7 @@ def run_gemm_pairs(prec, M, N, K, conv, act, out_kind, bias=True, seed=0, want_r
     b = torch.randn(N, generator=g).to(DEV) if bias else None
     C = torch.full((M, N), float("nan"), device=DEV)
     _lib.check(lib.svt_debug_gemm_pairs(prec, A.data_ptr(), A.numel(), W.data_ptr(), C.data_ptr(), b.data_ptr() if bias else None, M, N, K,
-                                        rpb, bstr, rstr, act, out_kind, 0, torch.cuda.current_stream().cuda_stream, 0, None), "svt_debug_gemm_pairs")
+                                        rpb, bstr, rstr, act, out_kind, 0, torch.cuda.current_stream().cuda_stream, 0, None), "svt_debug_gemm_pairs", lib)
     torch.cuda.synchronize()
     if not want_ref:
         return C.cpu(), None
@@ -229,12 +230,14 @@ def test_pair_row_split_kernel(bm, out_kind, name, prec, M, N, K, conv, act, bia
     """gemm_x3q_kernel (both operands pre-cut into pair rows; the schedule of gemm_pps_kernel with hi*hi + hi*lo + lo*hi per block)
     against an fp64 reference, for its three outputs (fp32 rows / pair rows / separate planes: the last two read back as hi + lo,
     which carries 22 of fp32's 24 mantissa bits), every tile height, tile boundaries inside a workgroup's stream, M tails, conv
-    rows, GELU, bias as the accumulators' initial value."""
-    if out_kind == 2 and act:
-        pytest.skip("the plane output (QKV projection) has no activation")
+    rows, GELU, bias as the accumulators' initial value.  The plane output (QKV projection) has no activation: that request is refused."""
     lib = _lib.load()
     lib.svt_debug_set(1, bm)
     try:
+        if out_kind == 2 and act:
+            with pytest.raises(_lib.SvtError, match="outside the contract of gemm_x3q_kernel"):
+                run_gemm_pairs(prec, M, N, K, conv, act, out_kind, bias=bias)
+            return
         got, ref = run_gemm_pairs(prec, M, N, K, conv, act, out_kind, bias=bias)
     finally:
         lib.svt_debug_set(1, 0)
@@ -253,18 +256,24 @@ def test_pair_row_split_kernel(bm, out_kind, name, prec, M, N, K, conv, act, bia
 def test_pair_row_one_wave_kernel_equals_two_wave_kernel(bm, out_kind, name, prec, M, N, K, conv, act, bias):
     """gemm_p1x_kernel (round 5: one wave per SIMD, three phases per slab, K >= 96; svt_debug_set key 30 = 1) against gemm_x3q_kernel (the
     dispatched kernel, which the test above holds to the fp64 reference): the same MFMAs in the same order per accumulator -- lo x hi,
-    hi x hi, hi x lo from the bias -- so the outputs are bit-identical, for every tile height, output form, M tail, conv rows and GELU."""
-    if out_kind == 2 and act:
-        pytest.skip("the plane output (QKV projection) has no activation")
-    lib = _lib.load()
-    if lib.svt_debug_set(30, 1) != 0:
-        pytest.skip("gemm_p1x_kernel is an A/B arm: built by `make DIAG=1` only (the shipped library holds what it dispatches)")
+    hi x hi, hi x lo from the bias -- so the outputs are bit-identical, for every tile height, output form, M tail, conv rows and GELU.
+    gemm_p1x_kernel is an A/B arm that only the diagnostic build holds (`make DIAG=1`: libsvt_mi355_diag.so, made by build()), so both
+    arms run in that build.  The plane output (QKV projection) has no activation: both arms refuse that request."""
+    lib = _lib.load("diag")
+    assert lib.svt_debug_set(30, 1) == 0, "the diagnostic build lacks gemm_p1x_kernel"
+    lib.svt_debug_set(30, 0)
     lib.svt_debug_set(1, bm)
     try:
+        if out_kind == 2 and act:
+            for p1x in (1, 0):
+                lib.svt_debug_set(30, p1x)
+                with pytest.raises(_lib.SvtError, match="outside the contract of gemm_x3q_kernel"):
+                    run_gemm_pairs(prec, M, N, K, conv, act, out_kind, bias=bias, want_ref=False, lib=lib)
+            return
         lib.svt_debug_set(30, 1)
-        one, _ = run_gemm_pairs(prec, M, N, K, conv, act, out_kind, bias=bias, want_ref=False)
+        one, _ = run_gemm_pairs(prec, M, N, K, conv, act, out_kind, bias=bias, want_ref=False, lib=lib)
         lib.svt_debug_set(30, 0)
-        two, _ = run_gemm_pairs(prec, M, N, K, conv, act, out_kind, bias=bias, want_ref=False)
+        two, _ = run_gemm_pairs(prec, M, N, K, conv, act, out_kind, bias=bias, want_ref=False, lib=lib)
     finally:
         lib.svt_debug_set(30, 0)
         lib.svt_debug_set(1, 0)

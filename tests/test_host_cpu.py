@@ -791,3 +791,35 @@ def test_committed_simulation_bounds_are_what_the_simulation_gives():
             assert n_ref == t[4] and abs(f_full - t[5]) <= 2.0 / max(1, n_ref) and abs(f_on - t[7]) <= 2.0 / max(1, n_ref), (name, mode)
             # another BLAS thread count may move the last bits of a sum, hence a near-tie frame
             assert abs(mx - t[0]) <= 0.02 * t[0] + 1e-5 and abs(mean - t[1]) <= 0.01 * t[1] + 1e-6 and abs(mism - t[2]) <= 1 and frames == t[3], (name, mode)
+
+
+def test_bench_dump_outputs_writes_float_arrays_and_samples_beyond_the_limit(tmp_path):
+    """bench.py --dump-outputs: frames split into their four fields (the float fields keep their bits), every file float32 / float64,
+    and above the size limit the same seeded sample of clips in every array, its indices beside them."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("svt_bench_module", os.path.join(ROOT, "bench.py"))
+    B = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(B)
+    n, T = 6, 5
+    p_on = torch.rand(n, T)
+    words = torch.stack([p_on.view(torch.int32), (1 - p_on).view(torch.int32), torch.randint(0, 5, (n, T), dtype=torch.int32),
+                         torch.randint(0, 13, (n, T), dtype=torch.int32)], -1)
+    f = B.frame_fields(words, T)
+    assert np.array_equal(f["frame_p_on"], p_on.numpy()) and f["frame_p_on"].dtype == np.float32
+    assert np.array_equal(f["frame_octave"], words[..., 2].numpy()) and f["frame_octave"].dtype == np.float64
+    arrays = dict(f, logits=torch.randn(n, T, 20).numpy())
+    names = B.dump_outputs(str(tmp_path / "all"), arrays)
+    assert names == sorted(arrays)
+    for k in names:
+        a = np.load(tmp_path / "all" / f"{k}.npy")
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, arrays[k])
+    per_clip = sum(a.nbytes for a in arrays.values()) // n
+    limit = 3 * per_clip + 100
+    names = B.dump_outputs(str(tmp_path / "part"), arrays, limit=limit)
+    assert "clip_index" in names
+    idx = np.load(tmp_path / "part" / "clip_index.npy")
+    assert len(idx) == 3 and np.all(np.diff(idx) > 0)
+    assert sum(os.path.getsize(tmp_path / "part" / f"{k}.npy") - 128 for k in names) <= limit
+    assert np.array_equal(np.load(tmp_path / "part" / "logits.npy"), arrays["logits"][idx.astype(int)])
+    B.dump_outputs(str(tmp_path / "again"), arrays, limit=limit)
+    assert np.array_equal(np.load(tmp_path / "again" / "clip_index.npy"), idx)
