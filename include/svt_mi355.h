@@ -305,31 +305,35 @@ int svt_softmax(const float* x_dev, int64_t rows, int32_t n, int32_t apply_log, 
 int svt_debug_attention(int32_t precision, const void* q, const void* k, const void* v, void* o, int32_t batch, int32_t t,
                         int32_t heads, int32_t head_dim, int64_t ldq, int64_t ldkv, int64_t ldo, float scale, int device,
                         void* stream);
-/* Diagnostics switches of the contraction kernels (tools/gemm_bench.py, tools/gemm_trace.py; never needed in production):
- * key 0 = kernel ablation variant, 1 = force the tile height (64/128/192/256), 2 = force the one-tile (2) / persistent (4)
- * scheduler, 3 = ablation variant while tracing, 5 = retired (the fused out-projection + LayerNorm kernel of rounds 1-2), 6 = small-problem kernel
- * (gemm_skinny.hip) on/off, 7 = its eligibility threshold in 128x256 tiles, 8 = 8-wave fused-attention workgroups on/off,
- * 9 = bf16 (1) or fp32 (0) convolution output in front of the conv-stack LayerNorm in bf16 mode, 10 = whole-head fused
- * attention kernel (K / V of a head resident in LDS; measured slower, off by default), 11 = LDS-DMA split-operand GEMM
- * kernel on/off (off: the register-staged one), 12 = svt_debug_gemm keeps the split copy of its weight between calls,
- * 13 = page-guarded device allocations (see svt_debug_alloc), 19 = split-operand modes keep product operands as pair rows written by
- * their producers (1, default) or as fp32 cut inside the product kernels (0: the round-2/3 path, A/B), 20 = (hi, lo) LayerNorm with two
- * rows per wave (1, default) or one (0), 21 = fused attention variant (0 = staggered wave groups, 1 = the round-3 lockstep kernel),
- * 22 = conv layer 0 on the matrix pipe in the 16-bit modes (1, default) or on the vector ALU (0), 23 = stage 1 of the lip front-end on
- * the frame-resident direct convolution (1, default; conv3x3_c64.hip) or on the GEMM kernels (0), 24 = query: returns the number of
- * direct-convolution launches of this process so far (value ignored), 25 = timing-ablation bits of the direct convolution (DIAG builds),
- * 26 = stem + max-pool of the lip front-end as one persistent kernel (1, default) or as two kernels (0), 27 = stage 2's 1x1 stride-2
- * downsample inside conv1's product (1, default) or as its own product (0), 28 = two-slot schedule of gemm_pps_kernel (0, default: four
- * slots), 29 = gemm_p1w_kernel (one wave per SIMD) for the 16-bit products it measured faster on (1, default), everywhere (2) or never (0),
- * 30 = gemm_p1x_kernel (the same loop for the split-operand products on pair rows: 1) or gemm_x3q_kernel (0, default: same bits, same speed),
- * 31 = query: returns the number of device buffers this process has FREED so far (value ignored; uploads and re-uploads must not free:
- * tests/test_gpu_uploads.py), 32 = the tickets of the three ordered cross-workgroup sums as acquire-release atomics (1) or relaxed ones behind
- * write-through stores (0, default: kernels.hip, last_workgroup; same bits, tests/test_gpu_statistics.py), 34 = the persistent 16-bit GEMM
- * kernels' tile walk: -1 (default) chosen per launch, 0 = n fastest, n > 0 = panels of n tile rows (common.h, tile_walk; same bits), 35 = the kernel-3 convolutions' K slabs tap-minor (1, default: the frame two
- * neighbouring output rows share is re-read out of L2) or tap-major (0) on gemm_p1w_kernel, 36 = FFN-2 of a small batch (<= 2048 rows) as a K-split small GEMM whose partial
- * products the following LayerNorm adds (1, default) or as one product (0), 33 = the small-problem GEMM uses 32 x 32 tiles while its 64 x 64 tiling has at most this many workgroups
- * (96, default; swept on the one-utterance forward: 150 / 200 / 1000 are 1.5-4.5 % slower).
- * Returns 0 (keys 24, 31: the count), SVT_ERR_INVALID for an unknown key. */
+/* Diagnostics switches of the contraction kernels (tools/gemm_bench.py, tools/gemm_trace.py; never needed in production), by key:
+ * 0 = kernel ablation variant, 1 = force the tile height (64/128/192/256), 2 = force the one-tile (2) / persistent (4) scheduler,
+ * 3 = ablation variant while tracing (50-79: force gemm_pps_kernel), 5 = retired (the fused out-projection + LayerNorm kernel of
+ * rounds 1-2), 6 = small-problem kernel (gemm_skinny.hip) on/off, 7 = its eligibility threshold in 128x256 tiles, 8 = 8-wave
+ * fused-attention workgroups on/off, 9 = bf16 (1) or fp32 (0) convolution output in front of the conv-stack LayerNorm in bf16 mode,
+ * 10 = retired (the whole-head fused attention kernel), 11 = LDS-DMA split-operand GEMM kernel on/off (off: the register-staged one),
+ * 12 = svt_debug_gemm keeps the split copy of its weight between calls, 13 = page-guarded device allocations (see svt_debug_alloc),
+ * 15 = slot-stamp form of the split-operand GEMM kernels (DIAG builds, tools/gemm_trace.py --x3-slots), 16 = retired (the eight-barrier
+ * schedule of gemm_pps_kernel), 18 = retired (tile stamps of the lockstep attention kernel), 19 = split-operand modes keep product
+ * operands as pair rows written by their producers (1, default) or as fp32 cut inside the product kernels (0: the round-2/3 path, A/B),
+ * 20 = (hi, lo) LayerNorm with two rows per wave (1, default) or one (0), 21 = retired (A/B arms of the fused attention: only 0 and 3,
+ * the staggered kernel, are accepted), 22 = conv layer 0 on the matrix pipe in the 16-bit modes (1, default) or on the vector ALU (0),
+ * 23 = stage 1 of the lip front-end on the frame-resident direct convolution (1, default; conv3x3_c64.hip) or on the GEMM kernels (0),
+ * 24 = query: returns the number of direct-convolution launches of this process so far (value ignored), 25 = timing-ablation bits of the
+ * direct convolution (DIAG builds), 26 = stem + max-pool of the lip front-end as one persistent kernel (1, default) or as two kernels (0),
+ * 27 = stage 2's 1x1 stride-2 downsample inside conv1's product (1, default) or as its own product (0), 28 = retired (the two-slot
+ * schedule of gemm_pps_kernel: only 0 is accepted), 29 = gemm_p1w_kernel (one wave per SIMD) for the 16-bit products it measured faster
+ * on (1, default), everywhere (2) or never (0), 30 = gemm_p1x_kernel (the same loop for the split-operand products on pair rows: 1; DIAG
+ * builds only) or gemm_x3q_kernel (0, default: same bits, same speed), 31 = query: returns the number of device buffers this process has
+ * FREED so far (value ignored; uploads and re-uploads must not free: tests/test_gpu_uploads.py), 32 = the tickets of the three ordered
+ * cross-workgroup sums as acquire-release atomics (1) or relaxed ones behind write-through stores (0, default: kernels.hip,
+ * last_workgroup; same bits, tests/test_gpu_statistics.py), 33 = the small-problem GEMM uses 32 x 32 tiles while its 64 x 64 tiling has
+ * at most this many workgroups (96, default; swept on the one-utterance forward: 150 / 200 / 1000 are 1.5-4.5 % slower), 34 = the
+ * persistent 16-bit GEMM kernels' tile walk: -1 (default) chosen per launch, 0 = n fastest, n > 0 = panels of n tile rows (common.h,
+ * tile_walk; same bits), 35 = the kernel-3 convolutions' K slabs tap-minor (1, default: the frame two neighbouring output rows share is
+ * re-read out of L2) or tap-major (0) on gemm_p1w_kernel, 36 = FFN-2 of a small batch (<= 2048 rows) as a K-split small GEMM whose
+ * partial products the following LayerNorm adds (1, default) or as one product (0), 37 = workgroups of a persistent GEMM launch (8 .. 256,
+ * a multiple of 8; 256 = one per CU, default).
+ * Returns 0 (keys 24, 31: the count), SVT_ERR_INVALID for an unknown key or a value a key does not accept (21, 28, 30, 37 above). */
 int svt_debug_set(int key, int value);
 
 /* ---- measurement hook: HIP-event timing of the dominant kernel on the stream it runs on ----

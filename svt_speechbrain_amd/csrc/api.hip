@@ -501,27 +501,10 @@ int svt_debug_attention(int32_t precision, const void* q, const void* k, const v
 
 static int g_conv_down_fused = 1;   // svt_debug_set key 27: 0 = stage 2's stride-2 conv1 and its 1x1 downsample as two products (A/B, tests)
 int svt_debug_set(int key, int value) {
-#ifndef SVT_DIAG
-  // A/B arms that only `make DIAG=1` builds: the shipped library holds the kernels it dispatches
-  if ((key == 21 && value != 0 && value != 3) || (key == 28 && value != 0) || (key == 30 && value != 0)) {
-    set_error("svt_debug_set: this A/B arm is built by `make DIAG=1` only"); return SVT_ERR_INVALID; }
-#endif
   if (key == 0) g_gemm_dbg = value;
   else if (key == 1) g_gemm_force_bm = value;
   else if (key == 2) g_gemm_ring = value;
   else if (key == 3) g_gemm_variant = value;
-  else if (key == 15) g_stamp_ends = value;
-  else if (key == 16) g_pps_half_barriers = value;
-  else if (key == 28) g_pps_two_slots = value;
-  else if (key == 29) g_gemm_p1w = value;
-  else if (key == 30) g_gemm_p1x = value;
-  else if (key == 33) g_gemm_skinny_small_tiles = value;
-  else if (key == 32) return set_ticket_fenced(value);
-  else if (key == 34) g_gemm_walk = value;
-  else if (key == 36) g_ffn2_ksplit = value;
-  else if (key == 35) g_conv_kperm = value;
-  else if (key == 37) { if (value < 8 || value > 256 || value % 8) { set_error("svt_debug_set(37): 8 .. 256, a multiple of 8"); return SVT_ERR_INVALID; } g_gemm_persist_wgs = value; }
-  else if (key == 18) g_attn_stamp = value;
   else if (key == 5) { /* retired: the fused out-projection + LayerNorm kernel */ }
   else if (key == 6) g_gemm_skinny = value;
   else if (key == 7) g_gemm_skinny_max_tiles = value;
@@ -531,16 +514,40 @@ int svt_debug_set(int key, int value) {
   else if (key == 11) g_gemm_x3 = value;
   else if (key == 12) g_debug_keep_split = value;
   else if (key == 13) g_guard_alloc = value;
+  else if (key == 15) g_stamp_ends = value;
+  else if (key == 16) { /* retired: the eight-barrier schedule of gemm_pps_kernel (profiles/r03_gemm_pps_slots.txt) */ }
+  else if (key == 18) { /* retired: tile stamps of the lockstep eight-wave attention kernel */ }
   else if (key == 19) g_x3_pairs = value;
   else if (key == 20) g_ln_two_rows = value;
-  else if (key == 21) g_attn_variant = value;
+  else if (key == 21) {
+    // retired: the A/B arms of the head_dim-64 attention (lockstep, software-pipelined, LDS-padded forms); 0 and 3 both name the
+    // staggered kernel that ships
+    if (value != 0 && value != 3) { set_error("svt_debug_set(21): the attention A/B arms are retired"); return SVT_ERR_INVALID; }
+  }
   else if (key == 22) g_conv0_mfma = value;
   else if (key == 23) g_conv3x3_c64 = value;
   else if (key == 24) return g_conv3x3_c64_launches;
-  else if (key == 31) return g_dev_frees.load(std::memory_order_relaxed);
   else if (key == 25) g_conv3x3_c64_form = value;
   else if (key == 26) g_stem_pool_fused = value;
   else if (key == 27) g_conv_down_fused = value;
+  else if (key == 28) {   // retired: the two-slot schedule of gemm_pps_kernel (profiles/r05_gemm_two_slot_ab.txt)
+    if (value != 0) { set_error("svt_debug_set(28): the two-slot schedule is retired"); return SVT_ERR_INVALID; }
+  }
+  else if (key == 29) g_gemm_p1w = value;
+  else if (key == 30) {
+#ifndef SVT_DIAG
+    // gemm_p1x_kernel is built by `make DIAG=1` only: the shipped library holds the kernels it dispatches
+    if (value != 0) { set_error("svt_debug_set(30): gemm_p1x_kernel is built by `make DIAG=1` only"); return SVT_ERR_INVALID; }
+#endif
+    g_gemm_p1x = value;
+  }
+  else if (key == 31) return g_dev_frees.load(std::memory_order_relaxed);
+  else if (key == 32) return set_ticket_fenced(value);
+  else if (key == 33) g_gemm_skinny_small_tiles = value;
+  else if (key == 34) g_gemm_walk = value;
+  else if (key == 35) g_conv_kperm = value;
+  else if (key == 36) g_ffn2_ksplit = value;
+  else if (key == 37) { if (value < 8 || value > 256 || value % 8) { set_error("svt_debug_set(37): 8 .. 256, a multiple of 8"); return SVT_ERR_INVALID; } g_gemm_persist_wgs = value; }
   else { set_error("svt_debug_set: unknown key"); return SVT_ERR_INVALID; }
   return SVT_OK;
 }

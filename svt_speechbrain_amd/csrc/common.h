@@ -242,7 +242,7 @@ struct GemmArgs {
   // the 128 bytes of the fp32 slab they replace -- element strides / offsets are those of the fp32 tensor (multiples of 32 elements).
   int a_pairs = 0;             // A holds pair rows (written by a producer kernel): served by gemm_x3q_kernel only
   int c_pairs = 0;             // C is written as pair rows (the next product's operand) instead of fp32
-  int stamp_ends = 0;           // diagnostics (gemm_pps_kernel slot stamps): 0 = slot starts, 1 = slot ends
+  int stamp_ends = 0;           // diagnostics (DIAG builds): slot-stamp form of gemm_x3p_kernel / gemm_x3s_kernel (svt_debug_set key 15)
   long long* trace = nullptr;  // diagnostics (dbg == 9): per-workgroup phase clock stamps, 16 x int64 per workgroup
 };
 
@@ -254,7 +254,7 @@ bool gemm_dma_eligible(const GemmArgs& a);
 int launch_gemm_dma(const GemmArgs& a, hipStream_t s);
 // persistent + staggered form of the LDS-DMA pipeline (gemm_pps.hip): bf16 output, no residual, activation none / GELU
 bool gemm_pps_eligible(const GemmArgs& a);
-int launch_gemm_pps(const GemmArgs& a, int bm, hipStream_t s, int store_policy = 0);   // 0 default, 1 nt, 2 sc1 stores
+int launch_gemm_pps(const GemmArgs& a, int bm, hipStream_t s);
 // small problems (a single utterance): 64 x 64 tiles, K split four ways inside the workgroup, operands straight from L2
 bool gemm_skinny_eligible(const GemmArgs& a);
 int launch_gemm_skinny(const GemmArgs& a, hipStream_t s);
@@ -300,12 +300,8 @@ extern int g_conv_kperm;     // svt_debug_set key 35: 1 (default) = tap-minor K 
 extern int g_ffn2_ksplit;   // svt_debug_set key 36 (api.hip): FFN-2 of a small batch as a K-split small GEMM + summing LayerNorm
 extern int g_gemm_skinny;  // 1 (default): small problems use it; 0: never (diagnostics, svt_debug_set key 6)
 extern int g_stamp_ends;
-extern int g_pps_half_barriers;
 extern int g_gemm_p1w;       // svt_debug_set key 29: the single-wave-per-SIMD kernel (gemm_p1w.hip) where gemm_pps_kernel is dispatched
 int launch_gemm_p1w(const GemmArgs& a, int bm, hipStream_t s);
-extern int g_pps_two_slots;   // gemm_pps_kernel: two slots per slab (svt_debug_set key 28)
-extern int g_attn_stamp;
-extern int g_attn_variant;
 extern int g_gemm_dbg;   // diagnostic variant applied to every launch (svt_debug_set)
 extern int g_gemm_force_bm;
 extern int g_gemm_ring;

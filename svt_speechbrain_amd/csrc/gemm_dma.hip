@@ -1327,8 +1327,7 @@ bool gemm_dma_eligible(const GemmArgs& a) { return a.K % 64 == 0 && a.N >= 128 &
 int g_gemm_dbg = 0;
 int g_gemm_force_bm = 0;
 int g_gemm_variant = 0;
-int g_pps_half_barriers = 1;   // gemm_pps_kernel, four barriers per slab: 0 = never (A/B, slot stamps), 1 = always, 2 = GELU tiles with K <= 1024 only (svt_debug_set key 16)
-int g_stamp_ends = 0;   // gemm_pps_kernel slot stamps (tools/gemm_trace.py --slots): 0 = slot starts, 1 = slot ends
+int g_stamp_ends = 0;   // svt_debug_set key 15: which slot stamps of gemm_x3p_kernel / gemm_x3s_kernel a DIAG build takes (tools/gemm_trace.py --x3-slots)
 int g_gemm_ring = 0;  // 0 = auto; 2 = force the one-tile-per-workgroup kernel, 4 = force the persistent kernel (diagnostics)
 int launch_gemm_dma(const GemmArgs& a0, hipStream_t s) {
   GemmArgs a = a0;
@@ -1369,12 +1368,11 @@ int launch_gemm_dma(const GemmArgs& a0, hipStream_t s) {
   // 52.7 -> 48.0, 4096^3 115 -> 109; large FFN-2 (500 tiles, K = 4096) equal.  Measured per shape:
   // profiles/r03_gemm_vendor_library_yardstick.txt.  Write-through (sc1) stores: the output leaves L2 while the kernel runs instead
   // of at the kernel boundary (FFN-1: 98 MB, 16 us).
-  // svt_debug_set key 3: 50 / 70 force it with default / sc1 stores (53: without epilogue), 49 switches it off.
+  // svt_debug_set key 3: 50 - 79 force it (the last digit is its dbg: 53 / 73 = without epilogue), 49 switches it off.
   if (g_gemm_variant >= 50 && g_gemm_variant < 80 && gemm_pps_eligible(a)) {
     GemmArgs b = a;
     b.dbg = g_gemm_variant % 10;
-    b.stamp_ends = g_stamp_ends;
-    return launch_gemm_pps(b, g_gemm_force_bm ? g_gemm_force_bm : (best < 128 ? 128 : best), s, (g_gemm_variant - 50) / 10);
+    return launch_gemm_pps(b, g_gemm_force_bm ? g_gemm_force_bm : (best < 128 ? 128 : best), s);
   }
   if (g_gemm_variant != 49 && g_gemm_ring == 0 && best >= 128 && ntiles >= 100 && gemm_pps_eligible(a)) {
     // single-wave-per-SIMD kernel (gemm_p1w.hip, round 5): 5-11 % faster per launch wherever its un-overlapped epilogue is small beside the
@@ -1387,7 +1385,7 @@ int launch_gemm_dma(const GemmArgs& a0, hipStream_t s) {
       }
       return launch_gemm_p1w(a, best, s);
     }
-    return launch_gemm_pps(a, best, s, 2);
+    return launch_gemm_pps(a, best, s);
   }
   const bool pers_ok = !a.resid && a.nz == 1 && a.K >= 128 && a.N % 256 == 0 && a.c_z1 == 0 && a.c_z2 == 0 &&
                        a.a_z1 == 0 && a.a_z2 == 0 && a.w_z1 == 0 && a.w_z2 == 0;

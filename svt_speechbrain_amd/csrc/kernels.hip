@@ -1560,7 +1560,7 @@ int launch_pairs_to_f32(int kind, const void* in, const void* lo_plane, float* y
 
 // Fills and copies as KERNELS of this library, not hipMemsetAsync / hipMemcpyAsync (round 6): inside a captured hipGraph the runtime's
 // memset node ran out of order from the second replay on -- the statistics region of the workspace was zeroed AFTER the moments kernel had
-// written it, the output norm saw (0, 0) and scaled by 1 / sqrt(eps) (tools/scratch/graph_debug.py; tests/test_gpu_graph.py).  A kernel
+// written it, the output norm saw (0, 0) and scaled by 1 / sqrt(eps) (tools/graph_debug.py; tests/test_gpu_graph.py).  A kernel
 // node keeps stream order.  Sizes and addresses are multiples of 16 bytes (the workspace carve is 256-byte aligned).
 namespace {
 __global__ __launch_bounds__(256) void zero16_kernel(uint4* p, int64_t n16) {

@@ -49,7 +49,7 @@ def test_no_split_vector_loads(lib):
 
 
 @pytest.mark.parametrize("lib", ["libsvt_mi355.so", "libsvt_mi355_f16.so"])
-def test_vmem_instructions_beside_hand_counted_waits(lib):
+def test_vmem_table_of_hand_counted_waits(lib):
     """every kernel with hand-written `s_waitcnt vmcnt(N)` is held to the committed table of its VMEM
     instructions and counted waits (tools/isa_vmem_table.py: written when the GPU suite, the soak and the determinism stress were green on
     this code) -- a spill, a split / widened / duplicated load, a wait the compiler added or dropped, or a load moved ACROSS a counted wait
@@ -76,13 +76,8 @@ def test_vmem_instructions_beside_hand_counted_waits(lib):
     assert not diff, (diff[:3], "VMEM / wait table changed: re-validate on the GPU, then python tools/isa_vmem_table.py")
 
 
-@pytest.mark.parametrize("lib", ["libsvt_mi355.so", "libsvt_mi355_f16.so"])
-def test_shipped_library_holds_no_ab_arms(lib):
-    """experiment kernels that nothing dispatches (`gemm_p1x_kernel`, the two-slot schedule of gemm_pps_kernel, the
-    lockstep 8-wave attention, stamped diagnostic instantiations) are built by `make DIAG=1` only."""
-    src = os.path.join(ROOT, "svt_speechbrain_amd", lib)
-    if not os.path.exists(src):
-        pytest.skip("library not present")
+def _kernel_names(src):
+    """Demangled names of the device kernels of a built library."""
     syms = subprocess.run(["nm", "-C", "--defined-only", src], capture_output=True, text=True).stdout
     if "gemm_pps_kernel" not in syms:   # kernel names live in the device code objects, not in the host symbol table
         import sys
@@ -90,13 +85,45 @@ def test_shipped_library_holds_no_ab_arms(lib):
         import isa_vmem_table as T
         syms = "\n".join(subprocess.run(["c++filt"], input="\n".join(
             m for dis in T.disassemble(src) for m in re.findall(r"^[0-9a-f]+ <(\S+)>:", dis, re.M)), capture_output=True, text=True).stdout.splitlines())
+    return syms
+
+
+@pytest.mark.parametrize("lib", ["libsvt_mi355.so", "libsvt_mi355_f16.so"])
+def test_shipped_library_holds_only_dispatched_forms(lib):
+    """experiment kernels that nothing dispatches (`gemm_p1x_kernel`, the lockstep 8-wave attention, stamped
+    diagnostic instantiations) are built by `make DIAG=1` only."""
+    src = os.path.join(ROOT, "svt_speechbrain_amd", lib)
+    if not os.path.exists(src):
+        pytest.skip("library not present")
+    syms = _kernel_names(src)
     assert "gemm_pps_kernel" in syms and "flash_attn_stag_kernel" in syms
     for residue in ("gemm_p1x_kernel", "flash_attn_pipe_kernel", "flash_attn_kernel<64, false, 8", "flash_attn_x3_kernel<64, true, 8",
                     "flash_attn_x3_kernel<64, false, 8"):
         assert residue not in syms, residue
-    # gemm_pps_kernel<BM, ACT, STAUX, STAMP, HALF, TWO>: no two-slot (TWO = true) and no stamped (STAMP != 0) instantiation
-    for m in re.findall(r"gemm_pps_kernel<([^>]*)>", syms):
-        a = [x.strip() for x in m.split(",")]
-        assert a[3] == "0" and a[-1] == "false", m
+    # gemm_pps_kernel<BM, ACT>: the six dispatched instantiations and no other
+    got = sorted(set(re.findall(r"gemm_pps_kernel<(\d+), (\d+)>", syms)))
+    assert got == sorted((str(bm), str(act)) for bm in (128, 192, 256) for act in (0, 1)), got
+    assert len(set(re.findall(r"gemm_pps_kernel<[^>]*>", syms))) == 6
     for m in re.findall(r"gemm_p1w_kernel<([^>]*)>", syms):
         assert m.split(",")[-1].strip() == "false", m   # TR (stamps) only under DIAG
+
+
+def test_diagnostic_library_holds_no_retired_arms():
+    """The A/B arms measured and dropped in rounds 3-5 are gone from the sources, so the diagnostic build (libsvt_mi355_diag.so, made by
+    build()) cannot hold them either: the software-pipelined attention, the lockstep non-bias 8-wave attention kernels, the two-slot /
+    eight-barrier / stamped / default-store forms of gemm_pps_kernel and the six-slot form of gemm_x3q_kernel.  What stays is
+    instrumentation of shipped kernels and the gemm_p1x_kernel candidate."""
+    src = os.path.join(ROOT, "svt_speechbrain_amd", "libsvt_mi355_diag.so")
+    if not os.path.exists(src):
+        pytest.skip("library not present")
+    syms = _kernel_names(src)
+    assert "gemm_p1x_kernel" in syms and "flash_attn_stag_kernel" in syms and "flash_attn_kernel<64, true, 8>" in syms
+    for residue in ("flash_attn_pipe_kernel", "flash_attn_kernel<64, false, 8", "flash_attn_x3_kernel<64, true, 8",
+                    "flash_attn_x3_kernel<64, false, 8"):
+        assert residue not in syms, residue
+    # gemm_pps_kernel<BM, ACT> only (the retired forms were further template arguments)
+    pps = set(re.findall(r"gemm_pps_kernel<([^>]*)>", syms))
+    assert pps == {f"{bm}, {act}" for bm in (128, 192, 256) for act in (0, 1)}, sorted(pps)
+    # gemm_x3q_kernel<F16, BM, OUT, DBG>: the three-slot form only (the six-slot form was a fifth argument)
+    x3q = set(re.findall(r"gemm_x3q_kernel<([^>]*)>", syms))
+    assert x3q and all(len(m.split(",")) == 4 for m in x3q), sorted(x3q)

@@ -161,7 +161,7 @@ if __name__ == "__main__":
     ap.add_argument("--nobias", action="store_true")
     ap.add_argument("--no-x3-dma", action="store_true", help="split-operand modes: register-staged kernel instead of the LDS-DMA one (A/B)")
     ap.add_argument("--pad", type=int, default=0, help="extra elements of row pitch for A and W (plain GEMM shapes)")
-    ap.add_argument("--set", action="append", default=[], help="key=value for svt_debug_set (repeatable), e.g. --set 28=1: two-slot schedule of gemm_pps_kernel")
+    ap.add_argument("--set", action="append", default=[], help="key=value for svt_debug_set (repeatable), e.g. --set 37=128: persistent launches of 128 workgroups")
     ap.add_argument("--lib-suffix", default=None, help="load libsvt_mi355_<suffix>.so (an experimental build of the bf16 library) instead")
     a = ap.parse_args()
     if a.lib_suffix:

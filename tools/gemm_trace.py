@@ -100,10 +100,8 @@ def main():
                     help="run the kernel back to back for this long before the stamped launch (the clock the chip holds under "
                          "load: MI355X_MICROARCH.md 'DVFS give-back' item 6 asks for >= 2 s)")
     ap.add_argument("--variant", type=int, default=0, help="extra diagnostic variant: 10 = no stores, 11 = no pointer setup")
-    ap.add_argument("--force-variant", type=int, default=0, help="svt_debug_set key 3 for the whole run (50 = the persistent staggered kernel, "
-                    "51 / 53 / 54 = without LDS-DMA / epilogue / both)")
-    ap.add_argument("--slots", type=int, default=0, help="gemm_pps_kernel slot stamps of one slab: 5 = middle of the second tile, 6 = last slab of "
-                    "the first tile, 7 = first slab of the second tile (uses --force-variant 70 + this digit)")
+    ap.add_argument("--force-variant", type=int, default=0, help="svt_debug_set key 3 for the whole run (50 - 79 = the persistent staggered "
+                    "kernel, gemm_pps_kernel; 53 / 73 = without its epilogue)")
     ap.add_argument("--one-tile", action="store_true", help="with --x3-slots: gemm_x3s_kernel (one tile per workgroup) instead of the persistent kernel")
     ap.add_argument("--x3-slots", action="store_true", help="slot stamps of gemm_x3p_kernel (fp16x3, the persistent split-operand kernel): four "
                     "launches, two slots each")
@@ -117,8 +115,6 @@ def main():
         return x3_slots(a)
     if a.p1w:
         a.force_variant = a.force_variant or 70   # the persistent kernels' record layout
-    if a.slots:
-        a.force_variant = 70 + a.slots
     lib = _lib.load()
     lib.svt_debug_set(1, a.bm)
     lib.svt_debug_set(2, a.ring)
@@ -203,36 +199,6 @@ def main():
             slabs = (t[:, 5] * (K // 64)).mean().item()
             print(f"  gemm_p1w_kernel: core cycles between reaching a slab's counted wait and leaving its barrier: mean {cw.mean().item() / slabs:.0f} per slab "
                   f"(the matrix pipe idles for them; {int(t[0, 7].item()) // 32 * 8 * 2 * 16} = its own cycles per slab)")
-        if a.slots:
-            def stamps():
-                r = trace[65536:65536 + 256 * 8 * 32].view(256, 8, 32).cpu()
-                return r[r[:, 0, 9] > 0]
-            starts = stamps()
-            lib.svt_debug_set(15, 1)
-            trace.zero_()
-            call(9)
-            torch.cuda.synchronize()
-            ends = stamps()
-            lib.svt_debug_set(15, 0)
-            # launch 1 holds stamps 0..8 (both ends of slots 0-3), launch 2 stamps 8..16 (slots 4-7 and the next slab's start)
-            def d(x, y):
-                return ((y - x) & 0xFFFFFFFF).double()
-            names0 = ["LOAD0", "MMA0", "LOAD1", "MMA1", "LOAD2", "MMA2", "LOAD3", "MMA3+retire"]
-            names1 = ["LOAD0", "MMA0", "LOAD1", "MMA1", "LOAD2", "MMA2", "LOAD3+retire", "MMA3(+epi)"]
-            print(f"  slab {int(starts[0,0,10])} of {int(starts[0,0,9])}: core cycles per slot, work = slot start .. the wave's arrival at the barrier, "
-                  f"wait = arrival .. release; median over {starts.shape[0]} workgroups x 4 waves")
-            for grp, names in ((0, names0), (1, names1)):
-                w = slice(4 * grp, 4 * grp + 4)
-                tot = 0.0
-                print(f"   waves {4*grp}-{4*grp+3}:")
-                for k in range(8):
-                    src = starts if k < 4 else ends
-                    b = 2 * (k & 3)
-                    work = d(src[:, w, b], src[:, w, b + 1]).median().item()
-                    wait = d(src[:, w, b + 1], src[:, w, b + 2]).median().item()
-                    tot += work + wait
-                    print(f"     {names[k]:14s} work {work:6.0f}   wait {wait:6.0f}")
-                print(f"     slab total {tot:.0f} cycles (2048 = the MFMA pipe's share)")
 
 
 if __name__ == "__main__":

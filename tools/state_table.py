@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""The figures of DESIGN.md section 5 / README's table from profiles/<prefix>_bench*.json (what tools/run_final_rNN.sh wrote).
+"""The figures of DESIGN.md section 5 / README's table from profiles/<prefix>_bench*.json (what a round's final-measurement script wrote).
 usage: python tools/state_table.py [r05]"""
 import json
 import os
