@@ -214,8 +214,9 @@ int svt_fbank(const float* wav_dev, int32_t batch, int64_t n_samples, int32_t sa
  * under tools/ and the bench's per-launch timing.  They are the ONE exception to the conventions of the product entry points above:
  * a svt_debug_* call may allocate and free device memory and may synchronise its stream (hipMalloc / hipStreamSynchronize inside), and
  * svt_debug_set changes process-wide kernel selection.  No product entry point (svt_encoder_*, svt_linear_*, svt_rca_*, svt_video_*,
- * svt_decode_frames, svt_ctc_greedy, svt_fbank, svt_deltas, svt_context_window, svt_bce_loss, svt_nll_loss, svt_softmax) calls them, and
- * none of those allocates or synchronises.
+ * svt_decode_frames, svt_ctc_greedy, svt_fbank, svt_deltas, svt_context_window, svt_bce_loss, svt_nll_loss, svt_softmax and the
+ * training step) calls them, and none of those allocates or synchronises, except svt_amt_objective_grad, which synchronises its
+ * stream to report an out-of-range target.
  * ====================================================================================================================== */
 /* ---- test / micro-benchmark hook: the dense contraction kernel on caller-supplied operands ----
  * C (M,N) = act(A W^T + bias) + resid with A (M,K) and W (N,K) in the operand type of `precision`
@@ -297,6 +298,39 @@ int svt_nll_loss(const float* log_probs_dev, int64_t batch, int64_t t_pred, int3
 /* y = softmax(x) or log_softmax(x) over the last axis of (rows, n): replaces speechbrain.nnet.activations.Softmax
  * (activations.py:22-75) as the recipes use it (hparams log_softmax, apply_log=True) */
 int svt_softmax(const float* x_dev, int64_t rows, int32_t n, int32_t apply_log, float* y_dev, int device, void* stream);
+
+/* ---- head-only training step: the linear-probe stage of the recipes (MIR_ST500/train_audio_ssl.py:192-199, encoder frozen) ----
+ * Every reduction has a fixed order (no float atomics, no inter-workgroup flags): two calls on the same inputs give the same bits.
+ * Workspace convention of these three: *workspace_bytes is in / out; with workspace_dev == NULL the call stores the size it needs
+ * there and returns SVT_OK without touching the device; otherwise a smaller *workspace_bytes is SVT_ERR_WORKSPACE.
+ *
+ * The recipe's objective (train_audio_ssl.py:50-76) and its gradient in one pass over logits (B,t_pred,n_out) f32, columns
+ * [onset, offset, octave x (pitch_octave_num+1), class x the rest], n_out <= 32: BCE with logits on onset (pos_weight
+ * onset_pos_weight) and offset, log-softmax + NLL on octave and class (label_smoothing as compute_masked_loss), each reduced "mean"
+ * under the mask (float)t < rel_len[b]*T after truncating to T = min(t_pred, t_tgt) (|t_pred - t_tgt| <= allowed_len_diff, else
+ * SVT_ERR_INVALID with the reference's message).  Targets (B,t_tgt): onset / offset f32, octave / class i64 (-100 ignored);
+ * rel_len (B,) f32 or NULL.  terms_dev[5] = {onset, offset, octave, class, their sum}, each equal to svt_bce_loss / svt_nll_loss
+ * (reduction 0) on the same inputs; dlogits_dev (B,t_pred,n_out) = d(sum)/d(logits), exactly 0 on masked and truncated frames.
+ * terms_host (5 floats, may be NULL) receives the terms too.  This call synchronises `stream` (the target range is checked on the
+ * device): a target outside [0, n_classes) that is not -100 gives SVT_ERR_INVALID. */
+int svt_amt_objective_grad(const float* logits_dev, int64_t batch, int64_t t_pred, int32_t n_out, int32_t pitch_octave_num,
+                           const float* onset_targets_dev, const float* offset_targets_dev, const int64_t* octave_targets_dev,
+                           const int64_t* class_targets_dev, int64_t t_tgt, const float* rel_len_dev, float onset_pos_weight,
+                           int32_t allowed_len_diff, float label_smoothing, float* terms_dev, float* terms_host, float* dlogits_dev,
+                           void* workspace_dev, size_t* workspace_bytes, int device, void* stream);
+/* Weight gradient of a Linear layer whose input is frozen: dweight (out_features, in_features) = dy^T x and dbias (may be NULL) =
+ * sum over rows of dy, x (rows, in_features) f32, dy (rows, out_features) f32; out_features in 1..32, in_features a multiple of 4,
+ * x / dweight / workspace 16-byte aligned.  Overwrites (does not accumulate into) dweight / dbias.  No dx. */
+int svt_linear_backward(const float* x_dev, const float* dy_dev, int64_t rows, int32_t in_features, int32_t out_features,
+                        float* dweight_dev, float* dbias_dev, void* workspace_dev, size_t* workspace_bytes, int device, void* stream);
+/* torch.nn.utils.clip_grad_norm_ over n_tensors (<= 16) f32 gradient tensors -- total = ||[||g_i||]||, every g_i *= min(max_norm /
+ * (total + 1e-6), 1) in place -- when max_norm > 0, then torch.optim.Adadelta's update of each parameter (single-tensor form, torch's
+ * order of operations; maximize / weight_decay as torch).  All pointer arrays are HOST arrays of device pointers, numels a host array.
+ * total_norm_dev (one float, may be NULL) receives the pre-clip total norm. */
+int svt_clip_adadelta_step(int32_t n_tensors, float* const* params_dev, float* const* grads_dev, float* const* square_avg_dev,
+                           float* const* acc_delta_dev, const int64_t* numels, float lr, double rho, float eps, float weight_decay,
+                           int32_t maximize, float max_norm, float* total_norm_dev, void* workspace_dev, size_t* workspace_bytes,
+                           int device, void* stream);
 
 /* Fused attention kernel alone (bf16, head_dim 64 or 128): o[b,t,h*dh+d] = softmax(scale q k^T) v with q rows at
  * q + (b*t_len + t)*ldq + h*dh, k / v rows likewise with ldkv, o with ldo (element strides).  Replaces the eager

@@ -2315,6 +2315,116 @@ int svt_softmax(const float* x, int64_t rows, int32_t n, int32_t apply_log, floa
   return SVT_OK;
 }
 
+// ---- head-only training step (linear probe) ----
+// workspace_bytes is in / out: with workspace == NULL the size the call needs is stored and nothing else happens
+static int ws_query(const char* who, void* ws, size_t* ws_bytes, size_t need, bool* query) {
+  *query = false;
+  if (!ws_bytes) { set_error(std::string(who) + ": workspace_bytes is null"); return SVT_ERR_INVALID; }
+  if (!ws) { *ws_bytes = need; *query = true; return SVT_OK; }
+  if (*ws_bytes < need) {
+    set_error(std::string(who) + ": workspace too small (need " + std::to_string(need) + " bytes)");
+    return SVT_ERR_WORKSPACE;
+  }
+  return SVT_OK;
+}
+
+int svt_amt_objective_grad(const float* logits, int64_t batch, int64_t t_pred, int32_t n_out, int32_t pitch_octave_num,
+                           const float* onset_targets, const float* offset_targets, const int64_t* octave_targets,
+                           const int64_t* class_targets, int64_t t_tgt, const float* rel_len, float onset_pos_weight,
+                           int32_t allowed_len_diff, float label_smoothing, float* terms, float* terms_host, float* dlogits,
+                           void* workspace, size_t* workspace_bytes, int device, void* stream) {
+  const char* who = "svt_amt_objective_grad";
+  if (batch < 1 || t_pred < 1 || t_tgt < 1) { set_error(std::string(who) + ": empty input"); return SVT_ERR_INVALID; }
+  bool query = false;
+  if (int r = ws_query(who, workspace, workspace_bytes, amt_objective_workspace_bytes(batch), &query)) return r;
+  if (query) return SVT_OK;
+  if (!logits || !onset_targets || !offset_targets || !octave_targets || !class_targets || !terms || !dlogits) {
+    set_error(std::string(who) + ": null argument"); return SVT_ERR_INVALID;
+  }
+  if (n_out < 4 || n_out > 32) { set_error(std::string(who) + ": n_out must be in 4..32"); return SVT_ERR_INVALID; }
+  if (pitch_octave_num < 0 || n_out - 2 - (pitch_octave_num + 1) < 1) {
+    set_error(std::string(who) + ": n_out leaves no pitch-class column after onset, offset and pitch_octave_num + 1 octave columns");
+    return SVT_ERR_INVALID;
+  }
+  if (batch > 65535) { set_error(std::string(who) + ": batch must be <= 65535"); return SVT_ERR_INVALID; }
+  if (!std::isfinite(onset_pos_weight) || !std::isfinite(label_smoothing)) { set_error(std::string(who) + ": non-finite pos_weight or label_smoothing"); return SVT_ERR_INVALID; }
+  const int64_t diff = t_pred - t_tgt;
+  if ((diff < 0 ? -diff : diff) > allowed_len_diff) {
+    // same condition and wording as speechbrain.nnet.losses.truncate (losses.py:608-613)
+    set_error("Predictions and targets should be same length, but got " + std::to_string(t_pred) + " and " +
+              std::to_string(t_tgt) + " respectively.");
+    return SVT_ERR_INVALID;
+  }
+  const int64_t T = diff < 0 ? t_pred : t_tgt;
+  if (T > (int64_t(1) << 24)) { set_error(std::string(who) + ": more than 2^24 frames"); return SVT_ERR_INVALID; }
+  if (int r = check_device(device)) return r;
+  SVT_HIP(hipSetDevice(device));
+  hipStream_t s = (hipStream_t)stream;
+  if (launch_amt_objective_grad(logits, batch, t_pred, n_out, pitch_octave_num + 1, onset_targets, offset_targets, octave_targets,
+                                class_targets, t_tgt, T, rel_len, onset_pos_weight, label_smoothing, dlogits, terms, workspace, s))
+    return SVT_ERR_HIP;
+  // the one synchronisation of the training entry points: the target range is only known on the device
+  struct { int32_t bad; float terms[5]; } st;
+  SVT_HIP(hipMemcpyAsync(&st, (char*)workspace + amt_objective_status_offset(batch), sizeof(st), hipMemcpyDeviceToHost, s));
+  SVT_HIP(hipStreamSynchronize(s));
+  if (st.bad) {
+    set_error(std::string(who) + ": an octave or class target is outside [0, n_classes) and is not -100");
+    return SVT_ERR_INVALID;
+  }
+  if (terms_host) std::memcpy(terms_host, st.terms, sizeof(st.terms));
+  return SVT_OK;
+}
+
+int svt_linear_backward(const float* x, const float* dy, int64_t rows, int32_t in_features, int32_t out_features, float* dweight,
+                        float* dbias, void* workspace, size_t* workspace_bytes, int device, void* stream) {
+  const char* who = "svt_linear_backward";
+  if (out_features < 1 || out_features > 32) { set_error(std::string(who) + ": out_features must be in 1..32"); return SVT_ERR_INVALID; }
+  if (in_features < 4 || in_features % 4 != 0) { set_error(std::string(who) + ": in_features must be a positive multiple of 4"); return SVT_ERR_INVALID; }
+  if (rows < 1 || rows > 2147483647LL) { set_error(std::string(who) + ": rows must be in 1..2^31-1"); return SVT_ERR_INVALID; }
+  bool query = false;
+  if (int r = ws_query(who, workspace, workspace_bytes, linear_wgrad_workspace_bytes(rows, in_features, out_features), &query)) return r;
+  if (query) return SVT_OK;
+  if (!x || !dy || !dweight) { set_error(std::string(who) + ": null argument"); return SVT_ERR_INVALID; }
+  if (((uintptr_t)x | (uintptr_t)dweight | (uintptr_t)workspace) & 15) {
+    set_error(std::string(who) + ": x, dweight and workspace must be 16-byte aligned"); return SVT_ERR_INVALID;
+  }
+  if (int r = check_device(device)) return r;
+  SVT_HIP(hipSetDevice(device));
+  if (launch_linear_wgrad(x, dy, rows, in_features, out_features, dweight, dbias, workspace, (hipStream_t)stream)) return SVT_ERR_HIP;
+  return SVT_OK;
+}
+
+int svt_clip_adadelta_step(int32_t n_tensors, float* const* params, float* const* grads, float* const* square_avg,
+                           float* const* acc_delta, const int64_t* numels, float lr, double rho, float eps, float weight_decay,
+                           int32_t maximize, float max_norm, float* total_norm, void* workspace, size_t* workspace_bytes, int device,
+                           void* stream) {
+  const char* who = "svt_clip_adadelta_step";
+  if (n_tensors < 1 || n_tensors > kAdaMaxTensors) {
+    set_error(std::string(who) + ": n_tensors must be in 1.." + std::to_string(kAdaMaxTensors)); return SVT_ERR_INVALID;
+  }
+  if (!numels) { set_error(std::string(who) + ": null argument"); return SVT_ERR_INVALID; }
+  for (int i = 0; i < n_tensors; ++i)
+    if (numels[i] < 0) { set_error(std::string(who) + ": negative numel"); return SVT_ERR_INVALID; }
+  bool query = false;
+  if (int r = ws_query(who, workspace, workspace_bytes, ada_workspace_bytes(numels, n_tensors), &query)) return r;
+  if (query) return SVT_OK;
+  if (!params || !grads || !square_avg || !acc_delta) { set_error(std::string(who) + ": null argument"); return SVT_ERR_INVALID; }
+  for (int i = 0; i < n_tensors; ++i)
+    if (numels[i] > 0 && (!params[i] || !grads[i] || !square_avg[i] || !acc_delta[i])) {
+      set_error(std::string(who) + ": null tensor pointer"); return SVT_ERR_INVALID;
+    }
+  if (!(rho >= 0.0 && rho <= 1.0) || !(eps >= 0.f) || !(lr >= 0.f) || !(weight_decay >= 0.f) || std::isnan(max_norm)) {
+    set_error(std::string(who) + ": lr, eps and weight_decay must be >= 0 and rho in [0, 1]"); return SVT_ERR_INVALID;
+  }
+  if (int r = check_device(device)) return r;
+  SVT_HIP(hipSetDevice(device));
+  // torch scales by (1 - rho) as a Python float, i.e. computed in double before the fp32 multiply
+  if (launch_clip_adadelta(n_tensors, params, grads, square_avg, acc_delta, numels, lr, (float)rho, (float)(1.0 - rho), eps, weight_decay,
+                           maximize ? 1 : 0, max_norm, total_norm, workspace, (hipStream_t)stream))
+    return SVT_ERR_HIP;
+  return SVT_OK;
+}
+
 }  // extern "C"
 
 namespace {

@@ -457,6 +457,22 @@ int launch_nll_loss(const float* logp, int64_t B, int64_t t_pred, int C, const i
                     const float* rel_len, float* per_frame, double* sums, int* bad_target, hipStream_t s);
 int launch_loss_reduce(const double* sums, int B, int reduction, float smoothing, float* out, hipStream_t s);
 int launch_softmax_small(const float* x, int64_t rows, int n, int apply_log, float* y, hipStream_t s);
+// head-only training step (train.hip): the recipe's objective + d/dlogits, the head's weight gradient, clip_grad_norm_ + Adadelta
+int launch_amt_objective_grad(const float* x, int64_t B, int64_t t_pred, int n_out, int n_oct_cols, const float* on_t,
+                              const float* off_t, const int64_t* oct_t, const int64_t* cls_t, int64_t t_tgt, int64_t T,
+                              const float* rel_len, float pos_weight, float smoothing, float* dx, float* terms, void* ws,
+                              hipStream_t s);
+size_t amt_objective_status_offset(int64_t B);   // {int32 bad target, float terms[5]} at this byte offset of the workspace
+size_t amt_objective_workspace_bytes(int64_t B);
+int64_t linear_wgrad_slabs(int64_t rows, int D);
+size_t linear_wgrad_workspace_bytes(int64_t rows, int D, int N);
+int launch_linear_wgrad(const float* x, const float* dy, int64_t rows, int D, int N, float* dw, float* db, void* ws, hipStream_t s);
+constexpr int kAdaMaxTensors = 16;   // tensors per svt_clip_adadelta_step call
+constexpr int64_t kAdaChunk = 4096;  // elements per sum-of-squares partial
+size_t ada_workspace_bytes(const int64_t* numels, int count);
+int launch_clip_adadelta(int count, float* const* params, float* const* grads, float* const* square_avg, float* const* acc_delta,
+                         const int64_t* numels, float lr, float rho, float one_minus_rho, float eps, float weight_decay, int maximize,
+                         float max_norm, float* total_norm, void* ws, hipStream_t s);
 bool linear_head_eligible(int K, int N);
 int launch_linear_head(const float* x, int64_t rows, int K, const float* w, const float* b, int N, float* y, hipStream_t s);
 struct FrameOut { float p_on, p_off; int32_t octave, pitch_class; };

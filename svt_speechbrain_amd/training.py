@@ -1,0 +1,340 @@
+"""The linear-probe stage of the recipes on the GPU: ``AMT.fit_batch`` with the wav2vec2 encoder frozen and only the 20-way
+``Linear`` head learning (``MIR_ST500/train_audio_ssl.py:192-199``, the first ``linear_prob_epochs``; the whole run with
+``freeze_wav2vec: True``).
+
+One step is the frozen encoder forward (the existing hot path), the head forward, then three HIP kernels of ``csrc/train.hip``:
+the recipe's objective and its gradient w.r.t. the logits in one pass (``compute_objectives``, ``train_audio_ssl.py:50-76``), the head's
+weight gradient, and ``Brain.check_gradients``' clip (``speechbrain/core.py:882-923``) fused with ``torch.optim.Adadelta``'s update.
+Nothing is computed by torch and there is no CPU fallback.  The encoder's backward (full fine-tuning) is out of scope.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import math
+from typing import Dict, Optional
+
+import torch
+
+from . import _lib
+from .amt import AMTForward
+
+TERMS = ("onset", "offset", "octave", "pitch")
+_MAX_TENSORS = 16   # tensors per svt_clip_adadelta_step call (csrc/common.h kAdaMaxTensors)
+
+
+def _workspace(query, device) -> torch.Tensor:
+    """Run a size query (a call with workspace NULL) and allocate that many bytes on ``device``."""
+    n = C.c_size_t(0)
+    query(n)
+    return torch.empty(max(16, int(n.value)), dtype=torch.uint8, device=device)
+
+
+def _bump(t: torch.Tensor) -> None:
+    """A kernel wrote ``t`` through its pointer: advance its version counter so every cached upload of it (``Linear._sync``,
+    the fused tail) sees a change."""
+    torch.autograd.graph.increment_version(t)
+
+
+def clip_adadelta_step(params, grads, square_avgs, acc_deltas, lr: float, rho: float, eps: float, weight_decay: float = 0.0,
+                       maximize: bool = False, max_norm: float = 0.0, total_norm: Optional[torch.Tensor] = None) -> None:
+    """``clip_grad_norm_(grads, max_norm)`` (when ``max_norm > 0``) then one Adadelta update of every parameter, in one call of
+    ``svt_clip_adadelta_step``.  All tensors contiguous fp32 on one GPU; ``total_norm`` (0-d fp32 on that GPU) receives the pre-clip
+    norm."""
+    if len(params) > _MAX_TENSORS:
+        raise _lib.SvtError(f"clip_adadelta_step: at most {_MAX_TENSORS} tensors per call")
+    dev = params[0].device
+    for group in (params, grads, square_avgs, acc_deltas):
+        for t in group:
+            if not t.is_cuda:
+                raise _lib.SvtError("Adadelta needs its parameters on the GPU; there is no CPU fallback")
+            if t.dtype != torch.float32 or not t.is_contiguous() or t.device != dev:
+                raise _lib.SvtError("Adadelta: parameters, gradients and state must be contiguous fp32 tensors on one device")
+    lib = _lib.load()
+    n = len(params)
+    arr = C.c_void_p * n
+    pp, gg, ss, aa = (arr(*[_lib.ptr(t) for t in g]) for g in (params, grads, square_avgs, acc_deltas))
+    numels = (C.c_int64 * n)(*[t.numel() for t in params])
+    idx, stream = _lib.dev_index(dev), _lib.stream_ptr(dev)
+
+    def call(ws, nbytes):
+        return lib.svt_clip_adadelta_step(n, pp, gg, ss, aa, numels, float(lr), float(rho), float(eps), float(weight_decay), int(maximize),
+                                          float(max_norm), _lib.ptr(total_norm) if total_norm is not None else None, ws, nbytes, idx,
+                                          stream)
+
+    ws = _workspace(lambda nb: _lib.check(call(None, nb), "svt_clip_adadelta_step"), dev)
+    nbytes = C.c_size_t(ws.numel())
+    _lib.check(call(_lib.ptr(ws), C.byref(nbytes)), "svt_clip_adadelta_step")
+    for t in params:
+        _bump(t)
+    if max_norm > 0:
+        for t in grads:
+            _bump(t)
+
+
+def amt_objective_grad(logits, onset, offset, octave, pitch_class, rel_len=None, onset_pos_weight: float = 15.0,
+                       pitch_octave_num: int = 4, allowed_len_diff: int = 3, label_smoothing: float = 0.0, workspace=None):
+    """The recipe's objective and its gradient (``svt_amt_objective_grad``): ``logits`` (B, T, n_out) fp32 on the GPU, targets
+    (B, T') -- onset / offset float, octave / class int64 (-100 ignored) -- and relative lengths (B,) or None.  Returns
+    ``(terms, dlogits, host)``: ``terms`` the device (5,) {onset, offset, octave, pitch, sum}, ``dlogits`` d(sum)/d(logits), ``host``
+    the five terms as Python floats.  Raises ``ValueError`` for a length difference beyond ``allowed_len_diff`` (the reference's
+    message) and ``SvtError`` for every other refusal (n_out > 32, a target out of range, ...)."""
+    if not logits.is_cuda:
+        raise _lib.SvtError("amt_objective_grad needs GPU tensors; there is no CPU fallback")
+    lib = _lib.load()
+    dev = logits.device
+    idx, stream = _lib.dev_index(dev), _lib.stream_ptr(dev)
+    x = logits.detach().to(torch.float32).contiguous()
+    if x.dim() != 3:
+        raise ValueError(f"logits must be (batch, frames, n_out), got {tuple(x.shape)}")
+    B, tp, n_out = x.shape
+    on_t = onset.detach().to(device=dev, dtype=torch.float32).contiguous()
+    off_t = offset.detach().to(device=dev, dtype=torch.float32).contiguous()
+    oct_t = octave.detach().to(device=dev, dtype=torch.int64).contiguous()
+    cls_t = pitch_class.detach().to(device=dev, dtype=torch.int64).contiguous()
+    tt = on_t.shape[1]
+    for t in (on_t, off_t, oct_t, cls_t):
+        if t.shape != (B, tt):
+            raise ValueError(f"targets must all be (batch, frames) = ({B}, {tt}), got {tuple(t.shape)}")
+    ln = None
+    if rel_len is not None:
+        ln = torch.as_tensor(rel_len, dtype=torch.float32, device=dev).reshape(-1).contiguous()
+        if ln.numel() != B:
+            raise ValueError(f"rel_len has {ln.numel()} entries for a batch of {B}")
+    terms = torch.empty(5, dtype=torch.float32, device=dev)
+    dlogits = torch.empty_like(x)
+    host = (C.c_float * 5)()
+
+    def call(ws, nbytes):
+        return lib.svt_amt_objective_grad(_lib.ptr(x), B, tp, n_out, int(pitch_octave_num), _lib.ptr(on_t), _lib.ptr(off_t),
+                                          _lib.ptr(oct_t), _lib.ptr(cls_t), tt, _lib.ptr(ln) if ln is not None else None,
+                                          float(onset_pos_weight), int(allowed_len_diff), float(label_smoothing), _lib.ptr(terms), host,
+                                          _lib.ptr(dlogits), ws, nbytes, idx, stream)
+
+    def query(nb):
+        _lib.check(call(None, nb), "svt_amt_objective_grad")
+
+    ws = workspace(query) if workspace is not None else _workspace(query, dev)
+    nb = C.c_size_t(ws.numel())
+    rc = call(_lib.ptr(ws), C.byref(nb))
+    if rc != 0:
+        msg = _lib.last_error()
+        if "same length" in msg:
+            raise ValueError(msg)   # speechbrain.nnet.losses.truncate's error
+        _lib.check(rc, "svt_amt_objective_grad")
+    return terms, dlogits, [float(v) for v in host]
+
+
+def linear_backward(x: torch.Tensor, dy: torch.Tensor, dweight: Optional[torch.Tensor] = None, dbias: Optional[torch.Tensor] = None,
+                    with_bias: bool = True, workspace=None):
+    """``svt_linear_backward``: dweight = dy^T x (out, in) and dbias = dy summed over rows, for x (rows, in) and dy (rows, out)
+    fp32 on the GPU.  Writes into ``dweight`` / ``dbias`` when given (contiguous fp32), else allocates; returns both."""
+    if not x.is_cuda:
+        raise _lib.SvtError("linear_backward needs GPU tensors; there is no CPU fallback")
+    lib = _lib.load()
+    dev = x.device
+    xx = x.detach().to(torch.float32).contiguous()
+    dd = dy.detach().to(device=dev, dtype=torch.float32).contiguous()
+    rows, d_in = xx.shape
+    d_out = dd.shape[1]
+    if dd.shape[0] != rows:
+        raise ValueError(f"x has {rows} rows, dy {dd.shape[0]}")
+    if dweight is None:
+        dweight = torch.empty((d_out, d_in), dtype=torch.float32, device=dev)
+    if dbias is None and with_bias:
+        dbias = torch.empty((d_out,), dtype=torch.float32, device=dev)
+    idx, stream = _lib.dev_index(dev), _lib.stream_ptr(dev)
+
+    def call(ws, nbytes):
+        return lib.svt_linear_backward(_lib.ptr(xx), _lib.ptr(dd), rows, d_in, d_out, _lib.ptr(dweight),
+                                       _lib.ptr(dbias) if dbias is not None else None, ws, nbytes, idx, stream)
+
+    def query(nb):
+        _lib.check(call(None, nb), "svt_linear_backward")
+
+    ws = workspace(query) if workspace is not None else _workspace(query, dev)
+    nb = C.c_size_t(ws.numel())
+    _lib.check(call(_lib.ptr(ws), C.byref(nb)), "svt_linear_backward")
+    return dweight, dbias
+
+
+class Adadelta(torch.optim.Optimizer):
+    """``torch.optim.Adadelta`` on GPU parameters, updated by a HIP kernel: same constructor, same ``param_groups`` and the same
+    ``state_dict()`` (per parameter ``step``, ``square_avg``, ``acc_delta``), so a checkpoint moves both ways and a scheduler that sets
+    ``param_groups[i]["lr"]`` (SpeechBrain's ``NewBobScheduler``) works unchanged.  fp32 parameters only; CPU parameters raise
+    ``SvtError``."""
+
+    def __init__(self, params, lr=1.0, rho=0.9, eps=1e-6, weight_decay=0, foreach=None, *, capturable=False, maximize=False,
+                 differentiable=False):
+        if isinstance(lr, torch.Tensor) and lr.numel() != 1:
+            raise ValueError("Tensor lr must be 1-element")
+        if not 0.0 <= float(lr):
+            raise ValueError(f"Invalid learning rate: {lr}")
+        if not 0.0 <= rho <= 1.0:
+            raise ValueError(f"Invalid rho value: {rho}")
+        if not 0.0 <= eps:
+            raise ValueError(f"Invalid epsilon value: {eps}")
+        if not 0.0 <= weight_decay:
+            raise ValueError(f"Invalid weight_decay value: {weight_decay}")
+        if differentiable:
+            raise NotImplementedError("Adadelta: differentiable=True is not provided (the update is a HIP kernel)")
+        defaults = dict(lr=lr, rho=rho, eps=eps, weight_decay=weight_decay, maximize=maximize, capturable=capturable, foreach=foreach,
+                        differentiable=differentiable)
+        super().__init__(params, defaults)
+
+    def _group_tensors(self, group):
+        params, grads, sqs, accs = [], [], [], []
+        for p in group["params"]:
+            if p.grad is None:
+                continue
+            if p.grad.is_sparse:
+                raise RuntimeError("Adadelta does not support sparse gradients")
+            if not p.is_cuda:
+                raise _lib.SvtError("svt_speechbrain_amd.Adadelta needs its parameters on the GPU; there is no CPU fallback")
+            state = self.state[p]
+            if len(state) == 0:
+                state["step"] = torch.tensor(0.0, dtype=torch.float32)
+                state["square_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                state["acc_delta"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+            params.append(p)
+            grads.append(p.grad if p.grad.is_contiguous() else p.grad.contiguous())
+            sqs.append(state["square_avg"])
+            accs.append(state["acc_delta"])
+        return params, grads, sqs, accs
+
+    @torch.no_grad()
+    def step(self, closure=None, max_norm: float = 0.0, total_norm: Optional[torch.Tensor] = None):
+        """One Adadelta update.  ``max_norm > 0`` (extension) first clips the gradients of ALL parameters of the optimizer by their
+        global norm as ``clip_grad_norm_`` does, in the same kernel call (one param group of at most 16 tensors)."""
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        if max_norm > 0 and len(self.param_groups) != 1:
+            raise NotImplementedError("Adadelta.step(max_norm=...): one param group only")
+        for group in self.param_groups:
+            params, grads, sqs, accs = self._group_tensors(group)
+            if not params:
+                continue
+            if max_norm > 0 and len(params) > _MAX_TENSORS:
+                raise NotImplementedError(f"Adadelta.step(max_norm=...): at most {_MAX_TENSORS} parameters")
+            for p in params:
+                self.state[p]["step"] += 1
+            lr = float(group["lr"])
+            for i in range(0, len(params), _MAX_TENSORS):
+                sl = slice(i, i + _MAX_TENSORS)
+                clip_adadelta_step(params[sl], grads[sl], sqs[sl], accs[sl], lr, group["rho"], group["eps"], group["weight_decay"],
+                                   group["maximize"], max_norm, total_norm)
+        return loss
+
+
+class LinearProbe:
+    """``AMT.fit_batch`` of the linear-probe stage with the encoder frozen (``train_audio_ssl.py:28-76`` + ``Brain.fit_batch`` /
+    ``check_gradients``, ``speechbrain/core.py:850-923``).  ``modules`` is the recipe's mapping (``wav2vec2`` + ``model``, as for
+    ``AMTForward``); the hparams carry the recipe's names.  The head, its gradients and the optimizer state are fp32 whatever the
+    encoder's ``precision``.
+
+    After ``fit_batch`` / ``fit_features``: ``head.w.weight.grad`` / ``.bias.grad`` hold the (clipped) gradients the step used,
+    ``last_terms`` the four loss terms, ``last_grad_norm`` the pre-clip norm, and ``head.state_dict()`` the new parameters (every later
+    ``head(...)`` or fused tail uploads them).  A non-finite loss skips the step (gradients set to None, parameters untouched); the
+    ``nonfinite_patience + 1``-th skip since ``on_epoch_start()`` raises ``ValueError``, as ``check_gradients`` does."""
+
+    def __init__(self, modules, optimizer: Optional[Adadelta] = None, lr: float = 3e-4, rho: float = 0.95, eps: float = 1e-8,
+                 onset_positive_weight: float = 15.0, pitch_octave_num: int = 4, pitch_class_num: int = 12, max_grad_norm: float = 5.0,
+                 nonfinite_patience: int = 3, allowed_len_diff: int = 3, label_smoothing: float = 0.0):
+        self.amt = AMTForward(modules, pitch_octave_num=pitch_octave_num, pitch_class_num=pitch_class_num)
+        self.head = self.amt._head(False)
+        self.onset_positive_weight = float(onset_positive_weight)
+        self.pitch_octave_num = int(pitch_octave_num)
+        self.pitch_class_num = int(pitch_class_num)
+        self.max_grad_norm = float(max_grad_norm)
+        self.nonfinite_patience = int(nonfinite_patience)
+        self.allowed_len_diff = int(allowed_len_diff)
+        self.label_smoothing = float(label_smoothing)
+        if optimizer is None:
+            optimizer = Adadelta(self.head.parameters(), lr=lr, rho=rho, eps=eps)
+        if not isinstance(optimizer, Adadelta):
+            raise TypeError("LinearProbe needs svt_speechbrain_amd.training.Adadelta (the clip is fused into its kernel)")
+        self.optimizer = optimizer
+        self.nonfinite_count = 0
+        self.last_terms: Dict[str, float] = {}
+        self.last_grad_norm: Optional[torch.Tensor] = None
+        self._ws: Dict[tuple, torch.Tensor] = {}
+
+    def on_epoch_start(self) -> None:
+        """Reset the non-finite counter, as ``Brain`` does at the start of every epoch (``core.py`` ``_fit_train``)."""
+        self.nonfinite_count = 0
+
+    def _scratch(self, key, query, device) -> torch.Tensor:
+        n = C.c_size_t(0)
+        query(n)
+        ws = self._ws.get(key)
+        if ws is None or ws.numel() < int(n.value) or ws.device != device:
+            ws = torch.empty(max(16, int(n.value)), dtype=torch.uint8, device=device)
+            self._ws[key] = ws
+        return ws
+
+    def fit_batch(self, wavs: torch.Tensor, wav_lens: Optional[torch.Tensor], anno: torch.Tensor,
+                  anno_lens: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """One training step from waveforms: the frozen encoder, then ``fit_features``."""
+        with torch.no_grad():
+            feats = self.amt._get("wav2vec2")(wavs)
+        return self.fit_features(feats, wav_lens, anno, anno_lens)
+
+    def fit_features(self, feats: torch.Tensor, wav_lens: Optional[torch.Tensor], anno: torch.Tensor,
+                     anno_lens: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """One training step from the frozen encoder's output (B, T, D), e.g. features saved by ``song.save_song_features``.
+        ``anno`` (B, T', 4): onset, offset, octave, pitch class per frame (``batch.anno``); the mask is ``wav_lens`` as in
+        ``compute_objectives`` (``anno_lens`` is accepted for the recipe's signature and not used there either).  Returns the
+        detached 0-d loss on the CPU, as ``Brain.fit_batch``."""
+        if not feats.is_cuda:
+            raise _lib.SvtError("LinearProbe needs its features on the GPU; there is no CPU fallback")
+        head = self.head
+        dev = feats.device
+        x = feats.detach().to(torch.float32).contiguous()
+        if x.dim() != 3 or x.shape[-1] != head.w.in_features:
+            raise ValueError(f"features must be (batch, frames, {head.w.in_features}), got {tuple(x.shape)}")
+        B, tp, D = x.shape
+        logits = head(x)
+        n_out = logits.shape[-1]
+        a = anno.to(dev)
+        if a.dim() != 3 or a.shape[0] != B or a.shape[2] < 4:
+            raise ValueError(f"anno must be (batch, frames, 4), got {tuple(anno.shape)}")
+        on_t = a[:, :, 0].to(torch.float32).contiguous()
+        off_t = a[:, :, 1].to(torch.float32).contiguous()
+        oct_t = a[:, :, 2].to(torch.int64).contiguous()
+        cls_t = a[:, :, 3].to(torch.int64).contiguous()
+        tt = a.shape[1]
+        ln = None
+        if wav_lens is not None:
+            ln = torch.as_tensor(wav_lens, dtype=torch.float32, device=dev).reshape(-1).contiguous()
+            if ln.numel() != B:
+                raise ValueError(f"wav_lens has {ln.numel()} entries for a batch of {B}")
+        terms, dlogits, host = amt_objective_grad(logits, on_t, off_t, oct_t, cls_t, ln, self.onset_positive_weight,
+                                                  self.pitch_octave_num, self.allowed_len_diff, self.label_smoothing,
+                                                  workspace=lambda q: self._scratch("obj", q, dev))
+        self.last_terms = dict(zip(TERMS, host[:4]))
+        loss = terms[4]
+        if not math.isfinite(float(host[4])):
+            # Brain.check_gradients: skip the step, count it, raise once the patience is spent
+            self.nonfinite_count += 1
+            head.w.weight.grad = None
+            if head.w.bias is not None:
+                head.w.bias.grad = None
+            if self.nonfinite_count > self.nonfinite_patience:
+                raise ValueError("Loss is not finite and patience is exhausted. To debug, wrap `fit()` with autograd's "
+                                 "`detect_anomaly()`, e.g.\n\nwith torch.autograd.detect_anomaly():\n\tbrain.fit(...)")
+            return loss.detach().cpu()
+        w, b = head.w.weight, head.w.bias
+        if w.grad is None or w.grad.shape != w.shape or not w.grad.is_contiguous():
+            w.grad = torch.empty_like(w, memory_format=torch.contiguous_format)
+        if b is not None and (b.grad is None or b.grad.shape != b.shape):
+            b.grad = torch.empty_like(b)
+
+        linear_backward(x.reshape(B * tp, D), dlogits.reshape(B * tp, n_out), w.grad, b.grad if b is not None else None,
+                        workspace=lambda q: self._scratch("wgrad", q, dev))
+        _bump(w.grad)
+        if b is not None:
+            _bump(b.grad)
+        self.last_grad_norm = torch.empty((), dtype=torch.float32, device=dev)
+        self.optimizer.step(max_norm=self.max_grad_norm, total_norm=self.last_grad_norm)
+        return loss.detach().cpu()
