@@ -194,6 +194,24 @@ int64_t svt_rca_workspace_bytes(const svt_rca* r, int32_t batch, int32_t t_audio
 int svt_rca_forward(svt_rca* r, const float* audio_dev, int32_t t_audio, const float* video_dev,
                     int32_t t_video, int32_t batch, float* out_dev, void* workspace_dev,
                     size_t workspace_bytes, void* stream);
+/* Training step of FusionRCA + head on frozen features (N20EMv2/audio_visual/train_rca_av.py:174-185); precision fp32 or bf16, head
+ * size 64 or 128 (otherwise SVT_ERR_INVALID).  The 24 fusion tensors are in this order, for layer1 then layer2: self_att.att.
+ * in_proj_weight, in_proj_bias, out_proj.weight, out_proj.bias, pos_ffn.ffn.0.weight, .0.bias, .3.weight, .3.bias, norm1.norm.weight,
+ * .bias, norm2.norm.weight, .bias (the positional table is not trainable).  No entry point below synchronises or copies.
+ *
+ * svt_rca_refresh_params: rewrites the handle's weights on `stream` from params_dev (24 device fp32 tensors) -- the operand-format
+ * copies the forward reads, with the bits a fresh svt_rca_load_param + svt_rca_finalize gives, and the transposed copies the backward
+ * needs.  Required once after every svt_rca_finalize before svt_rca_backward.  Unlike svt_rca_finalize it does not wait for forwards
+ * in flight: the caller orders it after every forward on other streams that reads this handle (replica lanes included). */
+int svt_rca_refresh_params(svt_rca* r, const float* const* params_dev, int32_t n, void* stream);
+int64_t svt_rca_train_workspace_bytes(const svt_rca* r, int32_t batch, int32_t t_audio);
+/* the kernels of svt_rca_forward (the same output bits), keeping in the workspace what svt_rca_backward reads */
+int svt_rca_forward_train(svt_rca* r, const float* audio_dev, int32_t t_audio, const float* video_dev, int32_t t_video, int32_t batch,
+                          float* out_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
+/* d(out) (B,T1,D) f32 -> the 24 gradients (overwritten, fp32, in the order above), from the workspace of the last
+ * svt_rca_forward_train with the same batch / t_audio.  No float atomics: two calls give the same bits. */
+int svt_rca_backward(svt_rca* r, const float* dout_dev, int32_t batch, int32_t t_audio, float* const* grads_dev, void* workspace_dev,
+                     size_t workspace_bytes, void* stream);
 
 /* ---- CTC greedy: replaces speechbrain.decoders.ctc.ctc_greedy_decode (ctc.py:341-383) ----
  * probs (B,T,V) f32, rel_lens (B,) f32 (device).  tokens_dev (B,T) i32 receives the collapsed, blank-free
@@ -323,7 +341,11 @@ int svt_amt_objective_grad(const float* logits_dev, int64_t batch, int64_t t_pre
  * x / dweight / workspace 16-byte aligned.  Overwrites (does not accumulate into) dweight / dbias.  No dx. */
 int svt_linear_backward(const float* x_dev, const float* dy_dev, int64_t rows, int32_t in_features, int32_t out_features,
                         float* dweight_dev, float* dbias_dev, void* workspace_dev, size_t* workspace_bytes, int device, void* stream);
-/* torch.nn.utils.clip_grad_norm_ over n_tensors (<= 16) f32 gradient tensors -- total = ||[||g_i||]||, every g_i *= min(max_norm /
+/* The data half of a Linear layer's backward: dx (rows, in_features) = dy (rows, out_features) weight (out_features, in_features), all
+ * f32; in_features a multiple of 4, weight / dx 16-byte aligned.  Overwrites dx. */
+int svt_linear_backward_data(const float* dy_dev, const float* weight_dev, int64_t rows, int32_t in_features, int32_t out_features,
+                             float* dx_dev, int device, void* stream);
+/* torch.nn.utils.clip_grad_norm_ over n_tensors (<= 32) f32 gradient tensors -- total = ||[||g_i||]||, every g_i *= min(max_norm /
  * (total + 1e-6), 1) in place -- when max_norm > 0, then torch.optim.Adadelta's update of each parameter (single-tensor form, torch's
  * order of operations; maximize / weight_decay as torch).  All pointer arrays are HOST arrays of device pointers, numels a host array.
  * total_norm_dev (one float, may be NULL) receives the pre-clip total norm. */
@@ -339,6 +361,18 @@ int svt_clip_adadelta_step(int32_t n_tensors, float* const* params_dev, float* c
 int svt_debug_attention(int32_t precision, const void* q, const void* k, const void* v, void* o, int32_t batch, int32_t t,
                         int32_t heads, int32_t head_dim, int64_t ldq, int64_t ldkv, int64_t ldo, float scale, int device,
                         void* stream);
+/* The RCA training kernels alone (tests/test_gpu_fusion_train.py), precision 0 (fp32) or 1 (bf16 operands); workspace convention of
+ * svt_linear_backward.  svt_debug_rca_wgrad: dw (n_out, n_in) = sum over the rows of one or two segments of dy_s^T x_s (dy f32 with row
+ * strides ldy_s, x operand type (rows, n_in); dy1 / x1 NULL for one segment), db (may be NULL) = the column sums of dy.
+ * svt_debug_rca_attn_bwd: for qkv (B*t, 3D) = [q_s | k | v] and qc (B*t, D) in the operand type, the attention outputs o_self / o_cross
+ * and d(blend) (B*t, D) f32 with d o_self = alpha d blend, d o_cross = (1 - alpha) d blend: dqkv (B*t, 3D) = [dq_s | dk | dv] and
+ * dqc (B*t, D), f32; head_dim 64 or 128. */
+int svt_debug_rca_wgrad(int32_t precision, const float* dy0, int64_t ldy0, const void* x0, const float* dy1, int64_t ldy1, const void* x1,
+                        int64_t rows, int32_t n_out, int32_t n_in, float* dw, float* db, void* workspace_dev, size_t* workspace_bytes,
+                        int device, void* stream);
+int svt_debug_rca_attn_bwd(int32_t precision, const void* qkv, const void* qc, const void* o_self, const void* o_cross,
+                           const float* dblend, float alpha, int32_t batch, int32_t t, int32_t heads, int32_t head_dim, float* dqkv,
+                           float* dqc, void* workspace_dev, size_t* workspace_bytes, int device, void* stream);
 /* Diagnostics switches of the contraction kernels (tools/gemm_bench.py, tools/gemm_trace.py; never needed in production), by key:
  * 0 = kernel ablation variant, 1 = force the tile height (64/128/192/256), 2 = force the one-tile (2) / persistent (4) scheduler,
  * 3 = ablation variant while tracing (50-79: force gemm_pps_kernel), 5 = retired (the fused out-projection + LayerNorm kernel of

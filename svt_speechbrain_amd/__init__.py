@@ -17,10 +17,10 @@ from .video import FairseqAVHubertPretrain, EvalTransform  # noqa: F401
 from .song import (SongTranscriber, utterance_bounds, save_song_features, feature_path, song_video_features,  # noqa: F401
                    save_song_video_features, video_feature_path)
 from . import training  # noqa: F401
-from .training import Adadelta, LinearProbe  # noqa: F401
+from .training import Adadelta, LinearProbe, FusionTrainer  # noqa: F401
 
 __all__ = ["EncoderConfig", "PRESETS", "config_from_source", "HuggingFaceWav2Vec2", "Linear", "FusionRCA", "Fbank",
            "decode_frames", "frame2note", "frames2note", "frames2note_batch", "frames_to_info", "ctc_greedy_decode", "filter_ctc_output", "AMTForward",
            "SongTranscriber", "utterance_bounds", "save_song_features", "feature_path", "song_video_features",
            "save_song_video_features", "video_feature_path", "EvalTransform", "FairseqAVHubertPretrain",
-           "Adadelta", "LinearProbe"]
+           "Adadelta", "LinearProbe", "FusionTrainer"]

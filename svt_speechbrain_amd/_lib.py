@@ -88,6 +88,10 @@ SYMBOLS = {
     "svt_rca_finalize": (C.c_int, [_P]),
     "svt_rca_workspace_bytes": (C.c_int64, [_P, C.c_int32, C.c_int32]),
     "svt_rca_forward": (C.c_int, [_P, _P, C.c_int32, _P, C.c_int32, C.c_int32, _P, _P, C.c_size_t, _P]),
+    "svt_rca_refresh_params": (C.c_int, [_P, C.POINTER(_P), C.c_int32, _P]),
+    "svt_rca_train_workspace_bytes": (C.c_int64, [_P, C.c_int32, C.c_int32]),
+    "svt_rca_forward_train": (C.c_int, [_P, _P, C.c_int32, _P, C.c_int32, C.c_int32, _P, _P, C.c_size_t, _P]),
+    "svt_rca_backward": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.POINTER(_P), _P, C.c_size_t, _P]),
     "svt_ctc_greedy": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32, _P, _P, C.c_int, _P]),
     "svt_fbank_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32]),
     "svt_fbank": (C.c_int, [_P, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
@@ -118,11 +122,16 @@ SYMBOLS = {
     "svt_amt_objective_grad": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int32, C.c_int32, _P, _P, _P, _P, C.c_int64, _P, C.c_float,
                                          C.c_int32, C.c_float, _P, C.POINTER(C.c_float), _P, _P, C.POINTER(C.c_size_t), C.c_int, _P]),
     "svt_linear_backward": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int32, _P, _P, _P, C.POINTER(C.c_size_t), C.c_int, _P]),
+    "svt_linear_backward_data": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int32, _P, C.c_int, _P]),
     "svt_clip_adadelta_step": (C.c_int, [C.c_int32, C.POINTER(_P), C.POINTER(_P), C.POINTER(_P), C.POINTER(_P), _I64P, C.c_float,
                                          C.c_double, C.c_float, C.c_float, C.c_int32, C.c_float, _P, _P, C.POINTER(C.c_size_t), C.c_int,
                                          _P]),
     "svt_debug_attention": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
                                       C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_float, C.c_int, C.c_void_p]),
+    "svt_debug_rca_wgrad": (C.c_int, [C.c_int32, _P, C.c_int64, _P, _P, C.c_int64, _P, C.c_int64, C.c_int32, C.c_int32, _P, _P, _P,
+                                      C.POINTER(C.c_size_t), C.c_int, _P]),
+    "svt_debug_rca_attn_bwd": (C.c_int, [C.c_int32, _P, _P, _P, _P, _P, C.c_float, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P,
+                                         _P, C.POINTER(C.c_size_t), C.c_int, _P]),
     "svt_debug_set": (C.c_int, [C.c_int, C.c_int]),
     "svt_debug_clock": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "svt_debug_encoder_layout": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.POINTER(C.c_int64), C.c_int]),

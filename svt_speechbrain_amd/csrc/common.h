@@ -467,12 +467,57 @@ size_t amt_objective_workspace_bytes(int64_t B);
 int64_t linear_wgrad_slabs(int64_t rows, int D);
 size_t linear_wgrad_workspace_bytes(int64_t rows, int D, int N);
 int launch_linear_wgrad(const float* x, const float* dy, int64_t rows, int D, int N, float* dw, float* db, void* ws, hipStream_t s);
-constexpr int kAdaMaxTensors = 16;   // tensors per svt_clip_adadelta_step call
+constexpr int kAdaMaxTensors = 32;   // tensors per svt_clip_adadelta_step call
 constexpr int64_t kAdaChunk = 4096;  // elements per sum-of-squares partial
 size_t ada_workspace_bytes(const int64_t* numels, int count);
 int launch_clip_adadelta(int count, float* const* params, float* const* grads, float* const* square_avg, float* const* acc_delta,
                          const int64_t* numels, float lr, float rho, float one_minus_rho, float eps, float weight_decay, int maximize,
                          float max_norm, float* total_norm, void* ws, hipStream_t s);
+// RCA training step (train_rca.hip): weight refresh, attention statistics and backward, LayerNorm backward, weight gradients
+struct RcaRefreshJob {
+  const float* src;   // rows x cols fp32
+  void* dst;          // operand type (or fp32 with f32), rows x cols or (transpose) cols x rows
+  int64_t rows, cols;
+  int transpose, f32;
+};
+constexpr int kRcaMaxRefreshJobs = 32;
+struct RcaRefreshJobs {
+  RcaRefreshJob j[kRcaMaxRefreshJobs];
+  int n;
+};
+int launch_rca_refresh(int prec, const RcaRefreshJobs& jobs, hipStream_t s);
+int launch_rca_attn_lse(int prec, const void* Q, long ldq, const void* K, long ldk, int B, int T, int H, int dh, float scale, float* lse,
+                        hipStream_t s);   // lse (B, H, T) fp32
+struct RcaAttnBwd {
+  const void *q[2], *k, *v, *o[2];   // operand type; q[0] / o[0]: self attention, q[1] / o[1]: cross attention (o row stride H * dh)
+  long ldq[2], ldkv;
+  const float* dbl;                  // d(blend) (B*T, H*dh) fp32: dO of stream s is coef[s] * dbl
+  float coef[2];
+  const float* lse;                  // [2][B][H][T]
+  float* delta;                      // [2][B][H][T] scratch
+  float* dq[2];
+  long lddq[2];
+  float *dk, *dv;
+  long lddkv;
+  int B, T, H, dh;
+  float scale;
+};
+int launch_rca_attn_bwd(int prec, const RcaAttnBwd& p, hipStream_t s);   // dh in {64, 128}
+size_t rca_ln_bwd_scratch_bytes(int64_t rows, int D);
+int launch_rca_ln_bwd(int prec, const float* x, const float* add, const float* gamma, const float* dy, int64_t rows, int D, float eps,
+                      float* dxF, void* dxT, float* dgamma, float* dbeta, void* scratch, hipStream_t s);
+int launch_rca_relu_mask(int prec, float* dh, const void* h, int64_t n, void* dhT, hipStream_t s);
+struct RcaWgrad {   // dW (N x C) = sum over the rows of nseg segments of dY_s^T X_s
+  const float* dy[2];
+  const void* x[2];   // operand type
+  long ldy[2], ldx[2];
+  int nseg;
+  int64_t rows;       // per segment
+  int N, C;
+};
+size_t rca_wgrad_scratch_bytes(int64_t vrows, int N, int C);
+int launch_rca_wgrad(int prec, const RcaWgrad& w, float* dw, float* db, void* scratch, hipStream_t s);
+int launch_linear_dgrad(const float* dy, const float* w, int64_t rows, int D, int N, float* dx, hipStream_t s);
 bool linear_head_eligible(int K, int N);
 int launch_linear_head(const float* x, int64_t rows, int K, const float* w, const float* b, int N, float* y, hipStream_t s);
 struct FrameOut { float p_on, p_off; int32_t octave, pitch_class; };

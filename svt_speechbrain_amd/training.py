@@ -6,6 +6,9 @@ One step is the frozen encoder forward (the existing hot path), the head forward
 the recipe's objective and its gradient w.r.t. the logits in one pass (``compute_objectives``, ``train_audio_ssl.py:50-76``), the head's
 weight gradient, and ``Brain.check_gradients``' clip (``speechbrain/core.py:882-923``) fused with ``torch.optim.Adadelta``'s update.
 Nothing is computed by torch and there is no CPU fallback.  The encoder's backward (full fine-tuning) is out of scope.
+
+``FusionTrainer`` is the audio-visual recipe's step (``N20EMv2/audio_visual/train_rca_av.py:174-185``): ``FusionRCA`` + the head on
+precomputed, frozen audio and video features, with the RCA layers' backward of ``csrc/train_rca.hip``.
 """
 from __future__ import annotations
 
@@ -19,7 +22,7 @@ from . import _lib
 from .amt import AMTForward
 
 TERMS = ("onset", "offset", "octave", "pitch")
-_MAX_TENSORS = 16   # tensors per svt_clip_adadelta_step call (csrc/common.h kAdaMaxTensors)
+_MAX_TENSORS = 32   # tensors per svt_clip_adadelta_step call (csrc/common.h kAdaMaxTensors)
 
 
 def _workspace(query, device) -> torch.Tensor:
@@ -157,6 +160,24 @@ def linear_backward(x: torch.Tensor, dy: torch.Tensor, dweight: Optional[torch.T
     return dweight, dbias
 
 
+def linear_backward_data(dy: torch.Tensor, weight: torch.Tensor, dx: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``svt_linear_backward_data``: dx (rows, in) = dy (rows, out) weight (out, in), fp32 on the GPU."""
+    if not (dy.is_cuda and weight.is_cuda):
+        raise _lib.SvtError("linear_backward_data needs GPU tensors; there is no CPU fallback")
+    lib = _lib.load()
+    dev = dy.device
+    dd = dy.detach().to(torch.float32).contiguous()
+    w = weight.detach().to(device=dev, dtype=torch.float32).contiguous()
+    rows, d_out = dd.shape
+    if w.shape[0] != d_out:
+        raise ValueError(f"dy has {d_out} columns, weight {w.shape[0]} rows")
+    if dx is None:
+        dx = torch.empty((rows, w.shape[1]), dtype=torch.float32, device=dev)
+    _lib.check(lib.svt_linear_backward_data(_lib.ptr(dd), _lib.ptr(w), rows, w.shape[1], d_out, _lib.ptr(dx), _lib.dev_index(dev),
+                                            _lib.stream_ptr(dev)), "svt_linear_backward_data")
+    return dx
+
+
 class Adadelta(torch.optim.Optimizer):
     """``torch.optim.Adadelta`` on GPU parameters, updated by a HIP kernel: same constructor, same ``param_groups`` and the same
     ``state_dict()`` (per parameter ``step``, ``square_avg``, ``acc_delta``), so a checkpoint moves both ways and a scheduler that sets
@@ -204,7 +225,7 @@ class Adadelta(torch.optim.Optimizer):
     @torch.no_grad()
     def step(self, closure=None, max_norm: float = 0.0, total_norm: Optional[torch.Tensor] = None):
         """One Adadelta update.  ``max_norm > 0`` (extension) first clips the gradients of ALL parameters of the optimizer by their
-        global norm as ``clip_grad_norm_`` does, in the same kernel call (one param group of at most 16 tensors)."""
+        global norm as ``clip_grad_norm_`` does, in the same kernel call (one param group of at most 32 tensors)."""
         loss = None
         if closure is not None:
             with torch.enable_grad():
@@ -337,4 +358,168 @@ class LinearProbe:
             _bump(b.grad)
         self.last_grad_norm = torch.empty((), dtype=torch.float32, device=dev)
         self.optimizer.step(max_norm=self.max_grad_norm, total_norm=self.last_grad_norm)
+        return loss.detach().cpu()
+
+
+# the 24 fusion tensors in the order of svt_rca_refresh_params / svt_rca_backward (include/svt_mi355.h)
+RCA_LAYER_KEYS = ("self_att.att.in_proj_weight", "self_att.att.in_proj_bias", "self_att.att.out_proj.weight", "self_att.att.out_proj.bias",
+                  "pos_ffn.ffn.0.weight", "pos_ffn.ffn.0.bias", "pos_ffn.ffn.3.weight", "pos_ffn.ffn.3.bias",
+                  "norm1.norm.weight", "norm1.norm.bias", "norm2.norm.weight", "norm2.norm.bias")
+RCA_KEYS = tuple(f"fusion.layer{l}.{k}" for l in (1, 2) for k in RCA_LAYER_KEYS)
+
+
+class FusionTrainer:
+    """``fit_batch`` of the audio-visual recipe (``train_rca_av.py:174-185``): ``FusionRCA`` + the 20-way ``Linear`` head trained on
+    precomputed, frozen audio and video features -- forward, ``compute_objectives``, backward, ``check_gradients`` (non-finite skip +
+    ``clip_grad_norm_``) and one Adadelta step over ``ModuleList[fusion, head]``, all HIP.  ``modules`` is the recipe's mapping
+    (``fusion`` + ``head``).  Fusion precision fp32 (parity) or bf16 (throughput); master weights, gradients and the optimizer state are
+    fp32 in both.  The fusion's parameters must be on the GPU.
+
+    After ``fit_batch``: every parameter's ``.grad`` holds the (clipped) gradient the step used, ``last_terms`` the four loss terms,
+    ``last_grad_norm`` the pre-clip norm.  The fusion's device weights are refreshed on the device from the new parameters, so the next
+    ``fusion(a, v)`` uploads nothing through the host.  A non-finite loss skips the step (gradients set to None, parameters
+    untouched); the ``nonfinite_patience + 1``-th skip since ``on_epoch_start()`` raises ``ValueError``."""
+
+    def __init__(self, modules, optimizer: Optional[Adadelta] = None, lr: float = 3e-4, rho: float = 0.95, eps: float = 1e-8,
+                 onset_positive_weight: float = 15.0, pitch_octave_num: int = 4, pitch_class_num: int = 12, max_grad_norm: float = 5.0,
+                 nonfinite_patience: int = 3, allowed_len_diff: int = 3, label_smoothing: float = 0.0):
+        from .fusion import FusionRCA
+        from .linear import Linear
+        self.fusion = modules["fusion"]
+        self.head = modules["head"]
+        if not isinstance(self.fusion, FusionRCA) or not isinstance(self.head, Linear):
+            raise TypeError("FusionTrainer needs modules {'fusion': FusionRCA, 'head': Linear} of svt_speechbrain_amd")
+        if self.fusion.precision not in ("fp32", "bf16"):
+            raise _lib.SvtError(f"FusionTrainer: training takes precision fp32 or bf16, not {self.fusion.precision!r}")
+        named = dict(self.fusion.named_parameters())
+        self._params = [named[k] for k in RCA_KEYS]
+        for p in self._params:
+            if not p.is_cuda:
+                raise _lib.SvtError("FusionTrainer needs the fusion's parameters on the GPU; there is no CPU fallback")
+            if p.dtype != torch.float32 or not p.is_contiguous():
+                raise _lib.SvtError("FusionTrainer: the fusion's parameters must be contiguous fp32")
+        self.onset_positive_weight = float(onset_positive_weight)
+        self.pitch_octave_num = int(pitch_octave_num)
+        self.pitch_class_num = int(pitch_class_num)
+        self.max_grad_norm = float(max_grad_norm)
+        self.nonfinite_patience = int(nonfinite_patience)
+        self.allowed_len_diff = int(allowed_len_diff)
+        self.label_smoothing = float(label_smoothing)
+        if optimizer is None:
+            optimizer = Adadelta(list(self.fusion.parameters()) + list(self.head.parameters()), lr=lr, rho=rho, eps=eps)
+        if not isinstance(optimizer, Adadelta):
+            raise TypeError("FusionTrainer needs svt_speechbrain_amd.training.Adadelta (the clip is fused into its kernel)")
+        self.optimizer = optimizer
+        self.nonfinite_count = 0
+        self.last_terms: Dict[str, float] = {}
+        self.last_grad_norm: Optional[torch.Tensor] = None
+        self._ws: Dict[tuple, torch.Tensor] = {}
+        self._refreshed = None   # (handle, signature) the transposed weights were written for
+
+    def on_epoch_start(self) -> None:
+        self.nonfinite_count = 0
+
+    def _scratch(self, key, nbytes: int, device) -> torch.Tensor:
+        ws = self._ws.get(key)
+        if ws is None or ws.numel() < nbytes or ws.device != device:
+            ws = torch.empty(max(16, nbytes), dtype=torch.uint8, device=device)
+            self._ws[key] = ws
+        return ws
+
+    def _ptrs(self, tensors):
+        return (C.c_void_p * len(tensors))(*[_lib.ptr(t) for t in tensors])
+
+    def _signature(self):
+        return tuple((t.data_ptr(), t._version) for _, t in self.fusion._param_owner()._tensors())
+
+    def _refresh(self, lib, slot, dev) -> None:
+        """Rewrite the handle's weights (and the transposes the backward reads) from the fp32 parameters, on the device."""
+        _lib.check(lib.svt_rca_refresh_params(slot.handle, self._ptrs(self._params), len(self._params), _lib.stream_ptr(dev)),
+                   "svt_rca_refresh_params", lib)
+        slot.sig = self._signature()
+        self._refreshed = (slot.handle.value, slot.sig)
+
+    def fit_batch(self, audio_feats: torch.Tensor, video_feats: torch.Tensor, wav_lens: Optional[torch.Tensor], anno: torch.Tensor,
+                  anno_lens: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """One step on audio (B, T1, D) and video (B, T2, D) features; ``anno`` (B, T', 4) as ``LinearProbe.fit_features``, masked by
+        ``wav_lens``.  Returns the detached 0-d loss on the CPU, as ``Brain.fit_batch``."""
+        if not (audio_feats.is_cuda and video_feats.is_cuda):
+            raise _lib.SvtError("FusionTrainer needs its features on the GPU; there is no CPU fallback")
+        fusion, head = self.fusion, self.head
+        lib = _lib.load()
+        dev = audio_feats.device
+        a = audio_feats.detach().to(torch.float32).contiguous()
+        v = video_feats.detach().to(torch.float32).contiguous()
+        if a.dim() != 3 or v.dim() != 3 or a.shape[0] != v.shape[0] or a.shape[2] != fusion.d_model or v.shape[2] != fusion.d_model:
+            raise ValueError(f"expected (B, T, {fusion.d_model}) features with equal batch, got {tuple(a.shape)} and {tuple(v.shape)}")
+        B, T1, D = a.shape
+        T2 = v.shape[1]
+        if abs(T1 - T2) > 15:
+            print("Alignment is wrong")  # the reference's diagnostic (fusion.py:204-205)
+        slot = fusion._sync(dev)
+        if self._refreshed != (slot.handle.value, slot.sig):
+            self._refresh(lib, slot, dev)
+        need = lib.svt_rca_train_workspace_bytes(slot.handle, B, T1)
+        if need < 0:
+            raise _lib.SvtError(_lib.last_error(lib))
+        ws = self._scratch("rca", int(need), dev)
+        stream = _lib.stream_ptr(dev)
+        feats = torch.empty((B, T1, D), dtype=torch.float32, device=dev)
+        _lib.check(lib.svt_rca_forward_train(slot.handle, _lib.ptr(a), T1, _lib.ptr(v), T2, B, _lib.ptr(feats), _lib.ptr(ws), ws.numel(),
+                                             stream), "svt_rca_forward_train", lib)
+        logits = head(feats)
+        n_out = logits.shape[-1]
+        an = anno.to(dev)
+        if an.dim() != 3 or an.shape[0] != B or an.shape[2] < 4:
+            raise ValueError(f"anno must be (batch, frames, 4), got {tuple(anno.shape)}")
+        on_t = an[:, :, 0].to(torch.float32).contiguous()
+        off_t = an[:, :, 1].to(torch.float32).contiguous()
+        oct_t = an[:, :, 2].to(torch.int64).contiguous()
+        cls_t = an[:, :, 3].to(torch.int64).contiguous()
+        ln = None
+        if wav_lens is not None:
+            ln = torch.as_tensor(wav_lens, dtype=torch.float32, device=dev).reshape(-1).contiguous()
+            if ln.numel() != B:
+                raise ValueError(f"wav_lens has {ln.numel()} entries for a batch of {B}")
+
+        def obj_ws(query):
+            n = C.c_size_t(0)
+            query(n)
+            return self._scratch("obj", int(n.value), dev)
+
+        terms, dlogits, host = amt_objective_grad(logits, on_t, off_t, oct_t, cls_t, ln, self.onset_positive_weight,
+                                                  self.pitch_octave_num, self.allowed_len_diff, self.label_smoothing, workspace=obj_ws)
+        self.last_terms = dict(zip(TERMS, host[:4]))
+        loss = terms[4]
+        all_params = self._params + [head.w.weight] + ([head.w.bias] if head.w.bias is not None else [])
+        if not math.isfinite(float(host[4])):
+            self.nonfinite_count += 1
+            for p in all_params:
+                p.grad = None
+            if self.nonfinite_count > self.nonfinite_patience:
+                raise ValueError("Loss is not finite and patience is exhausted. To debug, wrap `fit()` with autograd's "
+                                 "`detect_anomaly()`, e.g.\n\nwith torch.autograd.detect_anomaly():\n\tbrain.fit(...)")
+            return loss.detach().cpu()
+        for p in all_params:
+            if p.grad is None or p.grad.shape != p.shape or not p.grad.is_contiguous() or p.grad.device != p.device:
+                p.grad = torch.empty_like(p, memory_format=torch.contiguous_format)
+        w, b = head.w.weight, head.w.bias
+        rows = B * T1
+        x2, d2 = feats.reshape(rows, D), dlogits.reshape(rows, n_out)
+
+        def wg_ws(query):
+            n = C.c_size_t(0)
+            query(n)
+            return self._scratch("wgrad", int(n.value), dev)
+
+        linear_backward(x2, d2, w.grad, b.grad if b is not None else None, workspace=wg_ws)
+        dfeats = linear_backward_data(d2, w)
+        grads = [p.grad for p in self._params]
+        _lib.check(lib.svt_rca_backward(slot.handle, _lib.ptr(dfeats), B, T1, self._ptrs(grads), _lib.ptr(ws), ws.numel(), stream),
+                   "svt_rca_backward", lib)
+        for p in all_params:
+            _bump(p.grad)
+        self.last_grad_norm = torch.empty((), dtype=torch.float32, device=dev)
+        self.optimizer.step(max_norm=self.max_grad_norm, total_norm=self.last_grad_norm)
+        self._refresh(lib, slot, dev)
         return loss.detach().cpu()
