@@ -16,7 +16,9 @@ issued round-robin on two HIP streams (at N = 1 each lane REPLAYS its step from 
 buffers): every step still computes its whole batch, but the HBM-bound kernels of one step overlap the MFMA-bound
 kernels of the next.
 
-After the timed region (never part of `value`):
+A plain run does only what `value` needs: set-up, the W warm-up steps, the K timed steps, --dump-outputs if given, the JSON line.
+Everything else runs with --full, after the timed region (never part of `value`); --no-extra-legs, --no-parity-leg and
+--no-cpu-baseline leave parts of it out:
   * roofline leg   -- the same K steps on ONE stream with a HIP-event pair around every dense-contraction launch;
   * sustained leg  -- >= 3 s of back-to-back steps (`sustained_clips_per_s`) with shader-clock / wall-clock stamps
                       (s_memtime / s_memrealtime) on either side: the clock the chip HELD under this load;
@@ -26,11 +28,11 @@ After the timed region (never part of `value`):
                       argmax differs, clips with identical note lists, note-level precision / recall (`parity`, `meets_north_star_parity`);
   * parity-grade leg -- the same workload in precision "fp16x3", the fast mode that meets the north star's tolerance
                       (`parity_grade`: clips/s, its own roofline fraction against 2.5 PF / 3, max |dlogit| vs the exact fp32 mode);
-  * --dump-outputs DIR -- what the LAST timed step handed back, written as DIR/<name>.npy (float32 / float64; see dump_outputs) so that
-                      two builds can be compared output for output on identical, seeded inputs;
   * trained-like leg -- the numeric modes on seeded synthetic singing with the head fitted to it (`trained_like`: frames, identical note
                       lists, note F1 against the clips' ground truth: what 16-bit operands cost when decisions have margins);
   * cpu_baseline   -- the oracle on the host cores, SURVEY.md §8(d) protocol (rank 0, N = 1 only).
+With or without --full, --dump-outputs DIR writes what the LAST timed step handed back as DIR/<name>.npy (float32 / float64; see
+dump_outputs) so that two builds can be compared output for output on identical, seeded inputs.
 """
 from __future__ import annotations
 
@@ -295,9 +297,13 @@ def main():
     ap.add_argument("--batch", type=int, default=32, help="clips per GPU")
     ap.add_argument("--seconds", type=float, default=10.0)
     ap.add_argument("--precision", default="bf16", choices=["bf16", "fp16", "fp32", "bf16x3", "fp16x3"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra-legs", action="store_true", help="skip the sustained, notes-out, parity and parity-grade legs (profiling runs)")
-    ap.add_argument("--no-parity-leg", action="store_true", help="skip the parity leg (timed dtype vs the exact-fp32 mode: logits, frames, notes) and the parity-grade (fp16x3) leg of the default bf16 line")
+    ap.add_argument("--full", action="store_true", help="after the timed steps also run the legs the headline value does not need: roofline, "
+                    "sustained, notes-out, parity, parity-grade and trained-like legs and the CPU baseline (off by default)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extra-legs", action="store_true", help="with --full: skip the sustained, notes-out, parity, parity-grade and "
+                    "trained-like legs (profiling runs)")
+    ap.add_argument("--no-parity-leg", action="store_true", help="with --full: skip the parity leg (timed dtype vs the exact-fp32 mode: logits, "
+                    "frames, notes), the parity-grade (fp16x3) leg of the default bf16 line and the trained-like leg")
     ap.add_argument("--sustain-seconds", type=float, default=3.2)
     ap.add_argument("--gather", default="logits", choices=["logits", "frames"],
                     help="N > 1: all-gather the fp32 logits (80 B per frame, the north star's collective) or the compact decoded "
@@ -313,11 +319,11 @@ def main():
                     "(the PCIe-inclusive rate; never the reported metric, whose inputs are resident in HBM)")
     ap.add_argument("--streams", type=int, default=2, help="issue successive steps round-robin on this many HIP streams (each with its own encoder "
                     "object and workspace), so one step's HBM-bound kernels (LayerNorm, conv0, norms) run under the next step's MFMA-bound "
-                    "ones: measured +5 %% with 2, less with 3.  The roofline leg always runs on one stream.")
+                    "ones: measured +5 %% with 2, less with 3.  The roofline leg (--full) always runs on one stream.")
     ap.add_argument("--graph", dest="graph", action="store_true", default=None,
                     help="replay each lane's step (one svt_encoder_forward_head call: ~190 kernel nodes, no memset / memcpy nodes) from a hipGraph "
                     "captured after the warm-up (include/svt_mi355.h: forward calls neither synchronise nor allocate; tests/test_gpu_graph.py).  "
-                    "DEFAULT for N = 1 (round 6: C2 -0.8...-2.3 %, the one-utterance step 0.96 -> 0.92 ms); N > 1 launches eagerly unless this flag is "
+                    "DEFAULT for N = 1 (round 6: C2 -0.8...-2.3 %%, the one-utterance step 0.96 -> 0.92 ms); N > 1 launches eagerly unless this flag is "
                     "given (the collective stays outside the graph either way).  Before it is used, one replay is compared bit for bit with an "
                     "eager forward; a capture that fails or differs falls back to eager launches and config.launch says so")
     ap.add_argument("--no-graph", dest="graph", action="store_false", help="launch every step eagerly (the mode of rounds 1-5)")
@@ -550,22 +556,27 @@ def main():
         return n.value, ms_.value, fl_.value, by_.value
 
     live = prof(0)
+    # what runs from here on is --full only (the roofline leg even with --no-extra-legs: the profiling runs read it)
+    extra_legs = args.full and not args.no_extra_legs
+    parity_legs = extra_legs and not args.no_parity_leg
 
     # roofline leg: the SAME K steps again with a HIP-event pair around every launch of the dense-contraction kernels
     # (on the stream they are launched on).  Kept out of the throughput timing above because 2 event records per
     # launch x ~70 launches per step add ~5 % of GPU idle time.
     # It runs on ONE stream: with two, kernels of consecutive steps share the chip and a launch lasts ~1.2x longer while the
     # job finishes sooner -- a per-launch duration under overlap says nothing about the kernel.
-    lib.svt_prof_reset()
-    lib.svt_prof_enable(1)
-    D.run_sharded(fwds_eager[:1], n_total, rank, world, args.steps, 0, dev, lanes=lanes[:1], gatherers=gatherers[:1], sync=torch.cuda.synchronize)
-    lib.svt_prof_enable(0)
-    k_dom, k_other, k_attn = prof(0), prof(1), prof(2)
+    if args.full:
+        lib.svt_prof_reset()
+        lib.svt_prof_enable(1)
+        D.run_sharded(fwds_eager[:1], n_total, rank, world, args.steps, 0, dev, lanes=lanes[:1], gatherers=gatherers[:1],
+                      sync=torch.cuda.synchronize)
+        lib.svt_prof_enable(0)
+        k_dom, k_other, k_attn = prof(0), prof(1), prof(2)
 
     # sustained leg: the chip needs ~2.5 s of load to settle to the clock it holds (profiles/r01_gemm_clock_trace.txt); the
     # step count is derived from the max-over-ranks step time, so every rank issues the same number of collectives
     sustained = None
-    if not args.no_extra_legs:
+    if extra_legs:
         n_sus = max(args.steps, int(math.ceil(args.sustain_seconds / (elapsed / args.steps))))
         stamps = torch.zeros((2, 16), dtype=torch.int64, device=dev)
         _lib.check(lib.svt_debug_clock(_lib.ptr(stamps[0]), local, _lib.stream_ptr(dev)), "svt_debug_clock")
@@ -589,7 +600,7 @@ def main():
     # batches are in flight: while the host turns the frames of step i into notes, the GPU runs step i + 1 on the other lane
     # (frames_l / pinned host buffers are per lane), which is how a caller that wants notes would drive the path.
     notes_out = None
-    if not args.no_extra_legs:
+    if extra_legs:
         # ns steps stay in flight while the host assembles notes: the lane a finished step frees is refilled BEFORE its notes are
         # assembled (ns + 1 pinned host buffers, so the refill's copy never lands in the buffer being read)
         fr_host = [torch.empty((hi - lo, T, 4), dtype=torch.int32).pin_memory() for _ in range(ns + 1)]
@@ -634,7 +645,7 @@ def main():
     # shard, after the timed region.  The weights are seeded random (no network): near-tie rates of a trained checkpoint may differ.
     parity = None
     ref_logits = ref_frames = None
-    if not args.no_parity_leg and not args.no_extra_legs:
+    if parity_legs:
         from svt_speechbrain_amd.agreement import mode_agreement
         torch.cuda.synchronize()
         t_par = time.perf_counter()
@@ -667,7 +678,7 @@ def main():
     # fraction (against 2.5 PF / 3), and the largest |logit - fp32 logit| over the batch's first two clips (the exact-fp32-MFMA
     # mode on the whole batch: the whole-batch norms see the same clips).
     parity_grade = None
-    if not args.no_extra_legs and not args.no_parity_leg and args.precision == "bf16" and parity is not None:
+    if parity_legs and args.precision == "bf16" and parity is not None:
         pg_prec = "fp16x3"
         pg_encs = [S.HuggingFaceWav2Vec2(args.model, None, config=cfg, precision=pg_prec, normalize_wav=True, seed=1986).to(dev)]
         pg_encs += [pg_encs[0].replica() for _ in range(ns - 1)]
@@ -722,7 +733,7 @@ def main():
     # (svt_speechbrain_amd/agreement.py, trained_like_study) -- what 16-bit operands cost when decisions have trained-like margins,
     # in frames, identical note lists, and note-level F1 against the clips' ground truth.  After the timed region; ~3 s.
     trained_like = None
-    if (world == 1 and not args.no_extra_legs and not args.no_parity_leg and args.model == "wav2vec2-base"
+    if (world == 1 and parity_legs and args.model == "wav2vec2-base"
             and os.path.exists(os.path.join(ROOT, "tests", "golden", "trained_like_head.pt"))):
         from svt_speechbrain_amd.agreement import trained_like_study
         modes = [args.precision] + [m for m in ("fp16", "fp16x3") if m != args.precision and args.precision == "bf16"]
@@ -736,22 +747,50 @@ def main():
     if rank == 0:
         clips_per_s = n_total * args.steps / elapsed
         peak = MFMA_PEAK_TFLOPS[args.precision]
-        n_l, ms, fl, _ = k_dom
-        achieved = (fl / 1e12) / (ms / 1e3) if ms > 0 else 0.0
         flops_clip = cfg.flops_per_clip(L)
-        # HBM bytes per launch of the dominant kernel family from the committed PMC passes (separate rocprofv3 --pmc
-        # FETCH_SIZE / WRITE_SIZE runs of this same command, gfx950 read correction applied: tools/pmc_summary.py);
-        # null when that file is absent or the workload is not the default one
-        traffic = None
-        if os.path.exists(PMC_TRAFFIC_FILE) and args.model == "wav2vec2-base" and B == 32 and args.seconds == 10.0 and args.precision == "bf16":
-            try:
-                pm = json.load(open(PMC_TRAFFIC_FILE))
-                fam = [v for k, v in pm.items() if k.startswith(("gemm_p1w_kernel", "gemm_pps_kernel", "gemm_pers_kernel", "gemm_pp8_kernel"))]
-                tot_n = sum(v["launches"] for v in fam)
-                traffic = round(sum(v["launches"] * v["hbm_bytes_per_launch"] for v in fam) / tot_n / 1e9, 4)
-            except Exception:
-                traffic = None
-        split = args.precision in ("bf16x3", "fp16x3")
+        in_timed_region = {"launches_sampled": int(live[0]),
+                           "avg_launch_ms": round(live[1] / max(1, live[0]), 5),
+                           "achieved": round((live[2] / 1e12) / (live[1] / 1e3), 2) if live[1] > 0 else None,
+                           "streams": ns}
+        roofline = {"in_timed_region": in_timed_region,
+                    "note": "every 8th dense launch of the timed region (none when the steps are graph replays); the roofline leg runs with --full"}
+        if args.full:
+            n_l, ms, fl, _ = k_dom
+            achieved = (fl / 1e12) / (ms / 1e3) if ms > 0 else 0.0
+            # HBM bytes per launch of the dominant kernel family from the committed PMC passes (separate rocprofv3 --pmc
+            # FETCH_SIZE / WRITE_SIZE runs of this same command, gfx950 read correction applied: tools/pmc_summary.py);
+            # null when that file is absent or the workload is not the default one
+            traffic = None
+            if os.path.exists(PMC_TRAFFIC_FILE) and args.model == "wav2vec2-base" and B == 32 and args.seconds == 10.0 and args.precision == "bf16":
+                try:
+                    pm = json.load(open(PMC_TRAFFIC_FILE))
+                    fam = [v for k, v in pm.items() if k.startswith(("gemm_p1w_kernel", "gemm_pps_kernel", "gemm_pers_kernel", "gemm_pp8_kernel"))]
+                    tot_n = sum(v["launches"] for v in fam)
+                    traffic = round(sum(v["launches"] * v["hbm_bytes_per_launch"] for v in fam) / tot_n / 1e9, 4)
+                except Exception:
+                    traffic = None
+            split = args.precision in ("bf16x3", "fp16x3")
+            roofline = {"bound": "mfma",
+                        "kernel": ("svt::gemm_x3q_kernel <BM=128|192|256> (split-operand products on pair rows: activations AND weights pre-cut into "
+                                   "16-bit (hi, lo) pieces by their producers, hi*hi + hi*lo + lo*hi = three MFMAs per 16x16x32 block on the persistent "
+                                   "staggered schedule of gemm_pps_kernel); gemm_x3s_kernel for the batched positional conv") if split else
+                                  ("svt::gemm_p1w_kernel (one wave per SIMD; conv 1-6, projection, QKV, out-projection, FFN-2, large FFN-1) / gemm_pps_kernel "
+                                   "(two waves per SIMD taking turns; FFN-1 of the base model) / gemm_pp8_kernel <BM=128|192|256>: one LDS-DMA MFMA pipeline, "
+                                   "persistent stream of tiles per CU; one tile per workgroup for the batched positional conv"),
+                        "achieved": round(achieved, 2), "peak": round(peak, 1), "unit": "TFLOP/s",
+                        "frac": round(achieved / peak, 4), "traffic": traffic,
+                        "traffic_unit": f"GB of HBM traffic per launch (PMC, {os.path.relpath(PMC_TRAFFIC_FILE, ROOT)})",
+                        "algorithmic_gb_per_launch": round(k_dom[3] / max(1, n_l) / 1e9, 4),
+                        "launches": int(n_l), "avg_launch_ms": round(ms / max(1, n_l), 5),
+                        "ms_per_step": round(ms / args.steps, 4),
+                        "flops_per_launch_avg": round(fl / max(1, n_l), 1),
+                        "note": "achieved / avg_launch_ms: HIP events around every launch, the K steps replayed on ONE stream right after "
+                                f"the timed region; the timed region itself issues steps round-robin on {ns} stream(s), where kernels of "
+                                "consecutive steps share the chip and a launch lasts longer while the job finishes sooner "
+                                "(in_timed_region: every 8th launch of the timed region, same events, same stream as the launch)",
+                        "in_timed_region": in_timed_region,
+                        "other_kernels_ms_per_step": {"small/fp32 gemm": round(k_other[1] / args.steps, 4),
+                                                      "flash_attn": round(k_attn[1] / args.steps, 4)}}
         res_json = {
             "metric": "10s@16kHz clips/sec encoder+CTC forward, wav2vec2-base, 1/2/4/8 MI355X",
             "value": round(clips_per_s, 3),
@@ -785,30 +824,7 @@ def main():
                                                    "backend": torch.distributed.get_backend(),
                                                    "norm_all_reduce": "2 x 16 B per step (global-batch norms)" if args.global_norm else None},
             "per_rank_clips_per_s": [round(B * args.steps / t, 3) for t in res["elapsed_per_rank"]],
-            "roofline": {"bound": "mfma",
-                         "kernel": ("svt::gemm_x3q_kernel <BM=128|192|256> (split-operand products on pair rows: activations AND weights pre-cut into "
-                                    "16-bit (hi, lo) pieces by their producers, hi*hi + hi*lo + lo*hi = three MFMAs per 16x16x32 block on the persistent "
-                                    "staggered schedule of gemm_pps_kernel); gemm_x3s_kernel for the batched positional conv") if split else
-                                   ("svt::gemm_p1w_kernel (one wave per SIMD; conv 1-6, projection, QKV, out-projection, FFN-2, large FFN-1) / gemm_pps_kernel "
-                                    "(two waves per SIMD taking turns; FFN-1 of the base model) / gemm_pp8_kernel <BM=128|192|256>: one LDS-DMA MFMA pipeline, "
-                                    "persistent stream of tiles per CU; one tile per workgroup for the batched positional conv"),
-                         "achieved": round(achieved, 2), "peak": round(peak, 1), "unit": "TFLOP/s",
-                         "frac": round(achieved / peak, 4), "traffic": traffic,
-                         "traffic_unit": f"GB of HBM traffic per launch (PMC, {os.path.relpath(PMC_TRAFFIC_FILE, ROOT)})",
-                         "algorithmic_gb_per_launch": round(k_dom[3] / max(1, n_l) / 1e9, 4),
-                         "launches": int(n_l), "avg_launch_ms": round(ms / max(1, n_l), 5),
-                         "ms_per_step": round(ms / args.steps, 4),
-                         "flops_per_launch_avg": round(fl / max(1, n_l), 1),
-                         "note": "achieved / avg_launch_ms: HIP events around every launch, the K steps replayed on ONE stream right after "
-                                 f"the timed region; the timed region itself issues steps round-robin on {ns} stream(s), where kernels of "
-                                 "consecutive steps share the chip and a launch lasts longer while the job finishes sooner "
-                                 "(in_timed_region: every 8th launch of the timed region, same events, same stream as the launch)",
-                         "in_timed_region": {"launches_sampled": int(live[0]),
-                                             "avg_launch_ms": round(live[1] / max(1, live[0]), 5),
-                                             "achieved": round((live[2] / 1e12) / (live[1] / 1e3), 2) if live[1] > 0 else None,
-                                             "streams": ns},
-                         "other_kernels_ms_per_step": {"small/fp32 gemm": round(k_other[1] / args.steps, 4),
-                                                       "flash_attn": round(k_attn[1] / args.steps, 4)}},
+            "roofline": roofline,
         }
         if sustained is not None:
             res_json["sustained_clips_per_s"] = sustained["clips_per_s"]
@@ -821,7 +837,7 @@ def main():
         if parity_grade is not None:
             res_json["parity_grade_clips_per_s"] = parity_grade["clips_per_s"]
             res_json["parity_grade"] = parity_grade
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             sd = {k[len("model."):]: v.detach().cpu() for k, v in enc.state_dict().items()}
             res_json["cpu_baseline"] = cpu_baseline(cfg, sd, hd, model=args.model)
         print(json.dumps(res_json), flush=True)

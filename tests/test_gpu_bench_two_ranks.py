@@ -140,3 +140,25 @@ def test_one_rank_dump_outputs_of_the_last_timed_step(tmp_path):
         assert np.array_equal(a[k], b[k]), k
     # the frames are the decode of these logits: the octave field is the argmax over its five classes (20 = 2 + 5 + 13)
     assert np.array_equal(a["frame_octave"], a["logits"][..., 2:7].argmax(-1))
+
+
+def test_one_rank_plain_run_is_lean_and_full_runs_the_legs():
+    """A plain run prints the timed figures and none of the legs after the timed region; `--full` runs them (the CPU baseline is left
+    out here, `--no-cpu-baseline`: it is the oracle on the host, minutes at this size)."""
+    env = dict(os.environ)
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "SVT_SHARE_GPU", "SVT_DIST_BACKEND"):
+        env.pop(k, None)
+    seen = {}
+    for flags in ((), ("--full", "--no-cpu-baseline")):
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--batch", "2", "--seconds", "2", *flags]
+        r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=ROOT)
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert r.returncode == 0 and len(lines) == 1, (r.stdout[-2000:], r.stderr[-2000:])
+        seen[flags] = json.loads(lines[0])
+    plain, full = seen[()], seen[("--full", "--no-cpu-baseline")]
+    for j in (plain, full):
+        assert j["value"] > 0 and j["ms_per_step"] > 0 and j["steps"] == 2 and j["warmup"] == 1 and j["dtype"] == "bf16"
+        assert j["unit"] == "clips/s" and j["higher_is_better"] is True and "cpu_baseline" not in j
+    legs = ("sustained", "notes_out", "parity_grade", "trained_like")
+    assert not any(k in plain for k in legs) and plain["parity"] is None and "achieved" not in plain["roofline"]
+    assert all(k in full for k in legs) and full["parity"] is not None and full["roofline"]["launches"] > 0

@@ -704,6 +704,17 @@ def test_bench_refuses_a_rank_count_mismatch_and_lib_variant_path():
     assert ext == ".so" and os.path.exists(f"{root}_f16{ext}")
 
 
+def test_bench_help_lists_full_and_the_legs_it_gates():
+    """`bench.py --help` prints (every help string formats) and names --full, off by default, as what the skip flags qualify."""
+    import subprocess, sys
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=120, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    out = " ".join(r.stdout.split())
+    assert "--full" in out and "(off by default)" in out
+    for flag in ("--no-cpu-baseline", "--no-extra-legs", "--no-parity-leg"):
+        assert f"{flag} with --full:" in out, flag
+
+
 def test_local_directory_picks_the_weights_file_and_reads_shards(tmp_path):
     """A Trainer output directory holds optimizer.bin / training_args.bin beside the weights, and large checkpoints come as
     shards with an index: the wrapper must load pytorch_model.bin (or the shards), never the alphabetically first *.bin."""
