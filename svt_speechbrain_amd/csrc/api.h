@@ -1,0 +1,92 @@
+// Host-side pieces shared by the C-ABI translation units (api.hip and api_*.hip): device buffers, workspace carving, uploads,
+// the attention score path and the argument checks every entry point family uses.  Included by the api*.hip files only.
+#pragma once
+#include "common.h"
+
+#include <cstddef>
+#include <cstdint>
+
+namespace svt {
+
+// the helpers below stay out of the library's dynamic symbol table: the C ABI (include/svt_mi355.h) is its interface
+#pragma GCC visibility push(hidden)
+
+struct DevBuf {
+  void* p = nullptr;
+  size_t bytes = 0;
+  ~DevBuf() { release(); }
+  void release() { if (p) { split_weights_forget(p); dev_free(p); p = nullptr; } }
+  DevBuf() = default;
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  DevBuf(DevBuf&& o) noexcept : p(o.p), bytes(o.bytes) { o.p = nullptr; o.bytes = 0; }
+  int alloc(size_t n) {
+    if (p && bytes == n) return 0;   // a re-upload of the same tensor keeps its buffer (no free / allocate pair: see upload_operand)
+    release();
+    bytes = n;
+    return dev_alloc(&p, n);
+  }
+  template <typename T> T* as() const { return (T*)p; }
+};
+
+// upload fp32 host data as fp32 or (prec) bf16 operand
+int upload_f32(DevBuf& b, const float* h, size_t n);
+int upload_operand(int prec, DevBuf& b, const float* h, size_t n);
+// weight matrix (rows x K, K contiguous): storage copy as upload_operand + in the split-operand modes the packed (hi, lo)
+// pieces the LDS-DMA split kernel reads (gemm_dma.hip); `precision` is the svt_precision of the object
+int upload_weight(int precision, DevBuf& b, const float* h, size_t rows, size_t K);
+// first step of every svt_*_finalize: waits for the forwards still in flight before a RE-upload changes live buffers
+int begin_upload(bool& uploaded);
+
+static inline size_t align_up(size_t x, size_t a = 256) { return (x + a - 1) / a * a; }
+static inline int round_up_int(int x, int a) { return (x + a - 1) / a * a; }
+
+struct Carver {
+  char* base;
+  size_t off = 0;
+  explicit Carver(void* b) : base((char*)b) {}
+  void* take(size_t bytes) {
+    void* p = base ? base + off : nullptr;
+    off += align_up(bytes);
+    return p;
+  }
+};
+
+struct AttnBufs {
+  float* S;   // (B,H,T,Tp) fp32
+  void* P;    // operand type
+  void* Vt;   // (B,H,dh,Tp)
+  // split-operand modes: 16-bit (hi, lo) planes of the packed (rows, 3D) q/k/v projection, and of a separate (rows, D)
+  // query projection (RCA cross attention); null in the other modes
+  void* pl_qkv = nullptr;
+  void* pl_q = nullptr;
+};
+static inline size_t esize(int prec) { return prec ? 2 : 4; }
+// svt_precision -> storage type of activations / weights in HBM (0 = fp32, 1 = bf16).  The split-operand modes
+// (SVT_PREC_BF16X3 / SVT_PREC_FP16X3) keep the fp32 parity pipeline and change only the engine of the dense products:
+// launch_gemm(gp = precision) cuts the fp32 operands into 16-bit pieces on their way into LDS (gemm.hip).
+static inline int storage_prec(int precision) { return precision >= 2 ? 0 : precision; }
+
+// out[b,t,h*dh+d] = softmax(scale * q k^T) v (api.hip): the fused kernels where they apply, else the materialised scores
+bool use_flash(int prec, int dh, bool bias = false, int64_t T = 0);
+int attn_tp(int prec, int dh, int T, bool bias = false);
+int attention_scores_path(int prec, const void* Q, long ldq, const void* K, const void* V, long ldkv, int B,
+                          int T, int H, int dh, float scale, const AttnBufs& ab, bool vt_ready, void* out,
+                          long ldo, hipStream_t s, const float* gate = nullptr, const float* relpb = nullptr,
+                          int gp = -1, int o_pairs = 0);
+
+// a gfx950 device of this index exists; it becomes the current device
+int check_device(int device);
+// workspace_bytes is in / out: with workspace == NULL the size the call needs is stored and nothing else happens
+int ws_query(const char* who, void* ws, size_t* ws_bytes, size_t need, bool* query);
+
+#pragma GCC visibility pop
+
+}  // namespace svt
+
+struct svt_linear {
+  int in_f = 0, out_f = 0, has_bias = 0, device = 0;
+  bool loaded = false;
+  svt::DevBuf w, b;
+  svt::DevBuf wsum;  // sum_k w[j][k] per output (fp64 on the host): the fused out-norm + head tail needs it
+};

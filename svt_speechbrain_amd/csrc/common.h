@@ -297,7 +297,7 @@ extern int g_gemm_skinny_max_tiles;
 extern int g_gemm_skinny_small_tiles;   // svt_debug_set key 33
 extern int g_gemm_persist_wgs;   // svt_debug_set key 37: workgroups of a persistent GEMM launch (256 = one per CU, default; a multiple of 8)
 extern int g_conv_kperm;     // svt_debug_set key 35: 1 (default) = tap-minor K order for the kernel-3 convolutions on gemm_p1w_kernel, 0 = tap-major
-extern int g_ffn2_ksplit;   // svt_debug_set key 36 (api.hip): FFN-2 of a small batch as a K-split small GEMM + summing LayerNorm
+extern int g_ffn2_ksplit;   // svt_debug_set key 36 (api_encoder.hip): FFN-2 of a small batch as a K-split small GEMM + summing LayerNorm
 extern int g_gemm_skinny;  // 1 (default): small problems use it; 0: never (diagnostics, svt_debug_set key 6)
 extern int g_stamp_ends;
 extern int g_gemm_p1w;       // svt_debug_set key 29: the single-wave-per-SIMD kernel (gemm_p1w.hip) where gemm_pps_kernel is dispatched
@@ -306,6 +306,12 @@ extern int g_gemm_dbg;   // diagnostic variant applied to every launch (svt_debu
 extern int g_gemm_force_bm;
 extern int g_gemm_ring;
 extern int g_gemm_variant;  // diagnostics: replaces dbg inside the kernel while the trace pointer stays set
+// switches of the host entry points, defined beside their users; hidden like the helpers of api.h (not part of the exported symbols)
+#pragma GCC visibility push(hidden)
+extern int g_conv_ln_bf16;       // svt_debug_set(9, 0): fp32 conv output + LayerNorm (A/B; api_encoder.hip)
+extern int g_debug_keep_split;   // svt_debug_set(12, 1): svt_debug_gemm keeps the split copy of its weight operand between calls (api.hip)
+extern int g_conv_down_fused;    // svt_debug_set key 27: 0 = stage 2's stride-2 conv1 and its 1x1 downsample as two products (api_video.hip)
+#pragma GCC visibility pop
 
 // hipFuncAttributeMaxDynamicSharedMemorySize for a kernel that asks for more than 64 KiB of dynamic LDS: function attributes are
 // per DEVICE, so the "already set" memory is per (kernel, device), behind a mutex (DataParallel runs replicas from threads)

@@ -1178,7 +1178,7 @@ int gemm_walk_pm(const GemmArgs& a, int bm) {
 int g_x3_pairs = 1;
 int launch_gemm_x3(int kind, const GemmArgs& a, hipStream_t s) {
   if (a.a_pairs) {
-    // pair-row operand: only gemm_x3q_kernel reads it (the callers in api.hip ask gemm_x3q_eligible before they choose the layout)
+    // pair-row operand: only gemm_x3q_kernel reads it (the callers in api_encoder.hip ask gemm_x3q_eligible before they choose the layout)
     if (!gemm_x3q_eligible(a) || a.ldw != a.K) { set_error("gemm: pair-row operand outside the contract of gemm_x3q_kernel"); return -1; }
     const void* packed = nullptr;
     {

@@ -237,7 +237,7 @@ bool gemm_skinny_eligible(const GemmArgs& a) {
   return big_tiles <= g_gemm_skinny_max_tiles;
 }
 
-int g_ffn2_ksplit = 1;   // svt_debug_set key 36: the encoder's FFN-2 of a small batch as a K-split launch of this kernel (api.hip)
+int g_ffn2_ksplit = 1;   // svt_debug_set key 36: the encoder's FFN-2 of a small batch as a K-split launch of this kernel (api_encoder.hip)
 int g_gemm_skinny_small_tiles = 96;   // svt_debug_set key 33: 32 x 32 tiles while the 64 x 64 tiling has at most this many workgroups
 int launch_gemm_skinny(const GemmArgs& a, hipStream_t s) {
   if (a.ksplit > 1 && (a.bias || a.resid || a.act != ACT_NONE || !a.out_f32 || a.alpha != 1.f || (a.K / 64) < a.ksplit || a.ksplit_stride < (long)a.M * a.ldc)) {
