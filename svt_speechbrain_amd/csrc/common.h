@@ -246,23 +246,28 @@ struct GemmArgs {
   long long* trace = nullptr;  // diagnostics (dbg == 9): per-workgroup phase clock stamps, 16 x int64 per workgroup
 };
 
+// ---- dense products (GEMM) ----
 // operand type: 0 = fp32 (v_mfma_f32_16x16x4_f32, exact fp32 fma chain), 1 = bf16 (v_mfma_f32_16x16x32_bf16)
+// gemm_dispatch.hip: the one entry of every product; it picks the kernel, its tile and its grid, and brackets the launch for profiling
 int launch_gemm(int prec, const GemmArgs& a, hipStream_t s);
+// gemm_dispatch.hip: the small-problem kernel at the tile key 33 picks, with its own profiling bracket (also the FFN-2 K-split of api_encoder.hip)
+int launch_gemm_skinny(const GemmArgs& a, hipStream_t s);
 
-// large-tile LDS-DMA variant (bf16, K % 64 == 0); launch_gemm dispatches to it
+// Kernel files: a contract predicate and one launcher each, which launches exactly the configuration it is given (tile height bm, tile
+// width, diagnostic form)
+// large-tile LDS-DMA pipeline (gemm_dma.hip; bf16, K % 64 == 0): pp8 / pers below
 bool gemm_dma_eligible(const GemmArgs& a);
-int launch_gemm_dma(const GemmArgs& a, hipStream_t s);
 // persistent + staggered form of the LDS-DMA pipeline (gemm_pps.hip): bf16 output, no residual, activation none / GELU
 bool gemm_pps_eligible(const GemmArgs& a);
 int launch_gemm_pps(const GemmArgs& a, int bm, hipStream_t s);
-// small problems (a single utterance): 64 x 64 tiles, K split four ways inside the workgroup, operands straight from L2
+// the same contract, one wave per SIMD (gemm_p1w.hip), K >= 192
+int launch_gemm_p1w(const GemmArgs& a, int bm, hipStream_t s);
+// small problems (a single utterance): K split four ways inside the workgroup, operands straight from L2
 bool gemm_skinny_eligible(const GemmArgs& a);
-int launch_gemm_skinny(const GemmArgs& a, hipStream_t s);
-// split-operand modes: weight matrices cut once into packed 16-bit (hi, lo) pieces for the LDS-DMA split kernel
-// (gemm_dma.hip gemm_x3_kernel).  kind = svt_precision (2 = bf16 pieces, 3 = fp16 pieces); other kinds are ignored.
+// split-operand modes: weight matrices cut once into packed 16-bit (hi, lo) pieces for the LDS-DMA split kernels (gemm_dma.hip).
+// kind = svt_precision (2 = bf16 pieces, 3 = fp16 pieces); other kinds are ignored.
 int split_weights_register(const void* w_f32_dev, long n_rows, int K, int kind, hipStream_t s);
 void split_weights_forget(const void* w_f32_dev);
-int launch_gemm_x3(int kind, const GemmArgs& a, hipStream_t s);  // 0 = launched, 1 = not eligible (use the register-staged kernel), < 0 = error
 // persistent staggered form of the LDS-DMA split kernel (gemm_x3p.hip); `packed` = the registered (hi, lo) image of the weight rows
 bool gemm_x3p_eligible(const GemmArgs& a);
 int launch_gemm_x3p(int kind, const GemmArgs& a, const void* packed, hipStream_t s);
@@ -270,8 +275,31 @@ int launch_gemm_x3p(int kind, const GemmArgs& a, const void* packed, hipStream_t
 bool gemm_x3q_eligible(const GemmArgs& a);
 int launch_gemm_x3q(int kind, const GemmArgs& a, const void* packed, int bm, hipStream_t s);
 int launch_gemm_p1x(int kind, const GemmArgs& a, const void* packed, int bm, hipStream_t s);   // gemm_p1x.hip: the same product, one wave per SIMD (K >= 96)
-extern int g_gemm_p1x;   // svt_debug_set key 30
-extern int g_gemm_walk;  // svt_debug_set key 34: -1 (default) = choose per launch (gemm_walk_pm), 0 = always n fastest, > 0 = this panel height
+// shared by the dispatcher and the kernel files only: hidden like the helpers of api.h (not part of the exported symbols)
+#pragma GCC visibility push(hidden)
+// register-staged kernel (gemm.hip): prec as for launch_gemm; bn = 64 (256 x 64 tiles) or 128 (128 x 128)
+int launch_gemm_staged(int prec, const GemmArgs& a, int bn, hipStream_t s);
+// gemm_dma.hip: one tile per workgroup (with a.gen, bn = 128 gives the 256 x 128 tile), and one workgroup per CU walking a tile list
+int launch_gemm_pp8(const GemmArgs& a, int bm, int bn, hipStream_t s);
+int launch_gemm_pers(const GemmArgs& a, int bm, hipStream_t s);
+int launch_gemm_skinny_tile(const GemmArgs& a, int tile, hipStream_t s);   // gemm_skinny.hip: tile = 64 (64 x 64) or 32 (32 x 32)
+// the packed image of the rows [W, W + rows_needed) of a registered matrix of this kind and K (W may point into it), or null
+const void* split_weights_find(const void* W, int kind, int K, long rows_needed);
+// the one-tile split kernel with A fp32 in memory (gemm_dma.hip gemm_x3s_kernel): nbs = 4 / 3 for 256- / 192-column tiles; form: 0, or in
+// DIAG builds the timing ablations 1 / 3 and the slot stamps 11-14
+int launch_gemm_x3s(int kind, const GemmArgs& a, const void* packed, int nbs, int form, hipStream_t s);
+// the split kernels address a tile's 256 rows (possibly across clip boundaries) by 32-bit offsets from its first row, and the packed
+// weights by 32-bit offsets from their base
+inline bool tile_span_fits(const GemmArgs& a) {
+  const unsigned long clips = 255 / (unsigned long)(a.a_rpb > 0 ? a.a_rpb : 1) + 1;
+  const unsigned long bs = (unsigned long)(a.a_bstride > 0 ? a.a_bstride : 0), rs = (unsigned long)(a.a_rstride > 0 ? a.a_rstride : 0);
+  return a.a_bstride >= 0 && a.a_rstride > 0 && (clips * bs + 256ul * rs + (unsigned long)a.K) * 4 < 0xF0000000ul &&
+         (unsigned long)a.N * a.K * 4 < 0xF0000000ul;
+}
+// workgroups of a persistent launch: one per tile (rounded up to whole XCD rounds) up to the cap
+inline int persistent_blocks(int ntiles, int cap) { return ntiles < cap ? ((ntiles + 7) / 8) * 8 : cap; }
+#pragma GCC visibility pop
+
 // Tile walk of the persistent GEMM kernels (gemm_p1w / gemm_pps): logical tile index -> (tile_m, tile_n).  Blocks b and b + 8 share an XCD
 // and an XCD works on 32 consecutive logical tiles per round, so the walk decides what an XCD's L2 has to hold:
 //   pm == 0: n fastest -- 32 tiles = a few whole rows of tiles: every A row block is fetched by ONE XCD, all of W by every XCD in every
@@ -280,6 +308,7 @@ extern int g_gemm_walk;  // svt_debug_set key 34: -1 (default) = choose per laun
 //            XCD round fetches pm A blocks + 32 / pm W blocks instead of ~32 / tiles_n A blocks + ALL tiles_n W blocks.  For the large
 //            models' FFN-1 (N = 4096, K = 1024: W = 8 MiB, twice the L2) that is 6 MiB instead of 9 MiB per XCD and round, for a square
 //            8192 problem 48 instead of 132 (what the vendor library's kernel name calls WGM / SKXCCM: profiles/r06_gemm_tile_walk.txt).
+// The dispatcher sets the panel height per launch (GemmArgs::walk_pm, svt_debug_set key 34).
 __device__ __forceinline__ void tile_walk(int logical, int tiles_m, int tiles_n, int pm, int& tile_m, int& tile_n) {
   if (pm <= 0) { tile_n = logical % tiles_n; tile_m = logical / tiles_n; return; }
   const int per_panel = pm * tiles_n;
@@ -288,24 +317,27 @@ __device__ __forceinline__ void tile_walk(int logical, int tiles_m, int tiles_n,
   tile_n = rem / rows;
   tile_m = pnl * pm + (rem - tile_n * rows);
 }
-int gemm_walk_pm(const GemmArgs& a, int bm);   // gemm_dma.hip: the panel height for this launch (0 = n fastest)
-extern int g_x3_pairs;  // 1 (default): the split modes keep product operands as pair rows; 0: fp32 activations cut inside the product kernels (svt_debug_set key 19)
+
+// GEMM switches of svt_debug_set (api.hip), all defined in gemm_dispatch.hip
+extern int g_gemm_dbg;       // key 0: diagnostic variant applied to every launch; 9 = the caller's `resid` is the trace buffer (tools/gemm_trace.py)
+extern int g_gemm_force_bm;  // key 1: tile height (0 = the cost model's)
+extern int g_gemm_ring;      // key 2: 0 = auto; 2 = force the one-tile-per-workgroup kernel, 4 = force the persistent kernel (diagnostics)
+extern int g_gemm_variant;   // key 3: diagnostics: replaces dbg inside the kernel while the trace pointer stays set; kernel A/B arms
+extern int g_gemm_skinny;    // key 6: 1 (default): small problems use gemm_skinny_kernel; 0: never (diagnostics)
+extern int g_gemm_skinny_max_tiles;   // key 7: gemm_skinny_eligible's threshold in 128 x 256 tiles
+extern int g_gemm_x3;        // key 11: 1 (default): the LDS-DMA split kernels where eligible; 0: register-staged split kernel only
+extern int g_stamp_ends;     // key 15: which slot stamps of gemm_x3p_kernel / gemm_x3s_kernel a DIAG build takes (tools/gemm_trace.py --x3-slots)
+extern int g_x3_pairs;       // key 19: 1 (default): the split modes keep product operands as pair rows; 0: fp32 activations cut inside the product kernels
+extern int g_gemm_p1w;       // key 29: the single-wave-per-SIMD kernel (gemm_p1w.hip) where gemm_pps_kernel is dispatched
+extern int g_gemm_p1x;       // key 30: gemm_p1x_kernel in place of gemm_x3q_kernel (DIAG builds)
+extern int g_gemm_skinny_small_tiles;   // key 33: 32 x 32 tiles while the 64 x 64 tiling has at most this many workgroups
+extern int g_gemm_walk;      // key 34: -1 (default) = choose per launch, 0 = always n fastest, > 0 = this panel height
+extern int g_conv_kperm;     // key 35: 1 (default) = tap-minor K order for the kernel-3 convolutions on gemm_p1w_kernel, 0 = tap-major
+extern int g_gemm_persist_wgs;   // key 37: workgroups of a persistent GEMM launch (256 = one per CU, default; a multiple of 8)
+
 extern int g_ln_two_rows;  // (hi, lo) LayerNorm: half a wave per row, 16-byte accesses (1, default) or a wave per row (0)
-extern int g_gemm_x3;  // 1 (default): use it where eligible; 0: register-staged split kernel only (svt_debug_set key 11)
 extern int g_flash_wide;  // fused attention: 8-wave (256-query) workgroups for head_dim 64 (1, default) or 4-wave ones (0)
-extern int g_gemm_skinny_max_tiles;
-extern int g_gemm_skinny_small_tiles;   // svt_debug_set key 33
-extern int g_gemm_persist_wgs;   // svt_debug_set key 37: workgroups of a persistent GEMM launch (256 = one per CU, default; a multiple of 8)
-extern int g_conv_kperm;     // svt_debug_set key 35: 1 (default) = tap-minor K order for the kernel-3 convolutions on gemm_p1w_kernel, 0 = tap-major
 extern int g_ffn2_ksplit;   // svt_debug_set key 36 (api_encoder.hip): FFN-2 of a small batch as a K-split small GEMM + summing LayerNorm
-extern int g_gemm_skinny;  // 1 (default): small problems use it; 0: never (diagnostics, svt_debug_set key 6)
-extern int g_stamp_ends;
-extern int g_gemm_p1w;       // svt_debug_set key 29: the single-wave-per-SIMD kernel (gemm_p1w.hip) where gemm_pps_kernel is dispatched
-int launch_gemm_p1w(const GemmArgs& a, int bm, hipStream_t s);
-extern int g_gemm_dbg;   // diagnostic variant applied to every launch (svt_debug_set)
-extern int g_gemm_force_bm;
-extern int g_gemm_ring;
-extern int g_gemm_variant;  // diagnostics: replaces dbg inside the kernel while the trace pointer stays set
 // switches of the host entry points, defined beside their users; hidden like the helpers of api.h (not part of the exported symbols)
 #pragma GCC visibility push(hidden)
 extern int g_conv_ln_bf16;       // svt_debug_set(9, 0): fp32 conv output + LayerNorm (A/B; api_encoder.hip)

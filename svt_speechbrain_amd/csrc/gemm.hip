@@ -462,90 +462,26 @@ int launch_one(const GemmArgs& a, hipStream_t s) {
   ar.raster_gm = tiles_n >= 8 ? 8 : 64 / tiles_n;
   const size_t lds_bytes = 2 * (size_t)(BM + BN) * 128;
   if (int r_ = ensure_dyn_lds((const void*)gemm_kernel<T, BM, BN, GEN, SPLIT, NSET, MINW>, (int)lds_bytes)) return r_;
-  const double flops = 2.0 * a.M * (double)a.N * a.K * a.nz;
-  const double bytes = ((double)a.M * a.K + (double)a.N * a.K) * sizeof(T) * a.nz +
-                       (double)a.M * a.N * a.nz * ((a.out_f32 || sizeof(T) == 4) ? 4 : 2);
-  prof_begin(s);
   hipLaunchKernelGGL((gemm_kernel<T, BM, BN, GEN, SPLIT, NSET, MINW>), grid, dim3(256), lds_bytes, s, ar);
-  prof_end(s, flops, bytes, SPLIT ? 0 : 1);
   SVT_LAUNCH_CHECK();
   return 0;
 }
 
-}  // namespace
-
-int g_gemm_skinny = 1;
-int g_gemm_x3 = 1;
-// prec: 0 = fp32 operands, exact fp32 MFMA; 1 = bf16 operands; 2 / 3 = fp32 operands in memory, bf16x3 / fp16x3
-// split-operand products (every other argument as for prec 0)
-int launch_gemm(int prec_in, const GemmArgs& a, hipStream_t s) {
-  if (a.M <= 0 || a.N <= 0 || a.K <= 0) { set_error("gemm: empty problem"); return -1; }
-  // pair rows are understood by the split-operand LDS-DMA kernels only: every other kernel would read them as fp32 words
-  if ((a.a_pairs || a.c_pairs) && (prec_in < 2 || !g_gemm_x3)) {
-    set_error("gemm: pair-row operands / outputs need a split-operand precision and the LDS-DMA split kernels (svt_debug_set key 11 = 1)");
-    return -1;
-  }
-  if (a.planes) {
-    // C as (hi, lo) planes (split-operand modes only): written by the LDS-DMA split kernel's epilogue; any other kernel writes the
-    // fp32 C and the planes are cut from it afterwards
-    if (prec_in < 2 || a.nz != 1 || a.gen) { set_error("gemm: (hi, lo) plane output is served for plain split-operand products"); return -1; }
-    if (g_gemm_x3) {
-      GemmArgs gp = a;
-      gp.c_vec = !(a.ldc & 3) && !((uintptr_t)a.C & 15) && !((uintptr_t)a.resid & 15) && !((uintptr_t)a.bias & 15) && !(a.plane_stride & 3) &&
-                 !((uintptr_t)a.planes & 7);
-      const int r = launch_gemm_x3(prec_in, gp, s);
-      if (r <= 0) return r;
-    }
-    GemmArgs g2 = a;
-    g2.planes = nullptr;
-    if (int r = launch_gemm(prec_in, g2, s)) return r;
-    return launch_split_planes(prec_in, (const float*)a.C, a.ldc, a.M, a.N, a.planes, a.ldc, a.plane_stride, s);
-  }
-  const int split = prec_in >= 2 ? prec_in - 1 : 0;
-  const int prec = prec_in >= 2 ? 0 : prec_in;
-  const int epp = prec ? 8 : 4;
-  if (a.K % epp != 0) { set_error("gemm: K must be a multiple of the 16-byte piece"); return -1; }
-  auto mult = [](long v, long m) { return v % m == 0; };
-  if (!mult(a.a_rstride, epp) || !mult(a.a_bstride, epp) || !mult(a.a_z1, epp) || !mult(a.a_z2, epp) || !mult(a.ldw, epp) ||
-      !mult(a.w_z1, epp) || !mult(a.w_z2, epp) || ((uintptr_t)a.A & 15) || ((uintptr_t)a.W & 15)) {
-    set_error("gemm: operand rows must be 16-byte aligned");
-    return -1;
-  }
-  GemmArgs g = a;
-  const int cel = (a.out_f32 || !prec) ? 4 : 8;  // elements per 16 bytes of C
-  g.c_vec = mult(a.ldc, cel) && mult(a.c_z1, cel) && mult(a.c_z2, cel) && !((uintptr_t)a.C & 15) &&
-            mult(a.ldc, 4) && mult(a.c_z1, 4) && mult(a.c_z2, 4) && !((uintptr_t)a.resid & 15) &&
-            mult(a.bias_z2, 4) && !((uintptr_t)a.bias & 15);
-  const bool narrow = a.N <= 64;
-  if (a.gen) {
-    const int kel = prec ? 64 : 32;
-    if (a.kseg && (a.kseg % kel || a.K % a.kseg)) { set_error("gemm: kseg must divide K and be a multiple of the K slab"); return -1; }
-    if (!mult(a.a_e1, epp) || !mult(a.a_e2, epp) || !mult(a.kseg_stride, epp)) { set_error("gemm: generalised A strides must be 16-byte aligned"); return -1; }
-    g.c_vec = g.c_vec && mult(a.c_e1, cel) && mult(a.c_e2, cel) && mult(a.c_base, cel) &&
-              (!a.resid || !a.resid_op_type || !((uintptr_t)a.resid & 15));
-    // N >= 128 with bf16 output: the LDS-DMA pipeline (needs 64-element K slabs inside every run and nz == 1)
-    if (prec && a.K % 64 == 0 && a.N >= 128 && a.N % 8 == 0 && a.M >= 128 && g.c_vec && !a.out_f32 && a.nz == 1 &&
-        (!a.resid || a.resid_op_type) && a.alpha == 1.f && (a.kseg == 0 || a.kseg % 64 == 0))
-      return launch_gemm_dma(g, s);
-    if (prec) return narrow ? launch_one<bf16_t, 256, 64, true>(g, s) : launch_one<bf16_t, 128, 128, true>(g, s);
-    if (split == 1) return narrow ? launch_one<float, 256, 64, true, 1, 1>(g, s) : launch_one<float, 128, 128, true, 1, 2, 2>(g, s);
-    if (split == 2) return narrow ? launch_one<float, 256, 64, true, 2, 1>(g, s) : launch_one<float, 128, 128, true, 2, 2, 2>(g, s);
-    return narrow ? launch_one<float, 256, 64, true>(g, s) : launch_one<float, 128, 128, true>(g, s);
-  }
-  if (prec && g_gemm_skinny && gemm_skinny_eligible(g)) return launch_gemm_skinny(g, s);
-  if (prec && gemm_dma_eligible(g)) return launch_gemm_dma(g, s);
-  if (prec) return narrow ? launch_one<bf16_t, 256, 64>(g, s) : launch_one<bf16_t, 128, 128>(g, s);
-  if (split && g_gemm_x3) {
-    const int r = launch_gemm_x3(prec_in, g, s);
-    if (r <= 0) return r;
-  }
-  if (a.a_pairs || a.c_pairs) { set_error("gemm: this geometry is outside the pair-row kernels' contract"); return -1; }
+template <bool GEN>
+int launch_staged(int prec, const GemmArgs& g, bool narrow, hipStream_t s) {
+  if (prec == 1) return narrow ? launch_one<bf16_t, 256, 64, GEN>(g, s) : launch_one<bf16_t, 128, 128, GEN>(g, s);
   // split engine: two slabs in flight per workgroup, capped at 256 registers so that two workgroups share a CU (measured
   // on the encoder's shapes, tools/gemm_bench.py --prec 2: one set 185-212, two sets 186-212, three sets (one workgroup per
   // CU) 150-192 TFLOP/s: the kernel is bound by issue / barrier stalls of its four-wave lockstep, not by the loads)
-  if (split == 1) return narrow ? launch_one<float, 256, 64, false, 1, 1>(g, s) : launch_one<float, 128, 128, false, 1, 2, 2>(g, s);
-  if (split == 2) return narrow ? launch_one<float, 256, 64, false, 2, 1>(g, s) : launch_one<float, 128, 128, false, 2, 2, 2>(g, s);
-  return narrow ? launch_one<float, 256, 64>(g, s) : launch_one<float, 128, 128>(g, s);
+  if (prec == 2) return narrow ? launch_one<float, 256, 64, GEN, 1, 1>(g, s) : launch_one<float, 128, 128, GEN, 1, 2, 2>(g, s);
+  if (prec == 3) return narrow ? launch_one<float, 256, 64, GEN, 2, 1>(g, s) : launch_one<float, 128, 128, GEN, 2, 2, 2>(g, s);
+  return narrow ? launch_one<float, 256, 64, GEN>(g, s) : launch_one<float, 128, 128, GEN>(g, s);
+}
+
+}  // namespace
+
+int launch_gemm_staged(int prec, const GemmArgs& a, int bn, hipStream_t s) {
+  return a.gen ? launch_staged<true>(prec, a, bn == 64, s) : launch_staged<false>(prec, a, bn == 64, s);
 }
 
 }  // namespace svt

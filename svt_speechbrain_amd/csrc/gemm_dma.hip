@@ -13,7 +13,7 @@
 //     16 consecutive output columns of one row.
 //   * two kernels share this pipeline: gemm_pp8_kernel (one tile per workgroup, LDS-transposed coalesced epilogue)
 //     and gemm_pers_kernel (one workgroup per CU walks a tile list; the next tile's fills and the epilogue stores
-//     overlap the MFMAs).  launch_gemm_dma picks BM in {128,192,256} and the kernel per problem.
+//     overlap the MFMAs).  The dispatcher (gemm_dispatch.hip) picks BM in {128,192,256} and the kernel per problem.
 //   * gemm_pp8_kernel<BM, GEN = true, NBW> is the same pipeline with generalised addressing (GemmArgs::gen): A rows at
 //     m*stride + floor(m/d1)*e1 + floor(m/d2)*e2, K made of equal runs a fixed distance apart, C rows likewise -- the
 //     3x3 / 1x1 convolutions of the lip front-end's ResNet over zero-haloed channels-last tensors -- with bias +
@@ -1092,14 +1092,10 @@ template <int BM>
 int launch_pers(const GemmArgs& a, hipStream_t s) {
   const int tiles_m = (a.M + BM - 1) / BM, tiles_n = (a.N + 255) / 256;
   const int ntiles = tiles_m * tiles_n;
-  int nblk = ntiles < 256 ? ((ntiles + 7) / 8) * 8 : 256;
   const size_t lds_bytes = 5 * 32768;
   if (int r_ = ensure_dyn_lds((const void*)gemm_pers_kernel<BM>, (int)lds_bytes)) return r_;
-  const double flops = 2.0 * a.M * (double)a.N * a.K;
-  const double bytes = ((double)a.M * a.K + (double)a.N * a.K) * 2 + (double)a.M * a.N * (a.out_f32 ? 4 : 2);
-  prof_begin(s);
-  hipLaunchKernelGGL((gemm_pers_kernel<BM>), dim3(nblk), dim3(512), lds_bytes, s, a, tiles_n, ntiles);
-  prof_end(s, flops, bytes, 0);
+  // (one workgroup per CU: svt_debug_set key 37 does not apply to this kernel)
+  hipLaunchKernelGGL((gemm_pers_kernel<BM>), dim3(persistent_blocks(ntiles, 256)), dim3(512), lds_bytes, s, a, tiles_n, ntiles);
   SVT_LAUNCH_CHECK();
   return 0;
 }
@@ -1110,14 +1106,31 @@ int launch_pp8(const GemmArgs& a, hipStream_t s) {
   dim3 grid(tiles_m * tiles_n, a.nz, 1);
   const size_t lds_bytes = 5 * 32768;
   if (int r_ = ensure_dyn_lds((const void*)gemm_pp8_kernel<BM, GEN, NBW>, (int)lds_bytes)) return r_;
-  const double flops = 2.0 * a.M * (double)a.N * a.K * a.nz;
-  const double bytes = ((double)a.M * a.K + (double)a.N * a.K) * 2 * a.nz + (double)a.M * a.N * a.nz * (a.out_f32 ? 4 : 2);
-  prof_begin(s);
   hipLaunchKernelGGL((gemm_pp8_kernel<BM, GEN, NBW>), grid, dim3(512), lds_bytes, s, a);
-  prof_end(s, flops, bytes, 0);
   SVT_LAUNCH_CHECK();
   return 0;
 }
+
+// DBG > 0 (the diagnostic forms) launch one z only
+template <bool F16, int NBS, int DBG = 0>
+int launch_x3s(const GemmArgs& a, const void* packed, hipStream_t s) {
+  const long tiles = (long)((a.M + 255) / 256) * ((a.N + 64 * NBS - 1) / (64 * NBS));
+  const size_t lds_bytes = 5 * 32768;
+  if (int r_ = ensure_dyn_lds((const void*)gemm_x3s_kernel<F16, NBS, DBG>, (int)lds_bytes)) return r_;
+  hipLaunchKernelGGL((gemm_x3s_kernel<F16, NBS, DBG>), dim3((unsigned)tiles, DBG ? 1u : (unsigned)a.nz), dim3(512), lds_bytes, s, a, packed);
+  SVT_LAUNCH_CHECK();
+  return 0;
+}
+
+#ifdef SVT_DIAG
+template <int NBS>
+int launch_x3s_stamped(int form, const GemmArgs& a, const void* packed, hipStream_t s) {
+  if (form == 11) return launch_x3s<true, NBS, 11>(a, packed, s);
+  if (form == 12) return launch_x3s<true, NBS, 12>(a, packed, s);
+  if (form == 13) return launch_x3s<true, NBS, 13>(a, packed, s);
+  return launch_x3s<true, NBS, 14>(a, packed, s);
+}
+#endif
 
 }  // namespace
 
@@ -1159,248 +1172,52 @@ void split_weights_forget(const void* w_f32) {
   dev_free(it->second.packed);
   g_split_w.erase(it);
 }
-// launches the LDS-DMA split kernel when `a` is a plain (un-batched) product against a registered weight matrix; returns
-// 1 when the caller has to use the register-staged split kernel instead, 0 on success, < 0 on error
-// svt_debug_set key 34 (tile_walk, common.h).  The automatic choice: panels when W does not fit an XCD's L2 beside the A stream and the
-// problem has enough columns of tiles to form them.
-int g_gemm_walk = -1;
-int g_conv_kperm = 1;   // svt_debug_set key 35
-int g_gemm_persist_wgs = 256;   // svt_debug_set key 37
-int gemm_walk_pm(const GemmArgs& a, int bm) {
-  if (g_gemm_walk >= 0) return g_gemm_walk;
-  const int tiles_n = a.N / 256, tiles_m = (a.M + bm - 1) / bm;
-  const double w_bytes = (double)a.N * a.K * 2.0;
-  // measured (profiles/r06_gemm_tile_walk.txt, us at pm = 0 / 8): FFN-1 of the base model (W 4.5 MiB) 76.1 / 70.6, the large FFN-1 (8 MiB) 262 / 255,
-  // the large QKV (6 MiB) 181 / 177, 8192^3 800 / 746; QKV of the base model (W 3.4 MiB: resident) 52.3 / 53.5 -- hence the 4 MiB line
-  if (tiles_n < 8 || tiles_m < 16 || w_bytes <= 4.0 * 1024 * 1024) return 0;
-  return 8;
-}
-int g_x3_pairs = 1;
-int launch_gemm_x3(int kind, const GemmArgs& a, hipStream_t s) {
-  if (a.a_pairs) {
-    // pair-row operand: only gemm_x3q_kernel reads it (the callers in api_encoder.hip ask gemm_x3q_eligible before they choose the layout)
-    if (!gemm_x3q_eligible(a) || a.ldw != a.K) { set_error("gemm: pair-row operand outside the contract of gemm_x3q_kernel"); return -1; }
-    const void* packed = nullptr;
-    {
-      std::lock_guard<std::mutex> lk(g_split_mu);
-      auto it = g_split_w.upper_bound(a.W);
-      if (it != g_split_w.begin()) {
-        --it;
-        const size_t off = (const char*)a.W - (const char*)it->first;
-        if (it->second.kind == kind && it->second.K == a.K && off % ((size_t)a.K * 4) == 0 && off / ((size_t)a.K * 4) + a.N <= (size_t)it->second.N)
-          packed = (const char*)it->second.packed + off;
-      }
-    }
-    if (!packed) { set_error("gemm: pair-row product against a weight matrix that was not registered as split"); return -1; }
-    // tile height: rounds of 256 CUs x measured slab time of that height (the table of launch_gemm_dma)
-    const int cands[3] = {256, 192, 128};
-    const int slab_cost[3] = {167, 137, 105};
-    long best_cost = -1;
-    int best = 256;
-    for (int i = 0; i < 3; ++i) {
-      const long blocks = (long)((a.M + cands[i] - 1) / cands[i]) * (a.N / 256);
-      const long cost = ((blocks + 255) / 256) * slab_cost[i];
-      if (best_cost < 0 || cost < best_cost) { best_cost = cost; best = cands[i]; }
-    }
-    if (g_gemm_force_bm == 256 || g_gemm_force_bm == 192 || g_gemm_force_bm == 128) best = g_gemm_force_bm;
-    GemmArgs g = a;
-    g.planes_f16 = kind == 3;
-    const double flops = 2.0 * a.M * (double)a.N * a.K;
-    const double bytes = ((double)a.M * a.K + (double)a.N * a.K + (double)a.M * a.N) * 4;
-    prof_begin(s);
-    if (g_gemm_p1x && g.K >= 96) { if (int r_ = launch_gemm_p1x(kind, g, packed, best, s)) return r_; }   // one wave per SIMD (gemm_p1x.hip; svt_debug_set key 30 = 1: A/B, same bits)
-    else if (int r_ = launch_gemm_x3q(kind, g, packed, best, s)) return r_;
-    prof_end(s, flops, bytes, 0);
-    return 0;
-  }
-  // batched problems (nz > 1: the grouped positional conv, one z per group): the one-tile kernel with blockIdx.y = z; the registered
-  // matrix holds the groups' rows one after the other
-  const bool batched = a.nz > 1;
-  if (a.gen || a.nz < 1 || a.K % 32 || a.N < 128 || a.M < 128 || !a.c_vec || a.ldw != a.K || a.alpha != 1.f || (a.a_rstride & 3) ||
-      (a.a_bstride & 3) || ((uintptr_t)a.A & 15))
-    return 1;
-  if (!batched && (a.w_z1 || a.w_z2 || a.a_z1 || a.a_z2 || a.c_z1 || a.c_z2)) return 1;
-  if (batched && (a.planes || a.resid || a.nz2 < 1 || a.nz % a.nz2 || (a.a_z1 & 3) || (a.a_z2 & 3) || (a.c_z1 & 3) || (a.c_z2 & 3) || (a.bias_z2 & 3) ||
-                  a.w_z1 % a.K || a.w_z2 % a.K || a.nz > 65535))
-    return 1;
-  const void* packed = nullptr;
-  {
-    std::lock_guard<std::mutex> lk(g_split_mu);
-    // the weight pointer may point INTO a registered matrix (row offset): find the matrix that contains it
-    auto it = g_split_w.upper_bound(a.W);
-    if (it == g_split_w.begin()) return 1;
-    --it;
-    const char* base = (const char*)it->first;
-    const size_t off = (const char*)a.W - base;
-    if (it->second.kind != kind || it->second.K != a.K || off % ((size_t)a.K * 4) != 0) return 1;
-    const size_t row = off / ((size_t)a.K * 4);
-    const size_t last_z_row = batched ? ((size_t)(a.nz / a.nz2 - 1) * a.w_z1 + (size_t)(a.nz2 - 1) * a.w_z2) / (size_t)a.K : 0;
-    if (row + last_z_row + a.N > (size_t)it->second.N) return 1;
-    packed = (const char*)it->second.packed + row * (size_t)a.K * 4;
-  }
-  {
-    // the kernels address a tile's rows by 32-bit offsets from its first row, and the packed weights by 32-bit offsets from their base
-    const unsigned long clips = 255 / (unsigned long)(a.a_rpb > 0 ? a.a_rpb : 1) + 1;
-    const unsigned long bs = (unsigned long)(a.a_bstride > 0 ? a.a_bstride : 0), rs = (unsigned long)(a.a_rstride > 0 ? a.a_rstride : 0);
-    if (a.a_bstride < 0 || a.a_rstride <= 0 || (clips * bs + 256ul * rs + (unsigned long)a.K) * 4 >= 0xF0000000ul ||
-        (unsigned long)a.N * a.K * 4 >= 0xF0000000ul)
-      return 1;
-  }
-  const size_t lds_bytes = 5 * 32768;
-  GemmArgs g = a;
-  g.out_f32 = 1;
-  g.planes_f16 = kind == 3;
-  if (g_gemm_dbg == 9 && a.resid) {   // diagnostics (tools/gemm_trace.py --x3-slots): the trace buffer travels in `resid`
-    g.trace = (long long*)a.resid;
-    g.resid = nullptr;
-    g.stamp_ends = g_stamp_ends;
-  }
-  const double flops = 2.0 * a.M * (double)a.N * a.K * a.nz;
-  const double bytes = ((double)a.M * a.K + (double)a.N * a.K + (double)a.M * a.N) * 4 * a.nz;
-  // tile width: 192 columns when that fills the chip better (N = 768: 252 tiles against 189); g_gemm_variant 30 = the lockstep kernel (A/B)
-  const long tm = (a.M + 255) / 256;
-  const long t256 = tm * ((a.N + 255) / 256), t192 = tm * ((a.N + 191) / 192);
-  auto rounds = [](long t) { return (t + 255) / 256; };
-  const bool narrow = a.N % 192 == 0 && rounds(t192) * 3 < rounds(t256) * 4;
-  prof_begin(s);
-  // persistent form (gemm_x3p.hip: register epilogue, stores under the next tile's MFMAs) wherever it is eligible; 192-column tiles of
-  // the one-tile kernel when they fill the chip better and the launch is a single round anyway (svt_debug_set key 3: 32 = never the
-  // persistent form, 34 = always when eligible -- A/B)
-  // Measured per shape (profiles/r03_gemm_x3_variants.txt): the persistent form is ahead on the launches with a heavy epilogue and
-  // several tiles per CU (conv 1-4, FFN-1: GELU over fp32 outputs), the one-tile kernel on the plain projections (QKV, out-proj, FFN-2).
-  const bool x3p_ok = !batched && gemm_x3p_eligible(g) && g_gemm_variant != 30 && g_gemm_variant != 31 && g_gemm_variant != 32 && g_gemm_variant != 33;
-  if (x3p_ok && (g_gemm_variant == 34 || (a.act == ACT_GELU && t256 > 256) || t256 >= 1024)) {   // (large QKV, 1 500 tiles: 547 against 583 us)
-    g.dbg = g_gemm_dbg == 9 ? 0 : g_gemm_dbg;
-    if (int r_ = launch_gemm_x3p(kind, g, packed, s)) return r_;
-#ifdef SVT_DIAG
-  } else if (g.trace && kind == 3 && g.stamp_ends >= 1 && g.stamp_ends <= 4) {   // slot stamps of the one-tile kernel (diagnostics; make DIAG=1)
-#define SVT_X3S_STAMP(NBS_, D_)                                                                                    \
-  {                                                                                                                 \
-    if (int r_ = ensure_dyn_lds((const void*)gemm_x3s_kernel<true, NBS_, D_>, (int)lds_bytes)) return r_;           \
-    hipLaunchKernelGGL((gemm_x3s_kernel<true, NBS_, D_>), dim3((unsigned)(narrow ? t192 : t256)), dim3(512), lds_bytes, s, g, packed); \
-  }
-    if (narrow) {
-      if (g.stamp_ends == 1) SVT_X3S_STAMP(3, 11) else if (g.stamp_ends == 2) SVT_X3S_STAMP(3, 12)
-      else if (g.stamp_ends == 3) SVT_X3S_STAMP(3, 13) else SVT_X3S_STAMP(3, 14)
-    } else {
-      if (g.stamp_ends == 1) SVT_X3S_STAMP(4, 11) else if (g.stamp_ends == 2) SVT_X3S_STAMP(4, 12)
-      else if (g.stamp_ends == 3) SVT_X3S_STAMP(4, 13) else SVT_X3S_STAMP(4, 14)
-    }
-#undef SVT_X3S_STAMP
-  } else if ((g_gemm_variant == 31 || g_gemm_variant == 33) && kind == 3) {
-    if (g_gemm_variant == 31) {
-      if (int r_ = ensure_dyn_lds((const void*)gemm_x3s_kernel<true, 4, 1>, (int)lds_bytes)) return r_;
-      hipLaunchKernelGGL((gemm_x3s_kernel<true, 4, 1>), dim3((unsigned)t256), dim3(512), lds_bytes, s, g, packed);
-    } else {
-      if (int r_ = ensure_dyn_lds((const void*)gemm_x3s_kernel<true, 4, 3>, (int)lds_bytes)) return r_;
-      hipLaunchKernelGGL((gemm_x3s_kernel<true, 4, 3>), dim3((unsigned)t256), dim3(512), lds_bytes, s, g, packed);
-    }
-#endif
-  } else if (narrow) {
-    if (kind == 3) {
-      if (int r_ = ensure_dyn_lds((const void*)gemm_x3s_kernel<true, 3>, (int)lds_bytes)) return r_;
-      hipLaunchKernelGGL((gemm_x3s_kernel<true, 3>), dim3((unsigned)t192, (unsigned)a.nz), dim3(512), lds_bytes, s, g, packed);
-    } else {
-      if (int r_ = ensure_dyn_lds((const void*)gemm_x3s_kernel<false, 3>, (int)lds_bytes)) return r_;
-      hipLaunchKernelGGL((gemm_x3s_kernel<false, 3>), dim3((unsigned)t192, (unsigned)a.nz), dim3(512), lds_bytes, s, g, packed);
-    }
-  } else {
-    if (kind == 3) {
-      if (int r_ = ensure_dyn_lds((const void*)gemm_x3s_kernel<true, 4>, (int)lds_bytes)) return r_;
-      hipLaunchKernelGGL((gemm_x3s_kernel<true, 4>), dim3((unsigned)t256, (unsigned)a.nz), dim3(512), lds_bytes, s, g, packed);
-    } else {
-      if (int r_ = ensure_dyn_lds((const void*)gemm_x3s_kernel<false, 4>, (int)lds_bytes)) return r_;
-      hipLaunchKernelGGL((gemm_x3s_kernel<false, 4>), dim3((unsigned)t256, (unsigned)a.nz), dim3(512), lds_bytes, s, g, packed);
-    }
-  }
-  prof_end(s, flops, bytes, 0);
-  SVT_LAUNCH_CHECK();
-  return 0;
+const void* split_weights_find(const void* W, int kind, int K, long rows_needed) {
+  std::lock_guard<std::mutex> lk(g_split_mu);
+  // the weight pointer may point INTO a registered matrix (row offset): find the matrix that contains it
+  auto it = g_split_w.upper_bound(W);
+  if (it == g_split_w.begin()) return nullptr;
+  --it;
+  const size_t off = (const char*)W - (const char*)it->first, row_bytes = (size_t)K * 4;
+  if (it->second.kind != kind || it->second.K != K || off % row_bytes != 0 || off / row_bytes + (size_t)rows_needed > (size_t)it->second.N)
+    return nullptr;
+  return (const char*)it->second.packed + off;
 }
 
 bool gemm_dma_eligible(const GemmArgs& a) { return a.K % 64 == 0 && a.N >= 128 && a.M >= 128 && a.c_vec && a.N % 8 == 0; }
 
-// Dispatch.  Tile height BM minimises (rounds of 256 CUs) x BM; ties go to the larger tile (higher arithmetic
-// intensity against the L2->LDS fill rate).  Problems with at least two full rounds of tiles run the persistent
-// kernel (epilogue stores and the next tile's fills overlap the MFMAs); single-round problems run the
-// one-tile-per-workgroup kernel, whose LDS-transposed epilogue stores whole 128-byte lines.
-int g_gemm_dbg = 0;
-int g_gemm_force_bm = 0;
-int g_gemm_variant = 0;
-int g_stamp_ends = 0;   // svt_debug_set key 15: which slot stamps of gemm_x3p_kernel / gemm_x3s_kernel a DIAG build takes (tools/gemm_trace.py --x3-slots)
-int g_gemm_ring = 0;  // 0 = auto; 2 = force the one-tile-per-workgroup kernel, 4 = force the persistent kernel (diagnostics)
-int launch_gemm_dma(const GemmArgs& a0, hipStream_t s) {
-  GemmArgs a = a0;
-  a.dbg = g_gemm_dbg;
-  if (a.dbg == 9) { a.trace = (long long*)a.resid; a.resid = nullptr; if (g_gemm_variant) a.dbg = g_gemm_variant; }
-  const int tiles_n = (a.N + 255) / 256;
-  // Tile height: minimise (rounds of 256 CUs) x (time of one K slab at that height).  The slab times are measured
-  // (tools/gemm_trace.py / gemm_bench.py --bm): 1.67 / 1.37 / 1.05 / 0.85 us for 256 / 192 / 128 / 64 rows -- a shorter tile
-  // does proportionally less MFMA work but moves the same 32 KiB of W per slab through the CU, so it only pays when it
-  // saves whole rounds.  Ties go to the larger tile.
-  const int cands[4] = {256, 192, 128, 64};
-  const int slab_cost[4] = {167, 137, 105, 85};
-  long best_cost = -1;
-  int best = 256;
-  for (int i = 0; i < 4; ++i) {
-    const int bm = cands[i];
-    const long blocks = (long)((a.M + bm - 1) / bm) * tiles_n * a.nz;
-    const long rounds = (blocks + 255) / 256;
-    const long cost = rounds * slab_cost[i];
-    if (best_cost < 0 || cost < best_cost) { best_cost = cost; best = bm; }
-  }
-  if (g_gemm_force_bm) best = g_gemm_force_bm;
-  if (a.gen) {  // generalised addressing: one-tile kernel only (it also carries the residual epilogue)
-    // 128-channel outputs (second stage of the lip front-end) get a 128-column tile: a 256-wide tile would multiply
-    // zeros for half of its MFMAs
-    // (a 64-column tile, NBW = 1, is LDS-read bound -- 18 fragment reads per 16 MFMAs -- and measured slower than the
-    // register-staged kernel: 64-channel layers stay there)
-    if (a.N <= 128) return launch_pp8<256, true, 2>(a, s);
-    if (best == 256) return launch_pp8<256, true>(a, s);
-    if (best == 192) return launch_pp8<192, true>(a, s);
+// bm: 256 / 192 / 128, anything else 64 (generalised addressing: 128); bn = 128 (generalised addressing only, 256-row tiles) or 256
+int launch_gemm_pp8(const GemmArgs& a, int bm, int bn, hipStream_t s) {
+  if (a.gen) {
+    if (bn == 128) return launch_pp8<256, true, 2>(a, s);
+    if (bm == 256) return launch_pp8<256, true>(a, s);
+    if (bm == 192) return launch_pp8<192, true>(a, s);
     return launch_pp8<128, true>(a, s);
   }
-  const long ntiles = (long)((a.M + best - 1) / best) * tiles_n;
-  // Persistent staggered kernel (gemm_pps.hip): bf16 outputs without residual, from 100 tiles up.  With several tiles per workgroup
-  // the prologue, the epilogue stores and the next tile's fills overlap; on single-round launches its register epilogue costs
-  // 1.3 us against 4 us for the LDS-transposed one of gemm_pp8_kernel, and since its slab loop lost the per-slab register swaps
-  // (gemm_pps.hip) it is as fast per slab: FFN-2 (252 tiles, K = 3072) 68.3 -> 61.1 us, the 138-tile FFN-2 of a 35-utterance song
-  // 52.7 -> 48.0, 4096^3 115 -> 109; large FFN-2 (500 tiles, K = 4096) equal.  Measured per shape:
-  // profiles/r03_gemm_vendor_library_yardstick.txt.  Write-through (sc1) stores: the output leaves L2 while the kernel runs instead
-  // of at the kernel boundary (FFN-1: 98 MB, 16 us).
-  // svt_debug_set key 3: 50 - 79 force it (the last digit is its dbg: 53 / 73 = without epilogue), 49 switches it off.
-  if (g_gemm_variant >= 50 && g_gemm_variant < 80 && gemm_pps_eligible(a)) {
-    GemmArgs b = a;
-    b.dbg = g_gemm_variant % 10;
-    return launch_gemm_pps(b, g_gemm_force_bm ? g_gemm_force_bm : (best < 128 ? 128 : best), s);
-  }
-  if (g_gemm_variant != 49 && g_gemm_ring == 0 && best >= 128 && ntiles >= 100 && gemm_pps_eligible(a)) {
-    // single-wave-per-SIMD kernel (gemm_p1w.hip, round 5): 5-11 % faster per launch wherever its un-overlapped epilogue is small beside the
-    // tile -- everything except GELU launches with fewer than 16 K slabs (FFN-1 of the base model: 12 slabs, 72.8 us here against 81.9)
-    if (g_gemm_p1w && a.K >= 192 && (!a.trace || g_gemm_p1w == 2) && (g_gemm_p1w == 2 || !(a.act == ACT_GELU && a.K < 1024))) {   // key 29 = 2: everywhere, traced launches included (tools/gemm_trace.py --p1w)
-      if (a.W_kperm && g_conv_kperm && a.kperm_taps >= 2 && a.kperm_taps <= 3 && a.kperm_cin % 64 == 0 && a.K == a.kperm_taps * a.kperm_cin && a.ldw == a.K) {
-        GemmArgs b = a;   // a kernel-3 convolution: tap-minor K order (GemmArgs::k_taps; the caller's second copy of W is stored that way)
-        b.W = a.W_kperm; b.k_taps = a.kperm_taps; b.k_cin = a.kperm_cin;
-        return launch_gemm_p1w(b, best, s);
-      }
-      return launch_gemm_p1w(a, best, s);
-    }
-    return launch_gemm_pps(a, best, s);
-  }
-  const bool pers_ok = !a.resid && a.nz == 1 && a.K >= 128 && a.N % 256 == 0 && a.c_z1 == 0 && a.c_z2 == 0 &&
-                       a.a_z1 == 0 && a.a_z2 == 0 && a.w_z1 == 0 && a.w_z2 == 0;
-  int mode = g_gemm_ring;
-  if (mode == 0) mode = (pers_ok && ntiles >= 512) ? 4 : 2;
-  if (mode == 4 && pers_ok) {
-    if (best == 256) return launch_pers<256>(a, s);
-    if (best == 192) return launch_pers<192>(a, s);
-    if (best == 128) return launch_pers<128>(a, s);
-    return launch_pers<64>(a, s);
-  }
-  if (best == 256) return launch_pp8<256>(a, s);
-  if (best == 192) return launch_pp8<192>(a, s);
-  if (best == 128) return launch_pp8<128>(a, s);
-  return launch_pp8<64>(a, s);  // mid-size problems (2-16 utterances): twice the workgroups of the 128-row tile
+  if (bm == 256) return launch_pp8<256>(a, s);
+  if (bm == 192) return launch_pp8<192>(a, s);
+  if (bm == 128) return launch_pp8<128>(a, s);
+  return launch_pp8<64>(a, s);
+}
+
+// bm: 256 / 192 / 128, anything else 64
+int launch_gemm_pers(const GemmArgs& a, int bm, hipStream_t s) {
+  if (bm == 256) return launch_pers<256>(a, s);
+  if (bm == 192) return launch_pers<192>(a, s);
+  if (bm == 128) return launch_pers<128>(a, s);
+  return launch_pers<64>(a, s);
+}
+
+// kind = svt_precision (2 = bf16 pieces, 3 = fp16 pieces); nbs = 3 / 4 (192- / 256-column tiles); form: 0, or in DIAG builds (fp16 pieces)
+// 1 / 3 = the timing ablations of the 256-column tile (svt_debug_set key 3 = 31 / 33) and 11-14 = the slot stamps (key 15 = 1-4)
+int launch_gemm_x3s(int kind, const GemmArgs& a, const void* packed, int nbs, int form, hipStream_t s) {
+#ifdef SVT_DIAG
+  if (form == 1) return launch_x3s<true, 4, 1>(a, packed, s);
+  if (form == 3) return launch_x3s<true, 4, 3>(a, packed, s);
+  if (form >= 11) return nbs == 3 ? launch_x3s_stamped<3>(form, a, packed, s) : launch_x3s_stamped<4>(form, a, packed, s);
+#endif
+  if (kind == 3) return nbs == 3 ? launch_x3s<true, 3>(a, packed, s) : launch_x3s<true, 4>(a, packed, s);
+  return nbs == 3 ? launch_x3s<false, 3>(a, packed, s) : launch_x3s<false, 4>(a, packed, s);
 }
 
 }  // namespace svt

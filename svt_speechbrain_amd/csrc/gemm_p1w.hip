@@ -374,23 +374,14 @@ template <int BM, int ACT, bool TR = false>
 int launch_p1w_t(const GemmArgs& a, hipStream_t s) {
   const int tiles_m = (a.M + BM - 1) / BM, tiles_n = a.N / 256;
   const int ntiles = tiles_m * tiles_n;
-  const int nblk = ntiles < g_gemm_persist_wgs ? ((ntiles + 7) / 8) * 8 : g_gemm_persist_wgs;   // (svt_debug_set key 37: workgroups of a persistent launch)
   const size_t lds_bytes = 5 * 32768;
-  GemmArgs aw = a;
-  aw.walk_pm = gemm_walk_pm(a, BM);
   if (int r_ = ensure_dyn_lds((const void*)gemm_p1w_kernel<BM, ACT, TR>, (int)lds_bytes)) return r_;
-  const double flops = 2.0 * a.M * (double)a.N * a.K;
-  const double bytes = ((double)a.M * a.K + (double)a.N * a.K) * 2 + (double)a.M * a.N * 2;
-  prof_begin(s);
-  hipLaunchKernelGGL((gemm_p1w_kernel<BM, ACT, TR>), dim3(nblk), dim3(256), lds_bytes, s, aw, tiles_n, ntiles);
-  prof_end(s, flops, bytes, 0);
+  hipLaunchKernelGGL((gemm_p1w_kernel<BM, ACT, TR>), dim3(persistent_blocks(ntiles, g_gemm_persist_wgs)), dim3(256), lds_bytes, s, a, tiles_n, ntiles);
   SVT_LAUNCH_CHECK();
   return 0;
 }
 
 }  // namespace
-
-int g_gemm_p1w = 1;   // svt_debug_set key 29: 1 (default) = this kernel where it measured faster than gemm_pps_kernel (gemm_dma.hip), 0 = never
 
 int launch_gemm_p1w(const GemmArgs& a, int bm, hipStream_t s) {
 #ifdef SVT_DIAG

@@ -23,7 +23,6 @@
 // An A/B arm, not a dispatched kernel: built by `make DIAG=1` only (the shipped library holds what it dispatches: VERDICT r05 #11)
 #if defined(SVT_OPERAND_F16) || !defined(SVT_DIAG)
 namespace svt {
-int g_gemm_p1x = 0;
 int launch_gemm_p1x(int, const GemmArgs&, const void*, int, hipStream_t) { set_error("gemm_p1x: built by `make DIAG=1` (bf16 library) only"); return -1; }
 }  // namespace svt
 #else
@@ -340,10 +339,10 @@ template <bool F16, int BM, int OUT>
 int launch_p1x_t(const GemmArgs& a, const void* packed, hipStream_t s) {
   const int tiles_m = (a.M + BM - 1) / BM, tiles_n = a.N / 256;
   const int ntiles = tiles_m * tiles_n;
-  const int nblk = ntiles < 256 ? ((ntiles + 7) / 8) * 8 : 256;
   const size_t lds_bytes = 5 * 32768;
   if (int r_ = ensure_dyn_lds((const void*)gemm_p1x_kernel<F16, BM, OUT>, (int)lds_bytes)) return r_;
-  hipLaunchKernelGGL((gemm_p1x_kernel<F16, BM, OUT>), dim3(nblk), dim3(256), lds_bytes, s, a, packed, tiles_n, ntiles);
+  // (one workgroup per CU: svt_debug_set key 37 does not apply to this kernel)
+  hipLaunchKernelGGL((gemm_p1x_kernel<F16, BM, OUT>), dim3(persistent_blocks(ntiles, 256)), dim3(256), lds_bytes, s, a, packed, tiles_n, ntiles);
   SVT_LAUNCH_CHECK();
   return 0;
 }
@@ -356,13 +355,6 @@ int launch_p1x_o(const GemmArgs& a, const void* packed, hipStream_t s) {
 }
 
 }  // namespace
-
-// svt_debug_set key 30: 1 = this kernel for every gemm_x3q-eligible launch with K >= 96, 0 (default) = gemm_x3q_kernel.  Measured
-// (profiles/r05_gemm_p1x_ab.txt): bit-identical outputs and the SAME speed -- isolated launches within +-2 % (QKV -5 %, FFN-1 with GELU +3 %),
-// C2 fp16x3 2 567-2 570 against 2 570-2 578 clips/s, C3 1 015 both.  With three MFMAs per algorithmic multiply-add the split products are
-// bound by the matrix pipe at the clock the chip holds under that load, not by how the slab's loads are scheduled around it; the 16-bit
-// products, where the single-wave loop gained (gemm_p1w.hip), are not.  Kept as the A/B arm and as a second implementation the tests compare.
-int g_gemm_p1x = 0;
 
 // same arguments as launch_gemm_x3q (gemm_x3q.hip); the caller has checked gemm_x3q_eligible and K >= 96
 int launch_gemm_p1x(int kind, const GemmArgs& a, const void* packed, int bm, hipStream_t s) {

@@ -216,20 +216,15 @@ template <int NB>
 int launch_skinny(const GemmArgs& a, hipStream_t s) {
   constexpr int TS = 16 * NB;
   const int tiles_m = (a.M + TS - 1) / TS, tiles_n = (a.N + TS - 1) / TS;
-  const double flops = 2.0 * a.M * (double)a.N * a.K * a.nz;
-  const double bytes = ((double)a.M * a.K + (double)a.N * a.K) * 2 * a.nz + (double)a.M * a.N * a.nz * (a.out_f32 ? 4 : 2);
   const size_t lds_bytes = 4 * TS * (TS + 4) * sizeof(float);
   if (int r_ = ensure_dyn_lds((const void*)gemm_skinny_kernel<NB>, (int)lds_bytes)) return r_;
-  prof_begin(s);
   hipLaunchKernelGGL((gemm_skinny_kernel<NB>), dim3(tiles_m * tiles_n, a.nz, a.ksplit > 1 ? a.ksplit : 1), dim3(256), lds_bytes, s, a);
-  prof_end(s, flops, bytes, 1);
   SVT_LAUNCH_CHECK();
   return 0;
 }
 
 }  // namespace
 
-int g_gemm_skinny_max_tiles = 32;  // svt_debug_set key 7 (threshold sweeps)
 // Small problems only: the large-tile kernels are faster as soon as they can fill the chip.
 bool gemm_skinny_eligible(const GemmArgs& a) {
   if (a.gen || a.K % 64 != 0 || a.N % 16 != 0 || !a.c_vec || a.resid_op_type || a.slope || a.act == ACT_PRELU) return false;
@@ -238,12 +233,11 @@ bool gemm_skinny_eligible(const GemmArgs& a) {
 }
 
 int g_ffn2_ksplit = 1;   // svt_debug_set key 36: the encoder's FFN-2 of a small batch as a K-split launch of this kernel (api_encoder.hip)
-int g_gemm_skinny_small_tiles = 96;   // svt_debug_set key 33: 32 x 32 tiles while the 64 x 64 tiling has at most this many workgroups
-int launch_gemm_skinny(const GemmArgs& a, hipStream_t s) {
+// tile = 64 (64 x 64 tiles) or 32 (32 x 32)
+int launch_gemm_skinny_tile(const GemmArgs& a, int tile, hipStream_t s) {
   if (a.ksplit > 1 && (a.bias || a.resid || a.act != ACT_NONE || !a.out_f32 || a.alpha != 1.f || (a.K / 64) < a.ksplit || a.ksplit_stride < (long)a.M * a.ldc)) {
     set_error("gemm_skinny: a K-split launch writes raw fp32 partial tiles (no bias / activation / residual)"); return -1; }
-  const long tiles64 = (long)((a.M + 63) / 64) * ((a.N + 63) / 64) * a.nz;
-  return tiles64 <= g_gemm_skinny_small_tiles ? launch_skinny<2>(a, s) : launch_skinny<4>(a, s);
+  return tile == 32 ? launch_skinny<2>(a, s) : launch_skinny<4>(a, s);
 }
 
 }  // namespace svt

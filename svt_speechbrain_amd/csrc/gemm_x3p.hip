@@ -20,7 +20,7 @@
 //     (hi, lo) plane output of the QKV projection;
 //   * staggering, tile boundaries, unconditional ring requests, the bias fetched inside the stream and the vector-offset stores
 //     (soffset hazard) are those of gemm_pps_kernel.
-// Contract: a plain product against a registered split weight matrix (launch_gemm_x3 resolves it), N % 256 == 0, K % 32 == 0, K >= 64,
+// Contract: a plain product against a registered split weight matrix (gemm_dispatch.hip resolves it), N % 256 == 0, K % 32 == 0, K >= 64,
 // no residual, activation none or GELU, fp32 C or (hi, lo) planes.  Everything else stays on gemm_x3s_kernel.
 #include "common.h"
 
@@ -406,10 +406,10 @@ template <bool F16, bool PLANES, int STAMP = 0>
 int launch_x3p_t(const GemmArgs& a, const void* packed, hipStream_t s) {
   const int tiles_m = (a.M + 255) / 256, tiles_n = a.N / 256;
   const int ntiles = tiles_m * tiles_n;
-  const int nblk = ntiles < 256 ? ((ntiles + 7) / 8) * 8 : 256;
   const size_t lds_bytes = 5 * 32768;
   if (int r_ = ensure_dyn_lds((const void*)gemm_x3p_kernel<F16, PLANES, STAMP>, (int)lds_bytes)) return r_;
-  hipLaunchKernelGGL((gemm_x3p_kernel<F16, PLANES, STAMP>), dim3(nblk), dim3(512), lds_bytes, s, a, packed, tiles_n, ntiles);
+  // (one workgroup per CU: svt_debug_set key 37 does not apply to this kernel)
+  hipLaunchKernelGGL((gemm_x3p_kernel<F16, PLANES, STAMP>), dim3(persistent_blocks(ntiles, 256)), dim3(512), lds_bytes, s, a, packed, tiles_n, ntiles);
   SVT_LAUNCH_CHECK();
   return 0;
 }
@@ -417,17 +417,13 @@ int launch_x3p_t(const GemmArgs& a, const void* packed, hipStream_t s) {
 }  // namespace
 
 bool gemm_x3p_eligible(const GemmArgs& a) {
-  // a tile's rows are addressed by 32-bit offsets from its first row: 256 rows, possibly across clip boundaries
-  const unsigned long clips = 255 / (unsigned long)(a.a_rpb > 0 ? a.a_rpb : 1) + 1;
-  const unsigned long bs = (unsigned long)(a.a_bstride > 0 ? a.a_bstride : 0), rs = (unsigned long)(a.a_rstride > 0 ? a.a_rstride : 0);
-  const unsigned long tile_span = (clips * bs + 256ul * rs + (unsigned long)a.K) * 4;
   return !a.gen && a.nz == 1 && !a.resid && a.alpha == 1.f && (a.act == ACT_NONE || a.act == ACT_GELU) && !(a.planes && a.act != ACT_NONE) &&
-         a.K % 32 == 0 && a.K >= 64 && a.N % 256 == 0 && a.M >= 128 && a.c_vec && a.ldc % 4 == 0 && a.a_bstride >= 0 && a.a_rstride > 0 &&
-         tile_span < 0xF0000000ul && (unsigned long)a.N * a.K * 4 < 0xF0000000ul && ((uintptr_t)a.A & 15) == 0 && (a.a_rstride & 3) == 0 &&
+         a.K % 32 == 0 && a.K >= 64 && a.N % 256 == 0 && a.M >= 128 && a.c_vec && a.ldc % 4 == 0 && tile_span_fits(a) &&
+         ((uintptr_t)a.A & 15) == 0 && (a.a_rstride & 3) == 0 &&
          (a.a_bstride & 3) == 0 && (!a.planes || (((uintptr_t)a.planes & 7) == 0 && (a.plane_stride & 3) == 0));
 }
 
-// kind = svt_precision (2 = bf16 pieces, 3 = fp16 pieces); `packed` = the registered (hi, lo) image of the weight rows (launch_gemm_x3)
+// kind = svt_precision (2 = bf16 pieces, 3 = fp16 pieces); `packed` = the registered (hi, lo) image of the weight rows (gemm_dispatch.hip)
 int launch_gemm_x3p(int kind, const GemmArgs& a, const void* packed, hipStream_t s) {
   const bool f16 = kind == 3;
 #ifdef SVT_DIAG

@@ -354,10 +354,9 @@ template <bool F16, int BM, int OUT, int DBG = 0>
 int launch_x3q_t(const GemmArgs& a, const void* packed, hipStream_t s) {
   const int tiles_m = (a.M + BM - 1) / BM, tiles_n = a.N / 256;
   const int ntiles = tiles_m * tiles_n;
-  const int nblk = ntiles < g_gemm_persist_wgs ? ((ntiles + 7) / 8) * 8 : g_gemm_persist_wgs;   // (svt_debug_set key 37: workgroups of a persistent launch)
   const size_t lds_bytes = 5 * 32768;
   if (int r_ = ensure_dyn_lds((const void*)gemm_x3q_kernel<F16, BM, OUT, DBG>, (int)lds_bytes)) return r_;
-  hipLaunchKernelGGL((gemm_x3q_kernel<F16, BM, OUT, DBG>), dim3(nblk), dim3(512), lds_bytes, s, a, packed, tiles_n, ntiles);
+  hipLaunchKernelGGL((gemm_x3q_kernel<F16, BM, OUT, DBG>), dim3(persistent_blocks(ntiles, g_gemm_persist_wgs)), dim3(512), lds_bytes, s, a, packed, tiles_n, ntiles);
   SVT_LAUNCH_CHECK();
   return 0;
 }
@@ -372,19 +371,15 @@ int launch_x3q_o(const GemmArgs& a, const void* packed, hipStream_t s) {
 }  // namespace
 
 bool gemm_x3q_eligible(const GemmArgs& a) {
-  // a tile's rows are addressed by 32-bit offsets from its first row: 256 rows, possibly across clip boundaries
-  const unsigned long clips = 255 / (unsigned long)(a.a_rpb > 0 ? a.a_rpb : 1) + 1;
-  const unsigned long bs = (unsigned long)(a.a_bstride > 0 ? a.a_bstride : 0), rs = (unsigned long)(a.a_rstride > 0 ? a.a_rstride : 0);
-  const unsigned long tile_span = (clips * bs + 256ul * rs + (unsigned long)a.K) * 4;
   const bool planes_ok = !a.planes || (a.act == ACT_NONE && !a.c_pairs && ((uintptr_t)a.planes & 15) == 0 && (a.plane_stride & 7) == 0 && a.ldc % 8 == 0);
   const bool pairs_ok = !a.c_pairs || (a.ldc % 32 == 0 && ((uintptr_t)a.C & 127) == 0);
   return a.a_pairs && !a.gen && a.nz == 1 && !a.resid && a.alpha == 1.f && (a.act == ACT_NONE || a.act == ACT_GELU) && a.K % 32 == 0 &&
-         a.K >= 64 && a.N % 256 == 0 && a.M >= 128 && a.ldc % 4 == 0 && a.a_bstride >= 0 && a.a_rstride > 0 && a.a_rstride % 32 == 0 &&
-         a.a_bstride % 32 == 0 && tile_span < 0xF0000000ul && (unsigned long)a.N * a.K * 4 < 0xF0000000ul && ((uintptr_t)a.A & 127) == 0 &&
+         a.K >= 64 && a.N % 256 == 0 && a.M >= 128 && a.ldc % 4 == 0 && a.a_rstride % 32 == 0 && a.a_bstride % 32 == 0 &&
+         tile_span_fits(a) && ((uintptr_t)a.A & 127) == 0 &&
          ((uintptr_t)a.C & 15) == 0 && ((uintptr_t)a.bias & 15) == 0 && planes_ok && pairs_ok;
 }
 
-// kind = svt_precision (2 = bf16 pieces, 3 = fp16 pieces); `packed` = the registered (hi, lo) image of the weight rows (launch_gemm_x3);
+// kind = svt_precision (2 = bf16 pieces, 3 = fp16 pieces); `packed` = the registered (hi, lo) image of the weight rows (gemm_dispatch.hip);
 // bm = tile height (256 / 192 / 128)
 int launch_gemm_x3q(int kind, const GemmArgs& a, const void* packed, int bm, hipStream_t s) {
 #ifdef SVT_DIAG
