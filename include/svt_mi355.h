@@ -361,6 +361,13 @@ int svt_clip_adadelta_step(int32_t n_tensors, float* const* params_dev, float* c
 int svt_debug_attention(int32_t precision, const void* q, const void* k, const void* v, void* o, int32_t batch, int32_t t,
                         int32_t heads, int32_t head_dim, int64_t ldq, int64_t ldkv, int64_t ldo, float scale, int device,
                         void* stream);
+/* The same kernel with WavLM's gated relative position bias (operand-type q / k / v / o, head_dim 64):
+ * score(b, h, q, key) = scale q.k + gate[b, h, q] * pos_bias[h, key - q + t - 1], gate_dev (batch, heads, t) f32, pos_bias_dev
+ * (heads, 2 t - 1) f32.  The bias row of a head stays in LDS: a t with 2 t - 1 > 8192 is refused (SVT_ERR_INVALID, nothing is launched).
+ * Exposed for tests/test_gpu_attention.py: the encoder reaches these kernels only through a whole WavLM forward. */
+int svt_debug_attention_bias(const void* q, const void* k, const void* v, void* o, int32_t batch, int32_t t, int32_t heads, int64_t ldq,
+                             int64_t ldkv, int64_t ldo, float scale, const float* gate_dev, const float* pos_bias_dev, int device,
+                             void* stream);
 /* The RCA training kernels alone (tests/test_gpu_fusion_train.py), precision 0 (fp32) or 1 (bf16 operands); workspace convention of
  * svt_linear_backward.  svt_debug_rca_wgrad: dw (n_out, n_in) = sum over the rows of one or two segments of dy_s^T x_s (dy f32 with row
  * strides ldy_s, x operand type (rows, n_in); dy1 / x1 NULL for one segment), db (may be NULL) = the column sums of dy.
@@ -400,8 +407,12 @@ int svt_debug_rca_attn_bwd(int32_t precision, const void* qkv, const void* qc, c
  * tile_walk; same bits), 35 = the kernel-3 convolutions' K slabs tap-minor (1, default: the frame two neighbouring output rows share is
  * re-read out of L2) or tap-major (0) on gemm_p1w_kernel, 36 = FFN-2 of a small batch (<= 2048 rows) as a K-split small GEMM whose
  * partial products the following LayerNorm adds (1, default) or as one product (0), 37 = workgroups of a persistent GEMM launch (8 .. 256,
- * a multiple of 8; 256 = one per CU, default).
- * Returns 0 (keys 24, 31: the count), SVT_ERR_INVALID for an unknown key or a value a key does not accept (21, 28, 30, 37 above). */
+ * a multiple of 8; 256 = one per CU, default), 38 = query: returns the id of the fused attention kernel the last attention launch of
+ * this process chose (value ignored; 0 = none yet): 1 = flash_attn_kernel<64>, 2 = flash_attn_kernel<128>, 3 = flash_attn_stag_kernel<64>
+ * (head_dim 64, "wide" launches), 4 = flash_attn_kernel<64, true> (position bias), 5 = flash_attn_kernel<64, true, 8> (position bias,
+ * wide), 6 = flash_attn_x3_kernel<64, .>, 7 = flash_attn_x3_kernel<128, .>, 8 = flash_attn_x3_stag_kernel<.> (split-operand modes;
+ * tests/test_gpu_attention.py asserts the id of every case).
+ * Returns 0 (keys 24, 31: the count; key 38: the id), SVT_ERR_INVALID for an unknown key or a value a key does not accept (21, 28, 30, 37 above). */
 int svt_debug_set(int key, int value);
 
 /* ---- measurement hook: HIP-event timing of the dominant kernel on the stream it runs on ----

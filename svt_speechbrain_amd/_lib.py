@@ -128,6 +128,8 @@ SYMBOLS = {
                                          _P]),
     "svt_debug_attention": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
                                       C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_float, C.c_int, C.c_void_p]),
+    "svt_debug_attention_bias": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int64,
+                                           C.c_int64, C.c_int64, C.c_float, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "svt_debug_rca_wgrad": (C.c_int, [C.c_int32, _P, C.c_int64, _P, _P, C.c_int64, _P, C.c_int64, C.c_int32, C.c_int32, _P, _P, _P,
                                       C.POINTER(C.c_size_t), C.c_int, _P]),
     "svt_debug_rca_attn_bwd": (C.c_int, [C.c_int32, _P, _P, _P, _P, _P, C.c_float, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P,

@@ -426,6 +426,18 @@ int svt_debug_attention(int32_t precision, const void* q, const void* k, const v
   return SVT_OK;
 }
 
+int svt_debug_attention_bias(const void* q, const void* k, const void* v, void* o, int32_t batch, int32_t t, int32_t heads, int64_t ldq,
+                             int64_t ldkv, int64_t ldo, float scale, const float* gate_dev, const float* pos_bias_dev, int device,
+                             void* stream) {
+  if (!q || !k || !v || !o || !gate_dev || !pos_bias_dev) { set_error("svt_debug_attention_bias: null argument"); return SVT_ERR_INVALID; }
+  if (batch < 1 || t < 1 || heads < 1) { set_error("svt_debug_attention_bias: batch, t and heads must be positive"); return SVT_ERR_INVALID; }
+  if (int r = check_device(device)) return r;
+  SVT_HIP(hipSetDevice(device));
+  if (launch_flash_attention(q, ldq, (long)t * ldq, k, v, ldkv, (long)t * ldkv, o, ldo, (long)t * ldo, batch, t, heads, 64, scale,
+                             (hipStream_t)stream, gate_dev, pos_bias_dev)) return SVT_ERR_INVALID;
+  return SVT_OK;
+}
+
 int svt_debug_set(int key, int value) {
   if (key == 0) g_gemm_dbg = value;
   else if (key == 1) g_gemm_force_bm = value;
@@ -474,6 +486,7 @@ int svt_debug_set(int key, int value) {
   else if (key == 35) g_conv_kperm = value;
   else if (key == 36) g_ffn2_ksplit = value;
   else if (key == 37) { if (value < 8 || value > 256 || value % 8) { set_error("svt_debug_set(37): 8 .. 256, a multiple of 8"); return SVT_ERR_INVALID; } g_gemm_persist_wgs = value; }
+  else if (key == 38) return g_flash_kernel_id;
   else { set_error("svt_debug_set: unknown key"); return SVT_ERR_INVALID; }
   return SVT_OK;
 }

@@ -1018,6 +1018,12 @@ int launch_split_planes(int kind, const float* src, long ld_src, long rows, int 
   return 0;
 }
 
+// svt_debug_set key 38 returns it: which fused attention kernel the last launch of this process chose (0 = none yet), so that the
+// tests name the kernel they reached instead of restating the launchers' predicates.  1 = flash_attn_kernel<64>, 2 = flash_attn_kernel<128>,
+// 3 = flash_attn_stag_kernel<64>, 4 = flash_attn_kernel<64, true>, 5 = flash_attn_kernel<64, true, 8>, 6 = flash_attn_x3_kernel<64, F16>,
+// 7 = flash_attn_x3_kernel<128, F16>, 8 = flash_attn_x3_stag_kernel<F16>
+int g_flash_kernel_id = 0;
+
 bool flash_attention_x3_ok(int dh) { return dh == 64 || dh == 128; }
 // Q / K / V: 16-bit (hi, lo) planes (launch_split_planes); O fp32
 int launch_flash_attention_x3(int kind, const void* Q, long ldq, long q_bstride, long q_plane, const void* K, const void* V, long ldk,
@@ -1044,9 +1050,10 @@ int launch_flash_attention_x3(int kind, const void* Q, long ldq, long q_bstride,
       hipLaunchKernelGGL((flash_attn_x3_stag_kernel<false>), g1, dim3(512), lds_bytes, s, q, ldq, q_bstride, q_plane, k, v, ldk, k_bstride, k_plane, O,
                          ldo, o_bstride, T, H, c, o_pairs, nqb);
     }
+    g_flash_kernel_id = 8;
   }
-  else if (dh == 64) { if (kind == 3) SVT_X3_LAUNCH(64, true); else SVT_X3_LAUNCH(64, false); }
-  else if (dh == 128) { if (kind == 3) SVT_X3_LAUNCH(128, true); else SVT_X3_LAUNCH(128, false); }
+  else if (dh == 64) { if (kind == 3) SVT_X3_LAUNCH(64, true); else SVT_X3_LAUNCH(64, false); g_flash_kernel_id = 6; }
+  else if (dh == 128) { if (kind == 3) SVT_X3_LAUNCH(128, true); else SVT_X3_LAUNCH(128, false); g_flash_kernel_id = 7; }
   else { set_error("flash_attention_x3: head_dim must be 64 or 128"); return -1; }
 #undef SVT_X3_LAUNCH
   prof_end(s, flops, 0.0, 2);
@@ -1084,6 +1091,7 @@ int launch_flash_attention(const void* Q, long ldq, long q_bstride, const void* 
     else
       hipLaunchKernelGGL((flash_attn_kernel<64, true>), grid, dim3(256), dyn, s, (const bf16_t*)Q, ldq, q_bstride, (const bf16_t*)K,
                          ldk, k_bstride, (const bf16_t*)V, 0, (bf16_t*)O, ldo, o_bstride, T, H, c, gate, pb);
+    g_flash_kernel_id = wide ? 5 : 4;
     prof_end(s, flops, 0.0, 2);
     SVT_LAUNCH_CHECK();
     return 0;
@@ -1094,13 +1102,18 @@ int launch_flash_attention(const void* Q, long ldq, long q_bstride, const void* 
     const int nqb = (T + 255) / 256;
     hipLaunchKernelGGL((flash_attn_stag_kernel<64>), dim3((unsigned)(nqb * B * H)), dim3(512), 0, s, (const bf16_t*)Q, ldq, q_bstride,
                        (const bf16_t*)K, ldk, k_bstride, (const bf16_t*)V, (bf16_t*)O, ldo, o_bstride, T, H, c, nqb);
+    g_flash_kernel_id = 3;
   }
-  else if (dh == 64)
+  else if (dh == 64) {
     hipLaunchKernelGGL((flash_attn_kernel<64>), grid, dim3(256), 0, s, (const bf16_t*)Q, ldq, q_bstride, (const bf16_t*)K,
                        ldk, k_bstride, (const bf16_t*)V, 0, (bf16_t*)O, ldo, o_bstride, T, H, c, nullptr, nullptr);
-  else if (dh == 128)
+    g_flash_kernel_id = 1;
+  }
+  else if (dh == 128) {
     hipLaunchKernelGGL((flash_attn_kernel<128>), grid, dim3(256), 0, s, (const bf16_t*)Q, ldq, q_bstride,
                        (const bf16_t*)K, ldk, k_bstride, (const bf16_t*)V, 0, (bf16_t*)O, ldo, o_bstride, T, H, c, nullptr, nullptr);
+    g_flash_kernel_id = 2;
+  }
   else { set_error("flash_attention: head_dim must be 64 or 128"); return -1; }
   prof_end(s, flops, 0.0, 2);
   SVT_LAUNCH_CHECK();

@@ -337,6 +337,7 @@ extern int g_gemm_persist_wgs;   // key 37: workgroups of a persistent GEMM laun
 
 extern int g_ln_two_rows;  // (hi, lo) LayerNorm: half a wave per row, 16-byte accesses (1, default) or a wave per row (0)
 extern int g_flash_wide;  // fused attention: 8-wave (256-query) workgroups for head_dim 64 (1, default) or 4-wave ones (0)
+extern int g_flash_kernel_id;  // fused attention: id of the kernel the last launch chose (attention.hip; svt_debug_set key 38)
 extern int g_ffn2_ksplit;   // svt_debug_set key 36 (api_encoder.hip): FFN-2 of a small batch as a K-split small GEMM + summing LayerNorm
 // switches of the host entry points, defined beside their users; hidden like the helpers of api.h (not part of the exported symbols)
 #pragma GCC visibility push(hidden)

@@ -58,7 +58,7 @@ def main():
         torch.cuda.synchronize()
         us = e0.elapsed_time(e1) / a.iters * 1e3
         tf = 4.0 * B * H * T * T * dh / us / 1e6
-        print(f"{name:6s} B={B:3d} T={T} H={H:2d} dh={dh:3d}: {us:8.1f} us  {tf:7.1f} TFLOP/s"
+        print(f"{name:6s} B={B:3d} T={T} H={H:2d} dh={dh:3d}: kernel {lib.svt_debug_set(38, 0)} {us:8.1f} us  {tf:7.1f} TFLOP/s"
               + (f"  max|err|={err:.3e}" if err is not None else ""), flush=True)
 
 
