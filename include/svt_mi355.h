@@ -400,7 +400,7 @@ int svt_debug_rca_attn_bwd(int32_t precision, const void* qkv, const void* qc, c
  * on (1, default), everywhere (2) or never (0), 30 = gemm_p1x_kernel (the same loop for the split-operand products on pair rows: 1; DIAG
  * builds only) or gemm_x3q_kernel (0, default: same bits, same speed), 31 = query: returns the number of device buffers this process has
  * FREED so far (value ignored; uploads and re-uploads must not free: tests/test_gpu_uploads.py), 32 = the tickets of the three ordered
- * cross-workgroup sums as acquire-release atomics (1) or relaxed ones behind write-through stores (0, default: kernels.hip,
+ * cross-workgroup sums as acquire-release atomics (1) or relaxed ones behind write-through stores (0, default: stats.hip,
  * last_workgroup; same bits, tests/test_gpu_statistics.py), 33 = the small-problem GEMM uses 32 x 32 tiles while its 64 x 64 tiling has
  * at most this many workgroups (96, default; swept on the one-utterance forward: 150 / 200 / 1000 are 1.5-4.5 % slower), 34 = the
  * persistent 16-bit GEMM kernels' tile walk: -1 (default) chosen per launch, 0 = n fastest, n > 0 = panels of n tile rows (common.h,

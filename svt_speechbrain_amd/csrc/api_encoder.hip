@@ -364,7 +364,7 @@ EncWs carve_encoder(const svt_encoder* e, int B, int64_t L, void* base) {
   Carver cv(base);
   EncWs w;
   // 2 x (sum, sumsq) per norm group (<= B groups) + conv0 window moments, then the scratch of the three ordered sums (tickets + per-workgroup
-  // partials: kernels.hip, last_workgroup); the whole region is zeroed at the start of every forward (the tickets must be)
+  // partials: stats.hip, last_workgroup); the whole region is zeroed at the start of every forward (the tickets must be)
   {
     const int64_t t1 = c.num_conv_layers > 0 ? (L - c.conv_kernel[0]) / c.conv_stride[0] + 1 : 1;
     w.mom_scr[0] = align_up((4 * (size_t)B + (size_t)B * 65) * sizeof(double));
@@ -427,7 +427,7 @@ EncWs carve_encoder(const svt_encoder* e, int B, int64_t L, void* base) {
 }
 
 // Tail of a forward call: either the features (the wrapper's output) or, with a head, logits (+ decoded frames) straight
-// from the un-normalised encoder output (fused out-norm + head + decode, kernels.hip head_dots_kernel).
+// from the un-normalised encoder output (fused out-norm + head + decode, stats.hip head_dots_kernel).
 struct TailSpec {
   float* feats = nullptr;
   const svt_linear* head = nullptr;
@@ -526,7 +526,7 @@ static int encoder_forward_impl(svt_encoder* e, const float* wav, int32_t B, int
     set_error("encoder_forward: features-in mode has no input norm to group");
     return SVT_ERR_INVALID;
   }
-  if (launch_zero_bytes(w.mom, w.mom_zero, s)) return SVT_ERR_HIP;   // (a kernel, not a memset node: see kernels.hip)
+  if (launch_zero_bytes(w.mom, w.mom_zero, s)) return SVT_ERR_HIP;   // (a kernel, not a memset node: see encoder_ops.hip)
   double* wav_mom = c.normalize_wav ? w.mom : nullptr;
   double* out_mom = w.mom + 2 * (size_t)B;
   double* wm = w.mom + 4 * (size_t)B;
@@ -786,7 +786,7 @@ static int encoder_forward_impl(svt_encoder* e, const float* wav, int32_t B, int
   const int tmp_f32 = (prec && vecD) ? 0 : 1;
   if (!c.stable_layer_norm && prec && layernorm_hilo_ok(D) && c.num_layers > 0) {
     // throughput mode: the residual stream lives as a bf16 (hi, lo) pair -- hi IS the operand copy the next GEMM
-    // reads -- so a LayerNorm moves 10 bytes per element instead of 12 (see kernels.hip, layernorm_hilo_kernel)
+    // reads -- so a LayerNorm moves 10 bytes per element instead of 12 (see layernorm.hip, layernorm_hilo_kernel)
     bf16_t* xh = (bf16_t*)w.xb;
     bf16_t* xl = (bf16_t*)w.xlo;
     if (int r = launch_layernorm_hilo(nullptr, nullptr, nullptr, w.preF, rows, D, e->enc_g.as<float>(), e->enc_b.as<float>(), eps,

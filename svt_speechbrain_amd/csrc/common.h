@@ -41,6 +41,7 @@ __device__ __forceinline__ float gelu_fast(float x) {
   const float half_x = 0.5f * x;
   return fmaf(half_x, copysignf(erf_abs, x), half_x);
 }
+__device__ __forceinline__ float gelu_erf(float x) { return gelu_fast(x); }   // the name the exact-erf call sites use
 // the same function on a pair of values with packed fp32 math (v_pk_fma_f32 / v_pk_mul_f32: two lanes-worth of
 // FMA per issue slot; rcp/exp stay scalar): ~10 issue slots per element instead of ~17
 typedef float f32x2_t __attribute__((ext_vector_type(2)));
@@ -360,32 +361,15 @@ void prof_begin(hipStream_t s);
 // kind: 0 = the dominant family (gemm_pps / gemm_pers / gemm_pp8 kernels; the split form of gemm_kernel), 1 = other dense contraction kernels, 2 = flash attention
 void prof_end(hipStream_t s, double flops, double bytes, int kind = 1);
 
-// ---- elementwise / reduction kernels (kernels.hip) ----
-int launch_f32_to_bf16(const float* in, bf16_t* out, int64_t n, hipStream_t s);
-// fp32 <-> pair rows (GemmArgs::a_pairs); lo_plane != nullptr: `in` / `lo_plane` are separate (hi, lo) planes instead
-int launch_f32_to_pairs(int kind, const float* x, void* out, int64_t n, hipStream_t s);
-int launch_pairs_to_f32(int kind, const void* in, const void* lo_plane, float* y, int64_t n, hipStream_t s);
+// ---- sums over the workgroups of a launch (stats.hip): the whole-batch moments, conv layer 0's window moments, the fused frame head ----
+int set_ticket_fenced(int on);   // svt_debug_set key 32 (stats.hip, last_workgroup)
 // moments[0] = sum(x), moments[1] = sum(x^2) over n fp32 values (fp64 accumulation, workgroup partials added in a fixed order: the
 // result is reproducible bit for bit); scratch = moments_scratch_bytes(groups_max) bytes whose first 4 * groups_max bytes are ZERO
-int launch_zero_bytes(void* p, size_t bytes, hipStream_t s);            // kernel nodes instead of memset / memcpy nodes (kernels.hip)
-int launch_copy_f32(const float* in, float* out, int64_t n, hipStream_t s);
-int launch_zero_cols(float* p, int64_t rows, int cols, int64_t ld, hipStream_t s);
-int set_ticket_fenced(int on);   // svt_debug_set key 32 (kernels.hip, last_workgroup)
 int launch_moments(const float* x, int64_t n, double* moments, void* scratch, int groups_max, hipStream_t s, int groups = 1);  // groups > 1: n elements and 2 doubles per group
 size_t moments_scratch_bytes(int groups_max);
 // y = (x - mean) * rsqrt(var + eps) from global moments over n elements (no affine)
 int launch_global_norm(const float* x, float* y, int64_t n, const double* moments, float eps, hipStream_t s, int groups = 1,
                        double n_stat = 0);  // n_stat > 0: the moments were summed over n_stat elements (cross-rank reduction), not n
-
-// row LayerNorm over D: in fp32 or operand type; outputs: yT (operand type, may be null) and yF (fp32, may be null)
-// optional `add` (fp32, same shape) is summed into x before the statistics (residual add fused into the norm);
-// `sumF` (optional) receives x + add (the updated residual stream of the pre-LN encoder)
-int launch_layernorm(int prec, const void* x, int x_is_f32, int64_t rows, int D, const float* gamma,
-                     const float* beta, float eps, int gelu, void* yT, float* yF, hipStream_t s,
-                     const float* add = nullptr, float* sumF = nullptr,
-                     void* yP = nullptr, int pair_kind = 0,    // yP: the result as pair rows (split modes; kind 2 = bf16 / 3 = fp16 pieces)
-                     const void* addP = nullptr);              // addP: a second addend given as pair rows (may alias yP: in place)
-
 // conv layer 0 (Cin = 1) in "group" mode: per-(clip,channel) GroupNorm folded into 11 coefficients
 int launch_conv0_window_moments(const float* wav, int B, int64_t L, int k, int stride, int64_t T1,
                                 double* wm /*B x 65*/, void* scratch /*conv0_window_moments_scratch_bytes; first 4 B bytes ZERO*/, hipStream_t s);
@@ -394,6 +378,34 @@ int launch_conv0_group_coef(const double* wav_moments /*2, or null*/, int64_t n_
                             int64_t T1, int C, int k, const float* w0 /*C x k*/, const float* b0 /*C or null*/,
                             const float* gamma, const float* beta, float eps_wav, float eps_gn,
                             float* coef /*B x C x (k+1)*/, hipStream_t s, int clips_per_norm_group);  // wav_moments: 2 per group
+struct FrameOut { float p_on, p_off; int32_t octave, pitch_class; };
+// fused tail: whole-batch output norm (moments taken in the same pass) + frame head + optional per-frame decode, from the
+// UN-normalised encoder output x (rows x K); dots = rows x N scratch; mom = 2 doubles per norm group (written, reproducible bit for
+// bit) or null; scratch (needed with mom) = head_scratch_bytes(rows, groups) bytes whose first 4 are ZERO
+int launch_head_fused(const float* x, int64_t rows, int K, const float* w, const float* wsum, const float* b, int N, float* dots,
+                      double* mom, int64_t rows_per_group, float eps, float* logits, FrameOut* frames, int n_oct, int n_cls,
+                      hipStream_t s,
+                      double n_stat = 0, int (*between)(void*) = nullptr, void* between_arg = nullptr, void* scratch = nullptr);
+size_t head_scratch_bytes(int64_t rows, int groups_max);
+
+// ---- row LayerNorm (layernorm.hip) ----
+// row LayerNorm over D: in fp32 or operand type; outputs: yT (operand type, may be null) and yF (fp32, may be null)
+// optional `add` (fp32, same shape) is summed into x before the statistics (residual add fused into the norm);
+// `sumF` (optional) receives x + add (the updated residual stream of the pre-LN encoder)
+int launch_layernorm(int prec, const void* x, int x_is_f32, int64_t rows, int D, const float* gamma,
+                     const float* beta, float eps, int gelu, void* yT, float* yF, hipStream_t s,
+                     const float* add = nullptr, float* sumF = nullptr,
+                     void* yP = nullptr, int pair_kind = 0,    // yP: the result as pair rows (split modes; kind 2 = bf16 / 3 = fp16 pieces)
+                     const void* addP = nullptr);              // addP: a second addend given as pair rows (may alias yP: in place)
+// post-LN residual stream as a bf16 (hi, lo) pair (throughput mode, D in {512, 768, 1024})
+bool layernorm_hilo_ok(int D);
+// the same LayerNorm with the branch given as `nparts` fp32 partial products + bias (a K-split small GEMM: gemm_skinny.hip, ksplit)
+int launch_layernorm_hilo_parts(const float* parts, int nparts, long part_stride, const float* pbias, const bf16_t* rh, const bf16_t* rl, int64_t rows,
+                                int D, const float* gamma, const float* beta, float eps, bf16_t* yh, bf16_t* yl, float* yF, hipStream_t s);
+int launch_layernorm_hilo(const bf16_t* branch, const bf16_t* rh, const bf16_t* rl, const float* x32, int64_t rows, int D,
+                          const float* gamma, const float* beta, float eps, bf16_t* yh, bf16_t* yl, float* yF, hipStream_t s);
+
+// ---- conv layer 0 on the vector ALU, and the fp32 <-> pair-row re-layouts (conv0.hip) ----
 int launch_conv0_group_apply(int prec, const float* wav, int B, int64_t L, int k, int stride, int64_t T1, int C,
                              const float* coef, void* out /*B x T1 x C*/, hipStream_t s, int pair_kind = 0);   // pair_kind 2 / 3: out as pair rows
 // conv layer 0 in "layer" mode: conv + bias + LayerNorm over channels + GELU
@@ -401,6 +413,9 @@ int launch_conv0_layer(int prec, const float* wav, int B, int64_t L, int k, int 
                        const double* wav_moments, int64_t n_wav, float eps_wav, const float* w0, const float* b0,
                        const float* gamma, const float* beta, float eps, void* out, hipStream_t s, int clips_per_norm_group,
                        int pair_kind = 0);
+// fp32 <-> pair rows (GemmArgs::a_pairs); lo_plane != nullptr: `in` / `lo_plane` are separate (hi, lo) planes instead
+int launch_f32_to_pairs(int kind, const float* x, void* out, int64_t n, hipStream_t s);
+int launch_pairs_to_f32(int kind, const void* in, const void* lo_plane, float* y, int64_t n, hipStream_t s);
 
 // conv layer 0 on the matrix pipe (conv0_mfma.hip; 16-bit throughput modes, k = 10, C = 512): table_ws = conv0_mfma_table_bytes(B) bytes
 bool conv0_mfma_ok(int prec, int pair_kind, int k, int stride, int C);   // prec 1 (16-bit rows out) or pair_kind 2 / 3 (split modes: pair rows out)
@@ -412,18 +427,35 @@ int launch_conv0_mfma_layer(const float* wav, int B, int64_t L, int stride, int6
                             void* out, hipStream_t s, int clips_per_norm_group, int pair_kind = 0);
 extern int g_conv0_mfma;
 
+// ---- what the encoder and RCA entry points launch between the products (encoder_ops.hip) ----
+int launch_f32_to_bf16(const float* in, bf16_t* out, int64_t n, hipStream_t s);
+int launch_zero_bytes(void* p, size_t bytes, hipStream_t s);            // kernel nodes instead of memset / memcpy nodes (encoder_ops.hip)
+int launch_copy_f32(const float* in, float* out, int64_t n, hipStream_t s);
+int launch_zero_cols(float* p, int64_t rows, int cols, int64_t ld, hipStream_t s);
 // positional-conv operand: (B,T,D) fp32 -> (B, G, T + kp, D/G) operand type, zero padded by kp/2 in front
 int launch_posconv_gather(int prec, const float* h, int B, int T, int D, int G, int kp, int Tp, void* out, hipStream_t s,
                           const float* sc = nullptr, const float* sh = nullptr);  // sc/sh: per-channel affine on the valid frames
 int launch_posconv_scatter_add(const float* h, const void* y, int B, int T, int D, int G, int P, int Tq, float* pre, hipStream_t s,
                                int y_f32 = 0);   // y in the operand type, or fp32 (split modes)
-
 // attention helpers for the materialised-score path
 int launch_softmax_rows(int prec, const float* S, int64_t rows, int T, int Tp, void* P, hipStream_t s);
 // V slice of the packed qkv (B*T, ld) at column offset voff -> Vt (B, H, dh, Tp) operand type, zero padded
 int launch_transpose_v(int prec, const void* qkv, int B, int T, int H, int dh, long ld, long voff, int Tp,
                        void* Vt, hipStream_t s);
+// out = a*x + b*y (fp32 or operand type)
+int launch_axpby(int prec, const void* x, const void* y, float a, float b, void* out, int64_t n, hipStream_t s);
+// RCA: s = x + pe[t] (x f32 (B,T,D); x2 may be shorter in T: rows >= T2 read as zero) -> fp32 + operand type
+int launch_add_pe(int prec, const float* x, int B, int T, int Tsrc, int D, const float* pe, float* outF, void* outT,
+                  hipStream_t s);
+int launch_add_f32(const float* a, const float* b, float* out, int64_t n, hipStream_t s);
+// WavLM gated relative position bias
+int launch_relpos_table(const float* embed, int H, int T, int num_buckets, int max_distance, float* pb, hipStream_t s);
+int launch_relpos_gate(int prec, const void* u, int64_t rows, int T, int H, int dh, const float* wab, const float* bab,
+                       const float* cst, float* gate, hipStream_t s);
+int launch_scores_add_relbias(float* S, int64_t BH, int H, int T, int Tp, const float* gate, const float* pb, hipStream_t s);
+int launch_clock_stamp(long long* out16, hipStream_t s);
 
+// ---- attention.hip ----
 // fused attention (bf16, head_dim 64/128): Q/K row-major with row strides ldq/ldk and per-clip strides, V^T padded
 // Q/K/V row-major (K and V share row / clip strides); V is transposed on the fly by ds_read_b64_tr_b16
 // gate (B,H,T) / pb (H, 2T-1): WavLM's gated relative position bias, or nullptr
@@ -438,33 +470,36 @@ bool flash_attention_x3_ok(int dh);
 int launch_flash_attention_x3(int kind, const void* Q, long ldq, long q_bstride, long q_plane, const void* K, const void* V, long ldk,
                               long k_bstride, long k_plane, float* O, long ldo, long o_bstride, int B, int T, int H, int dh, float scale,
                               hipStream_t s, int o_pairs = 0);   // o_pairs: O written as pair rows (the output projection's operand)
-// out = a*x + b*y (fp32 or operand type)
-int launch_axpby(int prec, const void* x, const void* y, float a, float b, void* out, int64_t n, hipStream_t s);
-// RCA: s = x + pe[t] (x f32 (B,T,D); x2 may be shorter in T: rows >= T2 read as zero) -> fp32 + operand type
-int launch_add_pe(int prec, const float* x, int B, int T, int Tsrc, int D, const float* pe, float* outF, void* outT,
-                  hipStream_t s);
-int launch_add_f32(const float* a, const float* b, float* out, int64_t n, hipStream_t s);
 
+// ---- the kernels behind api_ops.hip (small_ops.hip): narrow linear layers, losses, Fbank add-ons, decodes ----
 // frame head (fp32 GEMV, N small) and per-frame decode
 int launch_linear_f32(const float* x, int64_t rows, int K, const float* w, const float* b, int N, float* y,
                       hipStream_t s);
 // frame head for K in {512,768,1024}, N <= 32: weight in LDS, four rows per wave (HBM-bound)
-// post-LN residual stream as a bf16 (hi, lo) pair (throughput mode, D in {512, 768, 1024})
-bool layernorm_hilo_ok(int D);
-// the same LayerNorm with the branch given as `nparts` fp32 partial products + bias (a K-split small GEMM: gemm_skinny.hip, ksplit)
-int launch_layernorm_hilo_parts(const float* parts, int nparts, long part_stride, const float* pbias, const bf16_t* rh, const bf16_t* rl, int64_t rows,
-                                int D, const float* gamma, const float* beta, float eps, bf16_t* yh, bf16_t* yl, float* yF, hipStream_t s);
-int launch_layernorm_hilo(const bf16_t* branch, const bf16_t* rh, const bf16_t* rl, const float* x32, int64_t rows, int D,
-                          const float* gamma, const float* beta, float eps, bf16_t* yh, bf16_t* yl, float* yF, hipStream_t s);
-// attention output projection + residual + LayerNorm in one kernel (gemm_ln.hip; hidden size 768, bf16 mode)
+bool linear_head_eligible(int K, int N);
+int launch_linear_head(const float* x, int64_t rows, int K, const float* w, const float* b, int N, float* y, hipStream_t s);
+// validation losses (masked BCE-with-logits / NLL, speechbrain/nnet/losses.py) and the narrow (log-)softmax
+int launch_bce_loss(const float* x, int64_t B, int64_t t_pred, const float* y, int64_t t_tgt, int64_t T, const float* rel_len,
+                    const float* pos_weight, float* per_frame, double* sums, hipStream_t s);
+int launch_nll_loss(const float* logp, int64_t B, int64_t t_pred, int C, const int64_t* tgt, int64_t t_tgt, int64_t T,
+                    const float* rel_len, float* per_frame, double* sums, int* bad_target, hipStream_t s);
+int launch_loss_reduce(const double* sums, int B, int reduction, float smoothing, float* out, hipStream_t s);
+int launch_softmax_small(const float* x, int64_t rows, int n, int apply_log, float* y, hipStream_t s);
 // Fbank add-ons: time derivatives and context window
 int launch_deltas(const float* x, long ldx, int B, int T, int C, int n, float inv_denom, float* out, long ldo, hipStream_t s);
 int launch_context_window(const float* x, int B, int T, int C, int ctx, int lag, int pad, float* out, hipStream_t s);
-// WavLM gated relative position bias
-int launch_relpos_table(const float* embed, int H, int T, int num_buckets, int max_distance, float* pb, hipStream_t s);
-int launch_relpos_gate(int prec, const void* u, int64_t rows, int T, int H, int dh, const float* wab, const float* bab,
-                       const float* cst, float* gate, hipStream_t s);
-int launch_scores_add_relbias(float* S, int64_t BH, int H, int T, int Tp, const float* gate, const float* pb, hipStream_t s);
+// Fbank pieces
+int launch_fbank_frames(const float* wav, int B, int64_t L, int n_fft, int hop, int64_t nframes, const float* window,
+                        float* frames /*B*nframes x n_fft*/, hipStream_t s);
+int launch_power_spectrum(const float* reim /*rows x ld: re at [0,nb), im at [imoff, imoff+nb)*/, int64_t rows, int nb,
+                          int imoff, int ld, float* power /*rows x ldp*/, int ldp, hipStream_t s);
+int launch_fbank_db(float* fb, int B, int64_t per_seq, float top_db, hipStream_t s);
+int launch_decode_frames(const float* logits, int64_t rows, int n_out, int n_oct, int n_cls, FrameOut* out,
+                         hipStream_t s);
+int launch_ctc_greedy(const float* probs, int B, int T, int V, const float* rel_lens, int blank, int32_t* tokens,
+                      int32_t* out_lens, hipStream_t s);
+
+// attention output projection + residual + LayerNorm in one kernel (gemm_ln.hip; hidden size 768, bf16 mode)
 // lip front-end (video.hip)
 int launch_video_pad(int prec, const float* v, int B, int T, int H, int W, int Hp, int Wp, void* out, hipStream_t s);
 // the recipe's uint8 -> float32 pixel map, ((u - sub0) / div0 - mean) / std in float64 (video.hip, svt_video_forward_u8)
@@ -489,13 +524,6 @@ int launch_conv3x3_c64(const void* in, const void* wimg, const float* bias, cons
 bool conv3x3_c128_ok(int prec, int Hs, int Ws);   // stage 2's stride-1 convolutions (128 -> 128 channels), same file
 int launch_conv3x3_c128(const void* in, const void* wimg, const float* bias, const float* slope, const void* resid, void* out, long F,
                         int Hs, int Ws, hipStream_t s);
-// validation losses (masked BCE-with-logits / NLL, speechbrain/nnet/losses.py) and the narrow (log-)softmax
-int launch_bce_loss(const float* x, int64_t B, int64_t t_pred, const float* y, int64_t t_tgt, int64_t T, const float* rel_len,
-                    const float* pos_weight, float* per_frame, double* sums, hipStream_t s);
-int launch_nll_loss(const float* logp, int64_t B, int64_t t_pred, int C, const int64_t* tgt, int64_t t_tgt, int64_t T,
-                    const float* rel_len, float* per_frame, double* sums, int* bad_target, hipStream_t s);
-int launch_loss_reduce(const double* sums, int B, int reduction, float smoothing, float* out, hipStream_t s);
-int launch_softmax_small(const float* x, int64_t rows, int n, int apply_log, float* y, hipStream_t s);
 // head-only training step (train.hip): the recipe's objective + d/dlogits, the head's weight gradient, clip_grad_norm_ + Adadelta
 int launch_amt_objective_grad(const float* x, int64_t B, int64_t t_pred, int n_out, int n_oct_cols, const float* on_t,
                               const float* off_t, const int64_t* oct_t, const int64_t* cls_t, int64_t t_tgt, int64_t T,
@@ -557,28 +585,5 @@ struct RcaWgrad {   // dW (N x C) = sum over the rows of nseg segments of dY_s^T
 size_t rca_wgrad_scratch_bytes(int64_t vrows, int N, int C);
 int launch_rca_wgrad(int prec, const RcaWgrad& w, float* dw, float* db, void* scratch, hipStream_t s);
 int launch_linear_dgrad(const float* dy, const float* w, int64_t rows, int D, int N, float* dx, hipStream_t s);
-bool linear_head_eligible(int K, int N);
-int launch_linear_head(const float* x, int64_t rows, int K, const float* w, const float* b, int N, float* y, hipStream_t s);
-struct FrameOut { float p_on, p_off; int32_t octave, pitch_class; };
-// fused tail: whole-batch output norm (moments taken in the same pass) + frame head + optional per-frame decode, from the
-// UN-normalised encoder output x (rows x K); dots = rows x N scratch; mom = 2 doubles per norm group (written, reproducible bit for
-// bit) or null; scratch (needed with mom) = head_scratch_bytes(rows, groups) bytes whose first 4 are ZERO
-int launch_head_fused(const float* x, int64_t rows, int K, const float* w, const float* wsum, const float* b, int N, float* dots,
-                      double* mom, int64_t rows_per_group, float eps, float* logits, FrameOut* frames, int n_oct, int n_cls,
-                      hipStream_t s,
-                      double n_stat = 0, int (*between)(void*) = nullptr, void* between_arg = nullptr, void* scratch = nullptr);
-size_t head_scratch_bytes(int64_t rows, int groups_max);
-int launch_decode_frames(const float* logits, int64_t rows, int n_out, int n_oct, int n_cls, FrameOut* out,
-                         hipStream_t s);
-int launch_ctc_greedy(const float* probs, int B, int T, int V, const float* rel_lens, int blank, int32_t* tokens,
-                      int32_t* out_lens, hipStream_t s);
-
-int launch_clock_stamp(long long* out16, hipStream_t s);
-// Fbank pieces
-int launch_fbank_frames(const float* wav, int B, int64_t L, int n_fft, int hop, int64_t nframes, const float* window,
-                        float* frames /*B*nframes x n_fft*/, hipStream_t s);
-int launch_power_spectrum(const float* reim /*rows x ld: re at [0,nb), im at [imoff, imoff+nb)*/, int64_t rows, int nb,
-                          int imoff, int ld, float* power /*rows x ldp*/, int ldp, hipStream_t s);
-int launch_fbank_db(float* fb, int B, int64_t per_seq, float top_db, hipStream_t s);
 
 }  // namespace svt

@@ -1,6 +1,6 @@
 // Conv layer 0 of the feature extractor (Cin = 1, 10 taps, stride 5, 512 channels) on the MATRIX pipe, for the 16-bit throughput modes.
 //
-// The vector-ALU kernels (kernels.hip: conv0_group_apply_kernel / conv0_layer_kernel) spend ~10 packed FMAs per output on the taps in
+// The vector-ALU kernels (conv0.hip: conv0_group_apply_kernel / conv0_layer_kernel) spend ~10 packed FMAs per output on the taps in
 // front of the normalisation and the GELU and are bound by vector issue (C2: 256 us for a 1.05 GB write, C3: 1.01 ms for 2.1 GB, 40
 // vector operations per output in the layer-norm form).  Here the taps are ONE v_mfma_f32_16x16x32 per 16 frames x 16 channels:
 //     K = 32 = [ x_hi(10) | x_lo(10) | x_hi(10) | 1 | 1 ]  against  [ w_hi(10) | w_hi(10) | w_lo(10) | b_hi | b_lo ]

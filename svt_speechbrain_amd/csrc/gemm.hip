@@ -33,8 +33,6 @@ template <> struct OpTraits<bf16_t> {
   static constexpr int BK = 64;
 };
 
-__device__ __forceinline__ float gelu_erf(float x) { return gelu_fast(x); }
-
 // ---- split-operand engine (precision "bf16x3" / "fp16x3") -------------------------------------------------------
 // Operands stay fp32 in HBM (the fp32 parity pipeline is unchanged); on its way into LDS every fp32 value x is cut
 // into two 16-bit pieces hi = round16(x), lo = round16(x - hi) and the product is accumulated in fp32 as

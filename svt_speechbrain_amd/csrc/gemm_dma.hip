@@ -26,7 +26,6 @@
 namespace svt {
 namespace {
 
-__device__ __forceinline__ float gelu_erf(float x) { return gelu_fast(x); }
 __device__ __forceinline__ float apply_act(float v, int act) {
   if (act == ACT_GELU) return gelu_erf(v);
   if (act == ACT_RELU) return v > 0.f ? v : 0.f;

@@ -375,7 +375,7 @@ def test_full_size_properties(cfg_name, B, L):
     b = enc32(wav)
     assert a.shape == (B, cfg.frames(L), cfg.hidden_size)
     assert torch.isfinite(a).all()
-    # the three cross-workgroup statistics are summed in a fixed order since round 5 (kernels.hip, last_workgroup): bit for bit
+    # the three cross-workgroup statistics are summed in a fixed order since round 5 (stats.hip, last_workgroup): bit for bit
     assert torch.equal(a, b)
     assert abs(a.mean().item()) < 1e-4 and abs(a.var(unbiased=False).item() - 1.0) < 1e-3
     perm = torch.arange(B - 1, -1, -1, device=DEV)
@@ -842,7 +842,7 @@ def test_audio_visual_compute_forward_with_the_recipe_module_names(golden):
 def test_small_batch_ffn2_k_split_against_the_unsplit_product(precision, B, L):
     """Round 6: for a few utterances (<= 2048 frames) FFN-2 runs as a K-split launch of the one-utterance GEMM -- four workgroups per
     tile, raw fp32 partial tiles -- and the LayerNorm behind it adds the parts and the bias and rounds the sum to the operand type
-    (csrc/gemm_skinny.hip ksplit, kernels.hip layernorm_hilo2_kernel<D, true>; svt_debug_set key 36 = 0: the un-split product).  Same
+    (csrc/gemm_skinny.hip ksplit, layernorm.hip layernorm_hilo2_kernel<D, true>; svt_debug_set key 36 = 0: the un-split product).  Same
     products, same rounding points, another fp32 summation order: the two forms agree to a few operand ulps of the branch output,
     each is reproducible bit for bit, and the goldens hold both (test_bf16_mode_error_bound runs the default)."""
     cfg = PRESETS["wav2vec2-base"]

@@ -1,5 +1,5 @@
 """The three cross-workgroup statistics of a forward (waveform moments, conv-0 window moments, output-norm moments) are summed in a fixed
-order by the launch's LAST workgroup (csrc/kernels.hip, last_workgroup): per-workgroup partials as write-through stores, a ticket atomic,
+order by the launch's LAST workgroup (csrc/stats.hip, last_workgroup): per-workgroup partials as write-through stores, a ticket atomic,
 cache-bypassing loads -- relaxed atomics, no fence (a fence is an L2 write-back on gfx950: +30-50 us per kernel).  ADVICE r05 asked for
 more than run-to-run bit equality: the sums are compared here with HOST fp64 sums of the same inputs, in both arms of the ticket
 (svt_debug_set key 32: 0 relaxed, 1 acquire-release), over many forwards with other work on the GPU between them -- a stale partial

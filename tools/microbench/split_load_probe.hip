@@ -1,5 +1,5 @@
 // Does `s_waitcnt vmcnt(N)` cover a 16-byte row that was fetched as an OVERLAPPING pair of loads -- global_load_dwordx3 at byte 4 +
-// global_load_dwordx2 at byte 0 -- the way hipcc split the first load of head_dots_kernel in round 4?  (kernels.hip; profiles/
+// global_load_dwordx2 at byte 0 -- the way hipcc split the first load of head_dots_kernel in round 4?  (stats.hip; profiles/
 // r05_determinism_under_gpu_sharing.txt: under memory contention the values read right behind the counted wait were stale in ~0.15 % of
 // the forwards.)  Every lane issues the pair (mode 0) or ONE global_load_dwordx4 (mode 1) for a random 16-byte row, then 14 more 16-byte
 // loads of other random rows, waits with the count that leaves exactly those 14 in flight, copies the registers at once, then waits for
