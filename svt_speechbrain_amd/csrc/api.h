@@ -33,7 +33,7 @@ struct DevBuf {
 int upload_f32(DevBuf& b, const float* h, size_t n);
 int upload_operand(int prec, DevBuf& b, const float* h, size_t n);
 // weight matrix (rows x K, K contiguous): storage copy as upload_operand + in the split-operand modes the packed (hi, lo)
-// pieces the LDS-DMA split kernel reads (gemm_dma.hip); `precision` is the svt_precision of the object
+// pieces the LDS-DMA split kernels read (split_weights.hip); `precision` is the svt_precision of the object
 int upload_weight(int precision, DevBuf& b, const float* h, size_t rows, size_t K);
 // first step of every svt_*_finalize: waits for the forwards still in flight before a RE-upload changes live buffers
 int begin_upload(bool& uploaded);

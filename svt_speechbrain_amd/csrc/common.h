@@ -256,7 +256,7 @@ int launch_gemm_skinny(const GemmArgs& a, hipStream_t s);
 
 // Kernel files: a contract predicate and one launcher each, which launches exactly the configuration it is given (tile height bm, tile
 // width, diagnostic form)
-// large-tile LDS-DMA pipeline (gemm_dma.hip; bf16, K % 64 == 0): pp8 / pers below
+// large-tile LDS-DMA pipeline (gemm_pp8.hip; bf16, K % 64 == 0): pp8 / pers below
 bool gemm_dma_eligible(const GemmArgs& a);
 // persistent + staggered form of the LDS-DMA pipeline (gemm_pps.hip): bf16 output, no residual, activation none / GELU
 bool gemm_pps_eligible(const GemmArgs& a);
@@ -265,7 +265,7 @@ int launch_gemm_pps(const GemmArgs& a, int bm, hipStream_t s);
 int launch_gemm_p1w(const GemmArgs& a, int bm, hipStream_t s);
 // small problems (a single utterance): K split four ways inside the workgroup, operands straight from L2
 bool gemm_skinny_eligible(const GemmArgs& a);
-// split-operand modes: weight matrices cut once into packed 16-bit (hi, lo) pieces for the LDS-DMA split kernels (gemm_dma.hip).
+// split-operand modes: weight matrices cut once into packed 16-bit (hi, lo) pieces for the LDS-DMA split kernels (split_weights.hip).
 // kind = svt_precision (2 = bf16 pieces, 3 = fp16 pieces); other kinds are ignored.
 int split_weights_register(const void* w_f32_dev, long n_rows, int K, int kind, hipStream_t s);
 void split_weights_forget(const void* w_f32_dev);
@@ -280,13 +280,13 @@ int launch_gemm_p1x(int kind, const GemmArgs& a, const void* packed, int bm, hip
 #pragma GCC visibility push(hidden)
 // register-staged kernel (gemm.hip): prec as for launch_gemm; bn = 64 (256 x 64 tiles) or 128 (128 x 128)
 int launch_gemm_staged(int prec, const GemmArgs& a, int bn, hipStream_t s);
-// gemm_dma.hip: one tile per workgroup (with a.gen, bn = 128 gives the 256 x 128 tile), and one workgroup per CU walking a tile list
+// gemm_pp8.hip: one tile per workgroup (with a.gen, bn = 128 gives the 256 x 128 tile); gemm_pers.hip: one workgroup per CU walking a tile list
 int launch_gemm_pp8(const GemmArgs& a, int bm, int bn, hipStream_t s);
 int launch_gemm_pers(const GemmArgs& a, int bm, hipStream_t s);
 int launch_gemm_skinny_tile(const GemmArgs& a, int tile, hipStream_t s);   // gemm_skinny.hip: tile = 64 (64 x 64) or 32 (32 x 32)
 // the packed image of the rows [W, W + rows_needed) of a registered matrix of this kind and K (W may point into it), or null
 const void* split_weights_find(const void* W, int kind, int K, long rows_needed);
-// the one-tile split kernel with A fp32 in memory (gemm_dma.hip gemm_x3s_kernel): nbs = 4 / 3 for 256- / 192-column tiles; form: 0, or in
+// the one-tile split kernel with A fp32 in memory (gemm_x3s.hip): nbs = 4 / 3 for 256- / 192-column tiles; form: 0, or in
 // DIAG builds the timing ablations 1 / 3 and the slot stamps 11-14
 int launch_gemm_x3s(int kind, const GemmArgs& a, const void* packed, int nbs, int form, hipStream_t s);
 // the split kernels address a tile's 256 rows (possibly across clip boundaries) by 32-bit offsets from its first row, and the packed
@@ -499,7 +499,6 @@ int launch_decode_frames(const float* logits, int64_t rows, int n_out, int n_oct
 int launch_ctc_greedy(const float* probs, int B, int T, int V, const float* rel_lens, int blank, int32_t* tokens,
                       int32_t* out_lens, hipStream_t s);
 
-// attention output projection + residual + LayerNorm in one kernel (gemm_ln.hip; hidden size 768, bf16 mode)
 // lip front-end (video.hip)
 int launch_video_pad(int prec, const float* v, int B, int T, int H, int W, int Hp, int Wp, void* out, hipStream_t s);
 // the recipe's uint8 -> float32 pixel map, ((u - sub0) / div0 - mean) / std in float64 (video.hip, svt_video_forward_u8)

@@ -17,7 +17,7 @@
 //     and 16-byte stores, no LDS round trip.
 //   * fp32 operands use v_mfma_f32_16x16x4_f32 (bit-exact fp32 fma chain) with the same staging and
 //     fragment layout: a fragment is 8 k-consecutive elements per lane for both types.
-#include "common.h"
+#include "gemm_ring.h"   // apply_act, xcd_tile
 #include <type_traits>
 
 namespace svt {
@@ -71,12 +71,6 @@ template <int SPLIT> __device__ __forceinline__ f32x4 mfma16(const uint4& a, con
     return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(real_bf16x8, a), __builtin_bit_cast(real_bf16x8, b), c, 0, 0, 0);
 }
 
-__device__ __forceinline__ float apply_act(float v, int act) {
-  if (act == ACT_GELU) return gelu_erf(v);
-  if (act == ACT_RELU) return v > 0.f ? v : 0.f;
-  return v;
-}
-
 // SPLIT (T = float only): 0 = exact fp32 MFMA, 1 = bf16x3, 2 = fp16x3 split-operand products (see above)
 // NSET = register sets of the global -> LDS staging, i.e. K slabs in flight per workgroup (the exact-fp32 and bf16 forms
 // multiply a slab for longer than a load takes: one set; the split form's 48 MFMAs per slab last ~0.35 us: two).
@@ -110,9 +104,7 @@ __global__ __launch_bounds__(256, MINW) void gemm_kernel(GemmArgs p) {
   const int tiles_m = (p.M + BM - 1) / BM;
   int tile_m, tile_n;
   {
-    const int nblk = gridDim.x, bid = blockIdx.x;
-    const int xcd = bid & 7, q = nblk >> 3, r = nblk & 7;
-    const int l = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
+    const int nblk = gridDim.x, l = xcd_tile(blockIdx.x, nblk);
     const int tiles_n = nblk / tiles_m;
     const int per_band = p.raster_gm * tiles_n;
     const int band = l / per_band, rem = l - band * per_band;

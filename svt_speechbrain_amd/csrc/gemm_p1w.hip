@@ -21,7 +21,7 @@
 //     wait of the next barrier can leave the stores in flight.
 // Contract = gemm_pps_eligible (bf16 output, no residual, alpha = 1, none / GELU, K % 64 == 0, N % 256 == 0, spans < 4 GiB) and K >= 192
 // (three slabs per tile: a tile boundary then never asks for rows of the tile after next, whose offsets exist only behind the epilogue).
-#include "common.h"
+#include "gemm_ring.h"
 
 namespace svt {
 namespace {
@@ -31,14 +31,6 @@ namespace {
 #ifndef SVT_P1W_STORE_AUX
 #define SVT_P1W_STORE_AUX 16
 #endif
-template <int N> __device__ __forceinline__ void p1_wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-
-__device__ __forceinline__ void p1_dma(unsigned voff, const void* sbase, unsigned lds_addr) {
-  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" ::"s"(lds_addr), "v"(voff), "s"(sbase) : "memory");
-}
-
-typedef unsigned p1_u32x4 __attribute__((ext_vector_type(4)));
-
 template <int BM, int ACT, bool TR = false>   // TR: the diagnostic instantiation (stamps; may spill a register or two: timing only)
 __global__ __launch_bounds__(256) void gemm_p1w_kernel(GemmArgs p, int tiles_n, int ntiles) {
   constexpr int BN = 256, BK = 64, NSLOT = 5;
@@ -54,9 +46,7 @@ __global__ __launch_bounds__(256) void gemm_p1w_kernel(GemmArgs p, int tiles_n, 
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave & 1, wn = wave >> 1;
   const int nblk = gridDim.x, b = blockIdx.x;
-  // blocks b and b + 8 share an XCD: in every round an XCD works on nblk / 8 consecutive logical tiles (n fastest)
-  const int per = nblk >> 3;
-  const int lbase = (b & 7) * per + (b >> 3);
+  const int lbase = xcd_first_tile(b, nblk);
   if (lbase >= ntiles) return;
   const int my_tiles = (ntiles - lbase + nblk - 1) / nblk;
   const int tiles_m = ntiles / tiles_n;
@@ -90,7 +80,8 @@ __global__ __launch_bounds__(256) void gemm_p1w_kernel(GemmArgs p, int tiles_n, 
     }
   };
   auto w_piece = [&](int i) -> long { return (long)(2 * (i & 3) + 128 * (i >> 2)) * w_col; };
-  const unsigned lds0 = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(void __attribute__((address_space(3)))*)lds);
+  const unsigned lds0 = lds_base(lds);
+  // kept local: a shared function (gemm_ring.h: lds_unit) in place of this lambda changes the schedule hipcc gives this kernel
   auto lds_unit = [&](int slot, int i) -> unsigned { return lds0 + (unsigned)(slot * SLOT + (wave + 4 * i) * 64) * 16u; };
 
   f32x4 acc[8][MB];
@@ -126,14 +117,14 @@ __global__ __launch_bounds__(256) void gemm_p1w_kernel(GemmArgs p, int tiles_n, 
   }
   // head of the stream: A_0 -> slot 0, W_0 -> slot 1, A_1 -> slot 2, W_1 -> slot 3 (nk >= 2: slab 1 belongs to the first tile)
 #pragma unroll
-  for (int i = 0; i < GA; ++i) p1_dma(aofE[i], gA, lds_unit(0, i));
+  for (int i = 0; i < GA; ++i) dma_sv(aofE[i], gA, lds_unit(0, i));
 #pragma unroll
-  for (int i = 0; i < GW; ++i) p1_dma(wofE, gW + w_piece(i), lds_unit(1, i));
+  for (int i = 0; i < GW; ++i) dma_sv(wofE, gW + w_piece(i), lds_unit(1, i));
 #pragma unroll
-  for (int i = 0; i < GA; ++i) p1_dma(aofE[i], gA + aoff(1), lds_unit(2, i));
+  for (int i = 0; i < GA; ++i) dma_sv(aofE[i], gA + aoff(1), lds_unit(2, i));
 #pragma unroll
-  for (int i = 0; i < GW; ++i) p1_dma(wofE, gW + BK * 2 + w_piece(i), lds_unit(3, i));
-  p1_wait_vm<GA + GW>();   // A_0 and W_0 (and the bias loads, older still) have landed
+  for (int i = 0; i < GW; ++i) dma_sv(wofE, gW + BK * 2 + w_piece(i), lds_unit(3, i));
+  wait_vm<GA + GW>();   // A_0 and W_0 (and the bias loads, older still) have landed
   asm volatile("" : "+v"(bq[0]), "+v"(bq[1]));
   __builtin_amdgcn_s_barrier();
   if (tr) { t_first = wall_clock64(); c_first = __builtin_amdgcn_s_memtime(); }
@@ -192,8 +183,8 @@ __global__ __launch_bounds__(256) void gemm_p1w_kernel(GemmArgs p, int tiles_n, 
       }
       if (i & 1) read_w(rs, rks, nb);                 // block nb is done for this k-step: its registers take the next k-step's
       if (i < MB) read_x(rs, rks, BUF ^ 1, i);
-      if (REQ == 1 && (i & 1) && (i >> 1) < GA) p1_dma(ev_a ? aofE[i >> 1] : aofO[i >> 1], srcA, lds_unit(slotA, i >> 1));
-      if (REQ == 2 && (i & 1) && (i >> 1) < GW) p1_dma(ev_w ? wofE : wofO, srcW + w_piece(i >> 1), lds_unit(slotW, i >> 1));
+      if (REQ == 1 && (i & 1) && (i >> 1) < GA) dma_sv(ev_a ? aofE[i >> 1] : aofO[i >> 1], srcA, lds_unit(slotA, i >> 1));
+      if (REQ == 2 && (i & 1) && (i >> 1) < GW) dma_sv(ev_w ? wofE : wofO, srcW + w_piece(i >> 1), lds_unit(slotW, i >> 1));
       __builtin_amdgcn_sched_barrier(0);
     }
   };
@@ -243,8 +234,8 @@ __global__ __launch_bounds__(256) void gemm_p1w_kernel(GemmArgs p, int tiles_n, 
 #pragma unroll
       for (int q = 0; q < NREQ; ++q) {
         const int rq = mb * NREQ + q;                  // requests 0 .. GW - 1: W pieces; GW .. GW + GA - 1: A pieces
-        if (rq < GW) p1_dma(ev ? wofE : wofO, srcW + w_piece(rq), lds_unit(slotW, rq));
-        else if (rq < GW + GA) p1_dma(ev ? aofE[rq - GW] : aofO[rq - GW], srcA, lds_unit(slotA, rq - GW));
+        if (rq < GW) dma_sv(ev ? wofE : wofO, srcW + w_piece(rq), lds_unit(slotW, rq));
+        else if (rq < GW + GA) dma_sv(ev ? aofE[rq - GW] : aofO[rq - GW], srcA, lds_unit(slotA, rq - GW));
       }
       __builtin_amdgcn_sched_barrier(0);
       if (!no_epi) {
@@ -271,7 +262,7 @@ __global__ __launch_bounds__(256) void gemm_p1w_kernel(GemmArgs p, int tiles_n, 
             for (int j = 0; j < 8; ++j) o[j] = (bf16_t)(FIN_VGPR ? fin[j][r] : acc[j][mb][r]);
           }
           // the row goes into the VECTOR offset (range check of a raw buffer; see gemm_pps_kernel for the soffset hazard)
-          __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(p1_u32x4, o), crsrc, off0 + (mb * 16 + r) * row_pitch, 0, SVT_P1W_STORE_AUX);
+          __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4v, o), crsrc, off0 + (mb * 16 + r) * row_pitch, 0, SVT_P1W_STORE_AUX);
           if constexpr (ACT == ACT_GELU) __builtin_amdgcn_sched_barrier(0);   // one row's polynomial at a time (register pressure)
         }
       } else {
@@ -289,7 +280,7 @@ __global__ __launch_bounds__(256) void gemm_p1w_kernel(GemmArgs p, int tiles_n, 
   auto mid_barrier = [&](auto out_c) {
     long long c0_ = 0;
     if (tr) c0_ = __builtin_amdgcn_s_memtime();
-    p1_wait_vm<decltype(out_c)::value>();
+    wait_vm<decltype(out_c)::value>();
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_sched_barrier(0);
     __builtin_amdgcn_s_barrier();
@@ -359,7 +350,7 @@ __global__ __launch_bounds__(256) void gemm_p1w_kernel(GemmArgs p, int tiles_n, 
   if (tr) t_loop = wall_clock64();
   // Everything this wave still has in flight -- the last tile's stores AND the stream's surplus LDS-DMA requests (they are INTERLEAVED with
   // those stores in the last k-step's row blocks LAST_W_BLOCK + 1 .. MB - 1, not older than them: ADVICE r05) -- retires before the wave ends
-  p1_wait_vm<0>();
+  wait_vm<0>();
   if (tr && lane == 0) {   // record layout of gemm_pps_kernel (tools/gemm_trace.py); waves 0 / 2 stand for its two wave groups
     if ((wave & 1) == 0) {
       long long* o = p.trace + ((long)blockIdx.x * 2 + (wave >> 1)) * 8;

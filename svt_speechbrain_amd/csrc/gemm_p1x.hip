@@ -18,7 +18,7 @@
 // pair rows / (hi, lo) planes; bias inside; exact-erf GELU) runs between two tiles, out of the accumulators, one row block at a time behind
 // an AGPR anchor; the next tile's A requests are issued in front of its stores so that the next barrier's counted wait leaves them in flight.
 // Contract = gemm_x3q_eligible and K >= 96 (three slabs per tile: a tile boundary never asks for rows of the tile after next).
-#include "common.h"
+#include "gemm_ring.h"
 
 // An A/B arm, not a dispatched kernel: built by `make DIAG=1` only (the shipped library holds what it dispatches: VERDICT r05 #11)
 #if defined(SVT_OPERAND_F16) || !defined(SVT_DIAG)
@@ -29,34 +29,6 @@ int launch_gemm_p1x(int, const GemmArgs&, const void*, int, hipStream_t) { set_e
 
 namespace svt {
 namespace {
-
-template <int N> __device__ __forceinline__ void px_wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-__device__ __forceinline__ void px_dma(unsigned voff, const void* sbase, unsigned lds_addr) {
-  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" ::"s"(lds_addr), "v"(voff), "s"(sbase) : "memory");
-}
-typedef unsigned px_u32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 px_f16x8 __attribute__((ext_vector_type(8)));
-
-template <bool F16> __device__ __forceinline__ f32x4 px_mma(const px_u32x4& a, const px_u32x4& b, const f32x4& c) {
-  if constexpr (F16) return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(px_f16x8, a), __builtin_bit_cast(px_f16x8, b), c, 0, 0, 0);
-  else return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(real_bf16x8, a), __builtin_bit_cast(real_bf16x8, b), c, 0, 0, 0);
-}
-// eight fp32 values -> packed (hi, lo) 16-bit pieces (gemm_x3q.hip)
-template <bool F16> __device__ __forceinline__ void px_cut8(const float (&v)[8], px_u32x4& hi, px_u32x4& lo) {
-  if constexpr (F16) {
-    px_f16x8 h, l;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) { h[j] = (_Float16)v[j]; l[j] = (_Float16)(v[j] - (float)h[j]); }
-    hi = __builtin_bit_cast(px_u32x4, h);
-    lo = __builtin_bit_cast(px_u32x4, l);
-  } else {
-    real_bf16x8 h, l;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) { h[j] = (__bf16)v[j]; l[j] = (__bf16)(v[j] - (float)h[j]); }
-    hi = __builtin_bit_cast(px_u32x4, h);
-    lo = __builtin_bit_cast(px_u32x4, l);
-  }
-}
 
 template <bool F16, int BM, int OUT>   // OUT: 0 = fp32 rows, 1 = pair rows, 2 = separate (hi, lo) planes
 __global__ __launch_bounds__(256) void gemm_p1x_kernel(GemmArgs p, const void* wsplit, int tiles_n, int ntiles) {
@@ -69,19 +41,19 @@ __global__ __launch_bounds__(256) void gemm_p1x_kernel(GemmArgs p, const void* w
   constexpr int MPG = MB / 2;        // MFMAs per group: a phase is 16 groups of (one W block) x (half of the A blocks)
   static_assert(MB == 8 || MB == 6 || MB == 4, "BM in {256, 192, 128}");
   extern __shared__ __attribute__((aligned(16))) uint4 lds[];
-  const px_u32x4* ldsv = (const px_u32x4*)lds;
+  const u32x4v* ldsv = (const u32x4v*)lds;
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave & 1, wn = wave >> 1;
   const int nblk = gridDim.x, b = blockIdx.x;
-  const int per = nblk >> 3;
-  const int lbase = (b & 7) * per + (b >> 3);      // blocks b and b + 8 share an XCD and take consecutive tiles (n fastest)
+  const int lbase = xcd_first_tile(b, nblk);
   if (lbase >= ntiles) return;
   const int my_tiles = (ntiles - lbase + nblk - 1) / nblk;
 
   const char* gW = (const char*)wsplit;            // [N][K / 32][hi 32 | lo 32]: a row of the packed matrix is 4 K bytes
   const int r8 = lane >> 3, ch = (lane & 7) ^ r8;
+  // kept local: the shared a_row_off (gemm_ring.h) in place of this lambda changes the schedule hipcc gives this kernel
   auto a_row_off = [&](int m) -> long { return ((long)(m / p.a_rpb) * p.a_bstride + (long)(m % p.a_rpb) * p.a_rstride) * 4; };
   // per tile parity: the 64-bit address of the tile's first A row (an fp32-sized conv activation exceeds 4 GiB), 32-bit offsets of this
   // lane's rows from it; ONE 32-bit offset of its W rows from the packed matrix (piece i sits a scalar distance behind piece 0)
@@ -105,7 +77,8 @@ __global__ __launch_bounds__(256) void gemm_p1x_kernel(GemmArgs p, const void* w
     wo = (unsigned)((long)n * w_col + ch * 16);
   };
   auto w_piece = [&](int i) -> long { return (long)(2 * (i & 3) + 128 * (i >> 2)) * w_col; };
-  const unsigned lds0 = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(void __attribute__((address_space(3)))*)lds);
+  const unsigned lds0 = lds_base(lds);
+  // kept local: a shared function (gemm_ring.h: lds_unit) in place of this lambda changes the schedule hipcc gives this kernel
   auto lds_unit = [&](int slot, int i) -> unsigned { return lds0 + (unsigned)(slot * SLOT + (wave + 4 * i) * 64) * 16u; };
 
   f32x4 acc[8][MB];
@@ -130,18 +103,18 @@ __global__ __launch_bounds__(256) void gemm_p1x_kernel(GemmArgs p, const void* w
   }
   // head of the stream: A_0 -> slot 0, W_0 -> slot 1, A_1 -> slot 2, W_1 -> slot 3
 #pragma unroll
-  for (int i = 0; i < GA; ++i) px_dma(aofE[i], abE, lds_unit(0, i));
+  for (int i = 0; i < GA; ++i) dma_sv(aofE[i], abE, lds_unit(0, i));
 #pragma unroll
-  for (int i = 0; i < GW; ++i) px_dma(wofE, gW + w_piece(i), lds_unit(1, i));
+  for (int i = 0; i < GW; ++i) dma_sv(wofE, gW + w_piece(i), lds_unit(1, i));
 #pragma unroll
-  for (int i = 0; i < GA; ++i) px_dma(aofE[i], abE + ROWB, lds_unit(2, i));
+  for (int i = 0; i < GA; ++i) dma_sv(aofE[i], abE + ROWB, lds_unit(2, i));
 #pragma unroll
-  for (int i = 0; i < GW; ++i) px_dma(wofE, gW + ROWB + w_piece(i), lds_unit(3, i));
-  px_wait_vm<GA + GW>();   // A_0 and W_0 (and the bias loads, older still) have landed
+  for (int i = 0; i < GW; ++i) dma_sv(wofE, gW + ROWB + w_piece(i), lds_unit(3, i));
+  wait_vm<GA + GW>();   // A_0 and W_0 (and the bias loads, older still) have landed
   asm volatile("" : "+v"(bq[0]), "+v"(bq[1]));
   __builtin_amdgcn_s_barrier();
 
-  px_u32x4 xh[MB], xl[MB], wh[8], wl[8];
+  u32x4v xh[MB], xl[MB], wh[8], wl[8];
   int sa = 0, ti = 0;   // ring slot of A_g (W_g sits in the next one); tile index
   auto slot_add = [](int s_, int d) { const int t = s_ + d; return t >= NSLOT ? t - NSLOT : t; };
 
@@ -166,26 +139,26 @@ __global__ __launch_bounds__(256) void gemm_p1x_kernel(GemmArgs p, const void* w
           const float bv = bq[nb >> 2][nb & 3];
           const f32x4 b4 = {bv, bv, bv, bv};
 #pragma unroll
-          for (int j = 0; j < MPG; ++j) acc[nb][mb0 + j] = px_mma<F16>(xl[mb0 + j], wh[nb], b4);
+          for (int j = 0; j < MPG; ++j) acc[nb][mb0 + j] = mma3<F16>(xl[mb0 + j], wh[nb], b4);
         } else {
 #pragma unroll
-          for (int j = 0; j < MPG; ++j) acc[nb][mb0 + j] = px_mma<F16>(xl[mb0 + j], wh[nb], acc[nb][mb0 + j]);
+          for (int j = 0; j < MPG; ++j) acc[nb][mb0 + j] = mma3<F16>(xl[mb0 + j], wh[nb], acc[nb][mb0 + j]);
         }
         if (i < MB) xh[i] = ldsv[rs * SLOT + xoff + i * 128 + fragH];
       } else if constexpr (PH == 1) {
 #pragma unroll
-        for (int j = 0; j < MPG; ++j) acc[nb][mb0 + j] = px_mma<F16>(xh[mb0 + j], wh[nb], acc[nb][mb0 + j]);
+        for (int j = 0; j < MPG; ++j) acc[nb][mb0 + j] = mma3<F16>(xh[mb0 + j], wh[nb], acc[nb][mb0 + j]);
         if (i & 1) wl[nb] = ldsv[rw * SLOT + woff + nb * 128 + fragL];
       } else {
 #pragma unroll
-        for (int j = 0; j < MPG; ++j) acc[nb][mb0 + j] = px_mma<F16>(xh[mb0 + j], wl[nb], acc[nb][mb0 + j]);
+        for (int j = 0; j < MPG; ++j) acc[nb][mb0 + j] = mma3<F16>(xh[mb0 + j], wl[nb], acc[nb][mb0 + j]);
         if (i < MB) xl[i] = ldsv[rs * SLOT + xoff + i * 128 + fragL];
         if (i & 1) wh[nb] = ldsv[rw * SLOT + woff + nb * 128 + fragH];
       }
-      if (REQ == 1 && (i & 1) && (i >> 1) < GA) px_dma(ev_a ? aofE[i >> 1] : aofO[i >> 1], srcA, lds_unit(slotA, i >> 1));
-      if (REQ == 2 && (i & 1) && (i >> 1) < GW) px_dma(ev_w ? wofE : wofO, srcW + w_piece(i >> 1), lds_unit(slotW, i >> 1));
-      if (REQ == 3 && i < 8 && i < GW) px_dma(ev_w ? wofE : wofO, srcW + w_piece(i), lds_unit(slotW, i));
-      if (REQ == 3 && i >= 8 && i - 8 < GA) px_dma(ev_a ? aofE[i - 8] : aofO[i - 8], srcA, lds_unit(slotA, i - 8));
+      if (REQ == 1 && (i & 1) && (i >> 1) < GA) dma_sv(ev_a ? aofE[i >> 1] : aofO[i >> 1], srcA, lds_unit(slotA, i >> 1));
+      if (REQ == 2 && (i & 1) && (i >> 1) < GW) dma_sv(ev_w ? wofE : wofO, srcW + w_piece(i >> 1), lds_unit(slotW, i >> 1));
+      if (REQ == 3 && i < 8 && i < GW) dma_sv(ev_w ? wofE : wofO, srcW + w_piece(i), lds_unit(slotW, i));
+      if (REQ == 3 && i >= 8 && i - 8 < GA) dma_sv(ev_a ? aofE[i - 8] : aofO[i - 8], srcA, lds_unit(slotA, i - 8));
       __builtin_amdgcn_sched_barrier(0);
     }
   };
@@ -195,7 +168,7 @@ __global__ __launch_bounds__(256) void gemm_p1x_kernel(GemmArgs p, const void* w
   using c3 = std::integral_constant<int, 3>;
   // barrier B_g with its counted wait (OUT_ = requests / stores that may stay in flight)
   auto mid_barrier = [&](auto out_c) {
-    px_wait_vm<decltype(out_c)::value>();
+    wait_vm<decltype(out_c)::value>();
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_sched_barrier(0);
     __builtin_amdgcn_s_barrier();
@@ -247,13 +220,13 @@ __global__ __launch_bounds__(256) void gemm_p1x_kernel(GemmArgs p, const void* w
         // row and column in the VECTOR offset: range check + the soffset store-data hazard (gemm_pps.hip)
         const unsigned off = off0 + (mb * 16 + r) * row_pitch;
         if constexpr (OUT == 0) {
-          const px_u32x4 v0 = {__builtin_bit_cast(unsigned, v[0]), __builtin_bit_cast(unsigned, v[1]), __builtin_bit_cast(unsigned, v[2]), __builtin_bit_cast(unsigned, v[3])};
-          const px_u32x4 v1 = {__builtin_bit_cast(unsigned, v[4]), __builtin_bit_cast(unsigned, v[5]), __builtin_bit_cast(unsigned, v[6]), __builtin_bit_cast(unsigned, v[7])};
+          const u32x4v v0 = {__builtin_bit_cast(unsigned, v[0]), __builtin_bit_cast(unsigned, v[1]), __builtin_bit_cast(unsigned, v[2]), __builtin_bit_cast(unsigned, v[3])};
+          const u32x4v v1 = {__builtin_bit_cast(unsigned, v[4]), __builtin_bit_cast(unsigned, v[5]), __builtin_bit_cast(unsigned, v[6]), __builtin_bit_cast(unsigned, v[7])};
           __builtin_amdgcn_raw_buffer_store_b128(v0, crsrc, off, 0, 16);
           __builtin_amdgcn_raw_buffer_store_b128(v1, crsrc, off + 16, 0, 16);
         } else {
-          px_u32x4 hi, lo;
-          px_cut8<F16>(v, hi, lo);
+          u32x4v hi, lo;
+          cut8<F16>(v, hi, lo);
           __builtin_amdgcn_raw_buffer_store_b128(hi, crsrc, off, 0, 16);
           __builtin_amdgcn_raw_buffer_store_b128(lo, lrsrc, OUT == 1 ? off + 64 : off, 0, 16);
         }
@@ -332,7 +305,7 @@ __global__ __launch_bounds__(256) void gemm_p1x_kernel(GemmArgs p, const void* w
   }
   // the surplus requests of the stream's tail must have landed before the workgroup gives its LDS back; the last epilogue's stores, younger,
   // need not be waited for
-  px_wait_vm<(NSTORE > 63 ? 63 : NSTORE)>();
+  wait_vm<(NSTORE > 63 ? 63 : NSTORE)>();
 }
 
 template <bool F16, int BM, int OUT>

@@ -1,4 +1,4 @@
-// bf16 dense contraction for gfx950: PERSISTENT + STAGGERED form of the LDS-DMA pipeline of gemm_dma.hip.
+// bf16 dense contraction for gfx950: PERSISTENT + STAGGERED form of the LDS-DMA pipeline of gemm_pp8.hip / gemm_pers.hip (ring: gemm_ring.h).
 //
 // gemm_pp8_kernel (one tile per workgroup) multiplies a 256 x 256 x 64 slab in 1.24 us -- eight slots per slab, waves 4-7 one
 // slot behind waves 0-3, so that on every SIMD one wave issues MFMAs while its partner reads fragments and issues the ring's
@@ -28,19 +28,10 @@
 //   * write-through (sc1) epilogue stores: the output leaves L2 while the kernel runs instead of at the kernel boundary.
 // Contract: bf16 (operand type) output, no residual, alpha = 1, activation none or GELU, K % 64 == 0, K >= 128, N % 256 == 0,
 // A and W spans below 4 GiB (32-bit offsets).  Everything else stays on gemm_pers_kernel / gemm_pp8_kernel.
-#include "common.h"
+#include "gemm_ring.h"
 
 namespace svt {
 namespace {
-
-template <int N> __device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-
-// one LDS-DMA instruction: 64 lanes x 16 bytes from sbase + voff (per lane) to LDS bytes [lds_addr, lds_addr + 1024)
-__device__ __forceinline__ void dma_sv(unsigned voff, const void* sbase, unsigned lds_addr) {
-  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" ::"s"(lds_addr), "v"(voff), "s"(sbase) : "memory");
-}
-
-typedef unsigned u32x4v __attribute__((ext_vector_type(4)));
 
 // an empty asm that "reads and writes" every register of a fragment array: whatever loads them must have completed here
 template <int N> __device__ __forceinline__ void touch_regs(bf16x8 (&r)[N]) {
@@ -62,9 +53,7 @@ __global__ __launch_bounds__(512) void gemm_pps_kernel(GemmArgs p, int tiles_n, 
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave & 3, wn = (wave >> 2) & 1;   // waves 0-3 (columns 0-127) run one slot ahead of waves 4-7 (columns 128-255)
   const int nblk = gridDim.x, b = blockIdx.x;
-  // blocks b and b + 8 share an XCD: in every round an XCD works on nblk / 8 consecutive logical tiles (n fastest)
-  const int per = nblk >> 3;
-  const int lbase = (b & 7) * per + (b >> 3);
+  const int lbase = xcd_first_tile(b, nblk);
   if (lbase >= ntiles) return;
   const int my_tiles = (ntiles - lbase + nblk - 1) / nblk;
   const int tiles_m = ntiles / tiles_n;
@@ -99,8 +88,7 @@ __global__ __launch_bounds__(512) void gemm_pps_kernel(GemmArgs p, int tiles_n, 
       wo[i] = (unsigned)(((long)n * p.ldw + ch * 8) * 2);
     }
   };
-  const unsigned lds0 = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(void __attribute__((address_space(3)))*)lds);
-  auto lds_unit = [&](int slot, int i) -> unsigned { return lds0 + (unsigned)(slot * SLOT + (wave + 8 * i) * 64) * 16u; };
+  const unsigned lds0 = lds_base(lds);
 
   auto dma = [&](unsigned voff, const void* sbase, unsigned lds_addr) { dma_sv(voff, sbase, lds_addr); };
   f32x4 acc[8][MB];
@@ -134,11 +122,11 @@ __global__ __launch_bounds__(512) void gemm_pps_kernel(GemmArgs p, int tiles_n, 
   }
   // head of the stream: A_0 -> slot 0, W_0 -> slot 1, A_1 -> slot 2
 #pragma unroll
-  for (int i = 0; i < GA; ++i) dma(aofE[i], gA, lds_unit(0, i));
+  for (int i = 0; i < GA; ++i) dma(aofE[i], gA, lds_unit(lds0, wave, 0, i));
 #pragma unroll
-  for (int i = 0; i < GW; ++i) dma(wofE[i], gW, lds_unit(1, i));
+  for (int i = 0; i < GW; ++i) dma(wofE[i], gW, lds_unit(lds0, wave, 1, i));
 #pragma unroll
-  for (int i = 0; i < GA; ++i) dma(aofE[i], gA + BK * 2, lds_unit(2, i));
+  for (int i = 0; i < GA; ++i) dma(aofE[i], gA + BK * 2, lds_unit(lds0, wave, 2, i));
   wait_vm<GA>();   // the bias loads are older than every request of the head
   asm volatile("" : "+v"(bq[0]), "+v"(bq[1]));
   __builtin_amdgcn_s_barrier();
@@ -241,7 +229,7 @@ __global__ __launch_bounds__(512) void gemm_pps_kernel(GemmArgs p, int tiles_n, 
       {                                                                                                             \
         const char* wb = w_cur ? gW + (long)(kt + 1) * (BK * 2) : gW;                                               \
         _Pragma("unroll") for (int i2 = half_ * 2; i2 < half_ * 2 + 2; ++i2)                                        \
-            dma(w_even ? wofE[i2] : wofO[i2], wb, lds_unit(wslot, i2));                                             \
+            dma(w_even ? wofE[i2] : wofO[i2], wb, lds_unit(lds0, wave, wslot, i2));                                             \
       }                                                                                                             \
       if (half_ == 1 && last_k && has_bias) {                                                                       \
         const float* bp = p.bias + (tile_col(ti + 1 < my_tiles ? (ti + 1) * nblk + lbase : lbase) * BN + wn * 128 + (lane & 15) * 8);       \
@@ -255,7 +243,7 @@ __global__ __launch_bounds__(512) void gemm_pps_kernel(GemmArgs p, int tiles_n, 
       {                                                                                                             \
         const char* ab = gA + (long)(a_cur ? kt + 2 : kt + 2 - nk) * (BK * 2);                                      \
         _Pragma("unroll") for (int i2 = half_ * ((GA + 1) / 2); i2 < (half_ ? GA : (GA + 1) / 2); ++i2)             \
-            dma(a_even ? aofE[i2] : aofO[i2], ab, lds_unit(aslot, i2));                                             \
+            dma(a_even ? aofE[i2] : aofO[i2], ab, lds_unit(lds0, wave, aslot, i2));                                             \
       }                                                                                                             \
     }                                                                                                               \
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                                              \

@@ -1,5 +1,5 @@
 // Split-operand products (precision "fp16x3" / "bf16x3") as a PERSISTENT, STAGGERED stream: the schedule of gemm_pps.hip with the
-// operands of gemm_x3_kernel (gemm_dma.hip).
+// operands of gemm_x3s_kernel (gemm_x3s.hip).
 //
 // Why: the one-tile kernels end every tile with 256 KiB of fp32 through LDS transpose patches, the exact-erf GELU of 65 536 values
 // and the store burst of all 256 CUs at once, with the matrix pipes idle; here the epilogue runs out of the accumulators (no LDS),
@@ -22,7 +22,7 @@
 //     (soffset hazard) are those of gemm_pps_kernel.
 // Contract: a plain product against a registered split weight matrix (gemm_dispatch.hip resolves it), N % 256 == 0, K % 32 == 0, K >= 64,
 // no residual, activation none or GELU, fp32 C or (hi, lo) planes.  Everything else stays on gemm_x3s_kernel.
-#include "common.h"
+#include "gemm_ring.h"
 
 #ifdef SVT_OPERAND_F16
 // The split-operand engines live in the bf16 build only (libsvt_mi355.so): precision codes 2 / 3 are rejected by the IEEE-half build.
@@ -35,50 +35,7 @@ int launch_gemm_x3p(int, const GemmArgs&, const void*, hipStream_t) { set_error(
 namespace svt {
 namespace {
 
-template <int N> __device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-__device__ __forceinline__ void dma_sv(unsigned voff, const void* sbase, unsigned lds_addr) {
-  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" ::"s"(lds_addr), "v"(voff), "s"(sbase) : "memory");
-}
-typedef unsigned u32x4v __attribute__((ext_vector_type(4)));
 typedef unsigned u32x2v __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x8v __attribute__((ext_vector_type(8)));
-
-template <bool F16> __device__ __forceinline__ f32x4 mma3(const u32x4v& a, const u32x4v& b, const f32x4& c) {
-  if constexpr (F16) return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8v, a), __builtin_bit_cast(f16x8v, b), c, 0, 0, 0);
-  else return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(real_bf16x8, a), __builtin_bit_cast(real_bf16x8, b), c, 0, 0, 0);
-}
-// 8 fp32 of one lane (two 16-byte chunks) -> (hi, lo) 16-bit pieces
-template <bool F16> __device__ __forceinline__ void cut8(const u32x4v& r0, const u32x4v& r1, u32x4v& hi, u32x4v& lo) {
-  const f32x4 v0 = __builtin_bit_cast(f32x4, r0), v1 = __builtin_bit_cast(f32x4, r1);
-  if constexpr (F16) {
-    f16x8v h, l;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      h[j] = (_Float16)v0[j]; l[j] = (_Float16)(v0[j] - (float)h[j]);
-      h[4 + j] = (_Float16)v1[j]; l[4 + j] = (_Float16)(v1[j] - (float)h[4 + j]);
-    }
-    hi = __builtin_bit_cast(u32x4v, h);
-    lo = __builtin_bit_cast(u32x4v, l);
-  } else {
-    real_bf16x8 h, l;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      h[j] = (__bf16)v0[j]; l[j] = (__bf16)(v0[j] - (float)h[j]);
-      h[4 + j] = (__bf16)v1[j]; l[4 + j] = (__bf16)(v1[j] - (float)h[4 + j]);
-    }
-    hi = __builtin_bit_cast(u32x4v, h);
-    lo = __builtin_bit_cast(u32x4v, l);
-  }
-}
-template <bool F16> __device__ __forceinline__ void cut1(float x, unsigned short& hi, unsigned short& lo) {
-  if constexpr (F16) {
-    const _Float16 a = (_Float16)x, b = (_Float16)(x - (float)a);
-    hi = __builtin_bit_cast(unsigned short, a); lo = __builtin_bit_cast(unsigned short, b);
-  } else {
-    const __bf16 a = (__bf16)x, b = (__bf16)(x - (float)a);
-    hi = __builtin_bit_cast(unsigned short, a); lo = __builtin_bit_cast(unsigned short, b);
-  }
-}
 
 // (the activation is a run-time flag, not a template parameter: the instantiation WITHOUT GELU was the one hipcc could not keep
 // inside 256 registers -- seven spilled dwords whose reloads put s_waitcnt vmcnt(0) between the MFMAs of every slab)
@@ -92,14 +49,12 @@ __global__ __launch_bounds__(512) void gemm_x3p_kernel(GemmArgs p, const void* w
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int nblk = gridDim.x, b = blockIdx.x;
-  const int per = nblk >> 3;
-  const int lbase = (b & 7) * per + (b >> 3);
+  const int lbase = xcd_first_tile(b, nblk);
   if (lbase >= ntiles) return;
   const int my_tiles = (ntiles - lbase + nblk - 1) / nblk;
 
   const char* gW = (const char*)wsplit;   // [N][K / 32][64 x 16 bit]: a row of the packed matrix is 4 K bytes
   // A rows: a 64-bit base per tile (its first row; the whole tensor may exceed 4 GiB) + 32-bit offsets of this lane's rows from it
-  auto a_row_off = [&](int m) -> long { return ((long)(m / p.a_rpb) * p.a_bstride + (long)(m % p.a_rpb) * p.a_rstride) * 4; };
   const char* abase;
   const char* abase2;
   unsigned aof[GA], wof[GW], aof2[GA], wof2[GW];
@@ -109,13 +64,13 @@ __global__ __launch_bounds__(512) void gemm_x3p_kernel(GemmArgs p, const void* w
     const int r8 = ln >> 3, ch = (ln & 7) ^ r8;
     const int tile_n = logical % tiles_n, tile_m = logical / tiles_n;
     const int m0 = tile_m * BM, n0 = tile_n * BN;
-    const long o0 = a_row_off(m0);
+    const long o0 = a_row_off(p, m0);
     ab = (const char*)p.A + o0;
 #pragma unroll
     for (int i = 0; i < GA; ++i) {
       int m = m0 + (wave + 8 * i) * 8 + r8;
       if (m > p.M - 1) m = p.M - 1;
-      ao[i] = (unsigned)(a_row_off(m) - o0) + ch * 16;
+      ao[i] = (unsigned)(a_row_off(p, m) - o0) + ch * 16;
     }
 #pragma unroll
     for (int i = 0; i < GW; ++i) {
@@ -125,8 +80,7 @@ __global__ __launch_bounds__(512) void gemm_x3p_kernel(GemmArgs p, const void* w
       wo[i] = (unsigned)((long)n * p.K * 4 + ch * 16);
     }
   };
-  const unsigned lds0 = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(void __attribute__((address_space(3)))*)lds);
-  auto lds_unit = [&](int slot, int i) -> unsigned { return lds0 + (unsigned)(slot * SLOT + (wave + 8 * i) * 64) * 16u; };
+  const unsigned lds0 = lds_base(lds);
 
   f32x4 acc[NB][2];
 #pragma unroll
@@ -148,13 +102,13 @@ __global__ __launch_bounds__(512) void gemm_x3p_kernel(GemmArgs p, const void* w
   setup(my_tiles > 1 ? nblk + lbase : lbase, abase2, aof2, wof2);
   // head of the stream: A_0 -> slot 0, W_0 -> slot 1, A_1 -> slot 2, W_1 -> slot 3; everything but W_1 landed before slab 0
 #pragma unroll
-  for (int i = 0; i < GA; ++i) dma_sv(aof[i], abase, lds_unit(0, i));
+  for (int i = 0; i < GA; ++i) dma_sv(aof[i], abase, lds_unit(lds0, wave, 0, i));
 #pragma unroll
-  for (int i = 0; i < GW; ++i) dma_sv(wof[i], gW, lds_unit(1, i));
+  for (int i = 0; i < GW; ++i) dma_sv(wof[i], gW, lds_unit(lds0, wave, 1, i));
 #pragma unroll
-  for (int i = 0; i < GA; ++i) dma_sv(aof[i], abase + BK * 4, lds_unit(2, i));
+  for (int i = 0; i < GA; ++i) dma_sv(aof[i], abase + BK * 4, lds_unit(lds0, wave, 2, i));
 #pragma unroll
-  for (int i = 0; i < GW; ++i) dma_sv(wof[i], gW + 128, lds_unit(3, i));
+  for (int i = 0; i < GW; ++i) dma_sv(wof[i], gW + 128, lds_unit(lds0, wave, 3, i));
   wait_vm<GW>();
   __builtin_amdgcn_s_barrier();
 
@@ -227,7 +181,7 @@ __global__ __launch_bounds__(512) void gemm_x3p_kernel(GemmArgs p, const void* w
           for (int s4 = 0; s4 < 4; ++s4) {
             unsigned short hi[4], lo[4];
 #pragma unroll
-            for (int c = 0; c < 4; ++c) cut1<F16>(acc[s4 * 4 + c][mb][r] + bq[s4][c], hi[c], lo[c]);
+            for (int c = 0; c < 4; ++c) cut_piece<F16 ? 3 : 2>(acc[s4 * 4 + c][mb][r] + bq[s4][c], hi[c], lo[c]);
             const u32x2v hv = {(unsigned)hi[0] | ((unsigned)hi[1] << 16), (unsigned)hi[2] | ((unsigned)hi[3] << 16)};
             const u32x2v lv = {(unsigned)lo[0] | ((unsigned)lo[1] << 16), (unsigned)lo[2] | ((unsigned)lo[3] << 16)};
             const unsigned off = off0 + (mb * 16 + r) * row_pitch + s4 * 128;
@@ -281,11 +235,11 @@ __global__ __launch_bounds__(512) void gemm_x3p_kernel(GemmArgs p, const void* w
     if ((Q) < 2) {                                                                                                  \
       const char* ab = (a_cur ? abase : abase2) + (long)(a_cur ? kt + 2 : kt + 2 - nk) * (BK * 4);                  \
       _Pragma("unroll") for (int i2 = (Q) * 2; i2 < (Q) * 2 + 2; ++i2)                                              \
-          dma_sv(a_cur ? aof[i2] : aof2[i2], ab, lds_unit(s3, i2));                                                 \
+          dma_sv(a_cur ? aof[i2] : aof2[i2], ab, lds_unit(lds0, wave, s3, i2));                                                 \
     } else {                                                                                                        \
       const char* wb = gW + (long)(a_cur ? kt + 2 : kt + 2 - nk) * 128;                                             \
       _Pragma("unroll") for (int i2 = ((Q) - 2) * 2; i2 < ((Q) - 2) * 2 + 2; ++i2)                                  \
-          dma_sv(a_cur ? wof[i2] : wof2[i2], wb, lds_unit(s4, i2));                                                 \
+          dma_sv(a_cur ? wof[i2] : wof2[i2], wb, lds_unit(lds0, wave, s4, i2));                                                 \
     }                                                                                                               \
   }
 #define X3P_LOAD(Q) X3P_LOAD_(Q, true)
@@ -304,7 +258,7 @@ __global__ __launch_bounds__(512) void gemm_x3p_kernel(GemmArgs p, const void* w
     if (WITH_DMA) X3P_DMA(Q)                                                                                        \
     __builtin_amdgcn_sched_barrier(0);                                                                              \
     /* (the pieces are "used" here by an empty asm: LLVM otherwise sinks both cuts to their only real use, the copy in the loop  \
-       latch -- behind the slab's last barrier, on the critical path of every slab: gemm_x3s_kernel, gemm_dma.hip) */     \
+       latch -- behind the slab's last barrier, on the critical path of every slab: gemm_x3s_kernel, gemm_x3s.hip) */     \
     if ((Q) == 1) { cut8<F16>(raw[0], raw[1], nh[0], nl[0]); asm volatile("" : "+v"(nh[0]), "+v"(nl[0])); }         \
     if ((Q) == 3) { cut8<F16>(raw[0], raw[1], nh[1], nl[1]); asm volatile("" : "+v"(nh[1]), "+v"(nl[1])); }         \
     __builtin_amdgcn_sched_barrier(0);                                                                              \

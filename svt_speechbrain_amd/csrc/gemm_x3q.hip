@@ -25,7 +25,7 @@
 //     split attention); bias; exact-erf GELU (run-time flag).
 // Contract: plain product (no batch, no residual, alpha 1) of pair rows against a registered split weight matrix, K % 32 == 0,
 // K >= 64, N % 256 == 0, M >= 128.  Everything else stays on gemm_x3s_kernel / the register-staged split kernel, which cut fp32 rows.
-#include "common.h"
+#include "gemm_ring.h"
 
 #ifdef SVT_OPERAND_F16
 // The split-operand engines live in the bf16 build only (libsvt_mi355.so): precision codes 2 / 3 are rejected by the IEEE-half build.
@@ -38,33 +38,6 @@ int launch_gemm_x3q(int, const GemmArgs&, const void*, int, hipStream_t) { set_e
 namespace svt {
 namespace {
 
-template <int N> __device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-__device__ __forceinline__ void dma_sv(unsigned voff, const void* sbase, unsigned lds_addr) {
-  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" ::"s"(lds_addr), "v"(voff), "s"(sbase) : "memory");
-}
-typedef unsigned u32x4v __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8v __attribute__((ext_vector_type(8)));
-
-template <bool F16> __device__ __forceinline__ f32x4 mma16(const u32x4v& a, const u32x4v& b, const f32x4& c) {
-  if constexpr (F16) return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8v, a), __builtin_bit_cast(f16x8v, b), c, 0, 0, 0);
-  else return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(real_bf16x8, a), __builtin_bit_cast(real_bf16x8, b), c, 0, 0, 0);
-}
-// eight fp32 values -> packed (hi, lo) 16-bit pieces
-template <bool F16> __device__ __forceinline__ void cut8v(const float (&v)[8], u32x4v& hi, u32x4v& lo) {
-  if constexpr (F16) {
-    f16x8v h, l;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) { h[j] = (_Float16)v[j]; l[j] = (_Float16)(v[j] - (float)h[j]); }
-    hi = __builtin_bit_cast(u32x4v, h);
-    lo = __builtin_bit_cast(u32x4v, l);
-  } else {
-    real_bf16x8 h, l;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) { h[j] = (__bf16)v[j]; l[j] = (__bf16)(v[j] - (float)h[j]); }
-    hi = __builtin_bit_cast(u32x4v, h);
-    lo = __builtin_bit_cast(u32x4v, l);
-  }
-}
 template <int N> __device__ __forceinline__ void touch_frag(u32x4v (&r)[N]) {
   static_assert(N >= 2 && N <= 4, "fragment arrays of 2..4 blocks");
   if constexpr (N == 4) asm volatile("" : "+v"(r[0]), "+v"(r[1]), "+v"(r[2]), "+v"(r[3]));
@@ -88,14 +61,12 @@ __global__ __launch_bounds__(512) void gemm_x3q_kernel(GemmArgs p, const void* w
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave & 3, wn = (wave >> 2) & 1;   // waves 0-3 (columns 0-127) run one slot ahead of waves 4-7 (columns 128-255)
   const int nblk = gridDim.x, b = blockIdx.x;
-  const int per = nblk >> 3;
-  const int lbase = (b & 7) * per + (b >> 3);      // blocks b and b + 8 share an XCD and take consecutive tiles (n fastest)
+  const int lbase = xcd_first_tile(b, nblk);
   if (lbase >= ntiles) return;
   const int my_tiles = (ntiles - lbase + nblk - 1) / nblk;
 
   const char* gW = (const char*)wsplit;            // [N][K / 32][hi 32 | lo 32]: a row of the packed matrix is 4 K bytes
   const int r8 = lane >> 3, ch = (lane & 7) ^ r8;
-  auto a_row_off = [&](int m) -> long { return ((long)(m / p.a_rpb) * p.a_bstride + (long)(m % p.a_rpb) * p.a_rstride) * 4; };
   // per tile parity (even / odd tiles of this workgroup's list: gemm_pps.hip): the 64-bit address of the tile's first A row, 32-bit
   // offsets of this lane's rows from it, 32-bit offsets of its W rows from the packed matrix
   const char* abE;
@@ -104,13 +75,13 @@ __global__ __launch_bounds__(512) void gemm_x3q_kernel(GemmArgs p, const void* w
   auto setup = [&](int logical, const char*& ab, unsigned (&ao)[GA], unsigned (&wo)[GW]) {
     const int tile_n = logical % tiles_n, tile_m = logical / tiles_n;
     const int m0 = tile_m * BM, n0 = tile_n * BN;
-    const long o0 = a_row_off(m0);
+    const long o0 = a_row_off(p, m0);
     ab = (const char*)p.A + o0;
 #pragma unroll
     for (int i = 0; i < GA; ++i) {
       int m = m0 + (wave + 8 * i) * 8 + r8;
       if (m > p.M - 1) m = p.M - 1;
-      ao[i] = (unsigned)(a_row_off(m) - o0) + ch * 16;
+      ao[i] = (unsigned)(a_row_off(p, m) - o0) + ch * 16;
     }
 #pragma unroll
     for (int i = 0; i < GW; ++i) {
@@ -119,7 +90,8 @@ __global__ __launch_bounds__(512) void gemm_x3q_kernel(GemmArgs p, const void* w
       wo[i] = (unsigned)((long)n * p.K * 4 + ch * 16);
     }
   };
-  const unsigned lds0 = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(void __attribute__((address_space(3)))*)lds);
+  const unsigned lds0 = lds_base(lds);
+  // kept local: a shared function (gemm_ring.h: lds_unit) in place of this lambda changes the schedule hipcc gives this kernel
   auto lds_unit = [&](int slot, int i) -> unsigned { return lds0 + (unsigned)(slot * SLOT + (wave + 8 * i) * 64) * 16u; };
 
   f32x4 acc[8][MB];
@@ -211,7 +183,7 @@ __global__ __launch_bounds__(512) void gemm_x3q_kernel(GemmArgs p, const void* w
           __builtin_amdgcn_raw_buffer_store_b128(v1, crsrc, off + 16, 0, 16);
         } else {
           u32x4v hi, lo;
-          cut8v<F16>(v, hi, lo);
+          cut8<F16>(v, hi, lo);
           __builtin_amdgcn_raw_buffer_store_b128(hi, crsrc, off, 0, 16);
           __builtin_amdgcn_raw_buffer_store_b128(lo, lrsrc, OUT == 1 ? off + 64 : off, 0, 16);
         }
@@ -278,7 +250,7 @@ __global__ __launch_bounds__(512) void gemm_x3q_kernel(GemmArgs p, const void* w
     if (!(DBG & 4)) {                                                                                               \
     _Pragma("unroll") for (int nb = 0; nb < 8; ++nb)                                                                \
       _Pragma("unroll") for (int jj = 0; jj < MB; ++jj)                                                             \
-        acc[nb][jj] = mma16<F16>(xfr[jj], wfr[nb], acc[nb][jj]);                                                    \
+        acc[nb][jj] = mma3<F16>(xfr[jj], wfr[nb], acc[nb][jj]);                                                    \
     } else { touch_frag(xfr); }                                                                                     \
     __builtin_amdgcn_s_setprio(0);                                                                                  \
     __builtin_amdgcn_sched_barrier(0);                                                                              \
