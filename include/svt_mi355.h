@@ -411,8 +411,13 @@ int svt_debug_rca_attn_bwd(int32_t precision, const void* qkv, const void* qc, c
  * this process chose (value ignored; 0 = none yet): 1 = flash_attn_kernel<64>, 2 = flash_attn_kernel<128>, 3 = flash_attn_stag_kernel<64>
  * (head_dim 64, "wide" launches), 4 = flash_attn_kernel<64, true> (position bias), 5 = flash_attn_kernel<64, true, 8> (position bias,
  * wide), 6 = flash_attn_x3_kernel<64, .>, 7 = flash_attn_x3_kernel<128, .>, 8 = flash_attn_x3_stag_kernel<.> (split-operand modes;
- * tests/test_gpu_attention.py asserts the id of every case).
- * Returns 0 (keys 24, 31: the count; key 38: the id), SVT_ERR_INVALID for an unknown key or a value a key does not accept (21, 28, 30, 37 above). */
+ * tests/test_gpu_attention.py asserts the id of every case), 39 = query: svt_debug_set(39, 0) returns which kernel the last dense product of this
+ * process ran on (value ignored; 0 = none yet) as 1000 * family + tile rows: family 1 = gemm_skinny_kernel (32 / 64), 2 = the register-staged
+ * gemm_kernel (128, or 256 for its 256 x 64 form; + 10000 for a split-operand instantiation), 3 = gemm_pp8_kernel (64 / 128 / 192 /
+ * 256), 4 = gemm_pers_kernel, 5 = gemm_pps_kernel, 6 = gemm_p1w_kernel, 7 = gemm_x3s_kernel (256; 192 names its 192-column form),
+ * 8 = gemm_x3p_kernel, 9 = gemm_x3q_kernel, 10 = gemm_p1x_kernel (tests/test_gpu_gemm_kernels.py and tests/test_gpu_gemm.py assert
+ * the id of every case).
+ * Returns 0 (keys 24, 31: the count; keys 38, 39: the id), SVT_ERR_INVALID for an unknown key or a value a key does not accept (21, 28, 30, 37 above). */
 int svt_debug_set(int key, int value);
 
 /* ---- measurement hook: HIP-event timing of the dominant kernel on the stream it runs on ----

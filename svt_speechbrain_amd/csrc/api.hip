@@ -487,6 +487,7 @@ int svt_debug_set(int key, int value) {
   else if (key == 36) g_ffn2_ksplit = value;
   else if (key == 37) { if (value < 8 || value > 256 || value % 8) { set_error("svt_debug_set(37): 8 .. 256, a multiple of 8"); return SVT_ERR_INVALID; } g_gemm_persist_wgs = value; }
   else if (key == 38) return g_flash_kernel_id;
+  else if (key == 39) return g_gemm_kernel_id;
   else { set_error("svt_debug_set: unknown key"); return SVT_ERR_INVALID; }
   return SVT_OK;
 }

@@ -26,9 +26,11 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 namespace svt {
 
 #if defined(__HIPCC__)
-// Exact-erf GELU, erf by Abramowitz-Stegun 7.1.26 (|abs err| <= 1.5e-7: fp32 rounding level, far inside the
-// 1e-3 parity budget): one v_rcp + one v_exp + 8 FMAs instead of libm erff's ~40 instructions.  The conv and
-// FFN epilogues evaluate it ~1.6e9 times per step.
+// Exact-erf GELU, erf by Abramowitz-Stegun 7.1.26: one v_rcp + one v_exp + 8 FMAs instead of libm erff's ~40 instructions.  The
+// formula's |abs err| is <= 1.5e-7; EVALUATED IN fp32 as below, erf is good to 5e-7 absolute (measured on the device over [-8, 8] through
+// the fp32-output kernels, tests/test_gpu_gemm_kernels.py: 4.8e-7 at |x| ~ 0.06, where erf = 1 - poly t e cancels from a product near 1
+// that carries the roundings of the rcp, the Horner chain and the exp; 1.7e-7 for x < -2), i.e. |y error| <= |x| / 2 * 5e-7: fp32
+// rounding level, far inside the 1e-3 parity budget.  The conv and FFN epilogues evaluate it ~1.6e9 times per step.
 __device__ __forceinline__ float gelu_fast(float x) {
   const float z = fabsf(x) * 0.70710678118654752440f;
   const float t = __builtin_amdgcn_rcpf(fmaf(0.3275911f, z, 1.0f));
@@ -122,8 +124,8 @@ __device__ __forceinline__ void gelu_bf16x2_xn(f32x2_t (&x)[NP]) {
 // steps, t q + 1/2, x *) instead of ~33 for the exp form and 17 for the degree-17 erf polynomial this replaces (the epilogue of
 // a GELU tile is VALU-bound: 5.0 -> 3.6 us per 256 x 256 tile).  |Phi error| <= 6.5e-5; |y error| <= 1.0e-4 |x| (2.4e-4 for
 // |x| <= 6, 1e-4 relative for x > 0.01): 20x below the bf16 rounding of the stored value (2^-9 relative).  The additive constant is
-// 1/2 - 9.27e-6 (SVT_GELU_HALF), chosen so that the clamped polynomial is 0 at t = -3.8 (6e-9 in fp32): Phi saturates at 6e-9 /
-// 1 - 1.9e-5 beyond +-3.8, i.e. the negative tail is flushed (|y| <= 6e-9 |x| for x < -3.8 instead of 9.3e-6 |x|, which grew
+// 1/2 - 9.27e-6 (SVT_GELU_HALF), chosen so that the clamped polynomial is 0 at t = -3.8 (6.3e-9 in fp32 with the fused Horner steps below: 6.27e-9): Phi saturates at 6.3e-9 /
+// 1 - 1.9e-5 beyond +-3.8, i.e. the negative tail is flushed (|y| <= 6.3e-9 |x| for x < -3.8 instead of 9.3e-6 |x|, which grew
 // without bound: x = -100 gave -9e-4 for a true value of 0); |Phi error| <= 7.4e-5 overall.  On (-3.8, 0) the error is absolute
 // (<= 7.4e-5 |x|), so the RELATIVE error of the tiny outputs there reaches several per cent -- of values below 5e-3.
 // fp32 outputs keep gelu_fast.  Coefficients: weighted least-squares minimax fit on [0, 3.8].
@@ -335,6 +337,7 @@ extern int g_gemm_skinny_small_tiles;   // key 33: 32 x 32 tiles while the 64 x 
 extern int g_gemm_walk;      // key 34: -1 (default) = choose per launch, 0 = always n fastest, > 0 = this panel height
 extern int g_conv_kperm;     // key 35: 1 (default) = tap-minor K order for the kernel-3 convolutions on gemm_p1w_kernel, 0 = tap-major
 extern int g_gemm_persist_wgs;   // key 37: workgroups of a persistent GEMM launch (256 = one per CU, default; a multiple of 8)
+extern int g_gemm_kernel_id;     // key 39 (query): 1000 * family + tile rows of the kernel the last product ran on (gemm_dispatch.hip)
 
 extern int g_ln_two_rows;  // (hi, lo) LayerNorm: half a wave per row, 16-byte accesses (1, default) or a wave per row (0)
 extern int g_flash_wide;  // fused attention: 8-wave (256-query) workgroups for head_dim 64 (1, default) or 4-wave ones (0)

@@ -28,8 +28,25 @@ int g_gemm_skinny_small_tiles = 96;
 int g_gemm_walk = -1;
 int g_conv_kperm = 1;
 int g_gemm_persist_wgs = 256;
+// key 39 (query): which kernel the last product of this process ran on, 1000 * family + tile rows (+ 10000: a split-operand instantiation of
+// the register-staged kernel); 0 = none yet.  Families: 1 gemm_skinny_kernel, 2 gemm_kernel (register-staged), 3 gemm_pp8_kernel,
+// 4 gemm_pers_kernel, 5 gemm_pps_kernel, 6 gemm_p1w_kernel, 7 gemm_x3s_kernel (tile rows 256; 192 names its 192-COLUMN form),
+// 8 gemm_x3p_kernel, 9 gemm_x3q_kernel, 10 gemm_p1x_kernel.  Written here, behind a launcher's call when it returned 0 (a refused launch
+// leaves the id of the last product that ran), with the height the launcher instantiates (height_of_* below); the kernel files do not know it.
+int g_gemm_kernel_id = 0;
 
 namespace {
+
+// the tile heights the launchers instantiate for a requested bm: 256 / 192 / 128, anything else 64 (launch_gemm_pp8, launch_gemm_pers) or 128
+// (launch_gemm_pps, launch_gemm_p1w, the generalised forms of launch_gemm_pp8); the stamped gemm_p1w forms exist at 256 / 192 only.  The
+// launchers' comments point back here: a launcher that changes its set of instantiations changes these with it.
+int height_of_4(int bm) { return bm == 256 || bm == 192 || bm == 128 ? bm : 64; }
+int height_of_3(int bm) { return bm == 256 || bm == 192 ? bm : 128; }
+// records the kernel of a launch that was made (rc = the launcher's return value, passed through)
+int ran(int family, int rows, int rc) {
+  if (!rc) g_gemm_kernel_id = 1000 * family + rows;
+  return rc;
+}
 
 // Tile height: minimise (rounds of 256 CUs) x (time of one K slab at that height).  The slab times are measured (tools/gemm_trace.py /
 // gemm_bench.py --bm): 1.67 / 1.37 / 1.05 / 0.85 us for 256 / 192 / 128 / 64 rows -- a shorter tile does proportionally less MFMA work
@@ -103,7 +120,7 @@ int launch_dma(const GemmArgs& a0, hipStream_t s) {
       // zeros for half of its MFMAs
       // (a 64-column tile is LDS-read bound -- 18 fragment reads per 16 MFMAs -- and measured slower than the
       // register-staged kernel: 64-channel layers stay there)
-      return a.N <= 128 ? launch_gemm_pp8(a, 256, 128, s) : launch_gemm_pp8(a, best, 256, s);
+      return a.N <= 128 ? ran(3, 256, launch_gemm_pp8(a, 256, 128, s)) : ran(3, height_of_3(best), launch_gemm_pp8(a, best, 256, s));
     }
     const long ntiles = (long)((a.M + best - 1) / best) * tiles_n;
     // Persistent staggered kernel (gemm_pps.hip): bf16 outputs without residual, from 100 tiles up.  With several tiles per workgroup
@@ -118,7 +135,7 @@ int launch_dma(const GemmArgs& a0, hipStream_t s) {
       const int bm = g_gemm_force_bm ? g_gemm_force_bm : (best < 128 ? 128 : best);
       GemmArgs b = persistent(a, bm, false);
       b.dbg = g_gemm_variant % 10;
-      return launch_gemm_pps(b, bm, s);
+      return ran(5, height_of_3(bm), launch_gemm_pps(b, bm, s));
     }
     if (g_gemm_variant != 49 && g_gemm_ring == 0 && best >= 128 && ntiles >= 100 && gemm_pps_eligible(a)) {
       // single-wave-per-SIMD kernel (gemm_p1w.hip, round 5): 5-11 % faster per launch wherever its un-overlapped epilogue is small beside the
@@ -129,16 +146,16 @@ int launch_dma(const GemmArgs& a0, hipStream_t s) {
           // a kernel-3 convolution: tap-minor K order (GemmArgs::k_taps; the caller's second copy of W is stored that way)
           b.W = a.W_kperm; b.k_taps = a.kperm_taps; b.k_cin = a.kperm_cin;
         }
-        return launch_gemm_p1w(b, best, s);
+        return ran(6, a.trace ? (best == 256 ? 256 : 192) : height_of_3(best), launch_gemm_p1w(b, best, s));
       }
-      return launch_gemm_pps(persistent(a, best, false), best, s);
+      return ran(5, height_of_3(best), launch_gemm_pps(persistent(a, best, false), best, s));
     }
     const bool pers_ok = !a.resid && a.nz == 1 && a.K >= 128 && a.N % 256 == 0 && a.c_z1 == 0 && a.c_z2 == 0 &&
                          a.a_z1 == 0 && a.a_z2 == 0 && a.w_z1 == 0 && a.w_z2 == 0;
     int mode = g_gemm_ring;
     if (mode == 0) mode = (pers_ok && ntiles >= 512) ? 4 : 2;
-    if (mode == 4 && pers_ok) return launch_gemm_pers(a, best, s);
-    return launch_gemm_pp8(a, best, 256, s);   // 64-row tiles for mid-size problems (2-16 utterances): twice the workgroups of the 128-row tile
+    if (mode == 4 && pers_ok) return ran(4, height_of_4(best), launch_gemm_pers(a, best, s));
+    return ran(3, height_of_4(best), launch_gemm_pp8(a, best, 256, s));   // 64-row tiles for mid-size problems (2-16 utterances): twice the workgroups of the 128-row tile
   });
 }
 
@@ -156,7 +173,8 @@ int launch_x3(int kind, const GemmArgs& a, hipStream_t s) {
     g.planes_f16 = kind == 3;
     return profiled(a, 4, 4, 0, s, [&] {
       // one wave per SIMD (gemm_p1x.hip; svt_debug_set key 30 = 1: A/B, same bits)
-      return g_gemm_p1x && g.K >= 96 ? launch_gemm_p1x(kind, g, packed, bm, s) : launch_gemm_x3q(kind, g, packed, bm, s);
+      const bool p1x = g_gemm_p1x && g.K >= 96;
+      return ran(p1x ? 10 : 9, bm, p1x ? launch_gemm_p1x(kind, g, packed, bm, s) : launch_gemm_x3q(kind, g, packed, bm, s));
     });
   }
   // batched problems (nz > 1: the grouped positional conv, one z per group): the one-tile kernel with blockIdx.y = z; the registered
@@ -190,14 +208,14 @@ int launch_x3(int kind, const GemmArgs& a, hipStream_t s) {
   return profiled(a, 4, 4, 0, s, [&]() -> int {
     if (x3p_ok && (g_gemm_variant == 34 || (a.act == ACT_GELU && t256 > 256) || t256 >= 1024)) {   // (large QKV, 1 500 tiles: 547 against 583 us)
       g.dbg = g_gemm_dbg == 9 ? 0 : g_gemm_dbg;
-      return launch_gemm_x3p(kind, g, packed, s);
+      return ran(8, 256, launch_gemm_x3p(kind, g, packed, s));
     }
 #ifdef SVT_DIAG
     // slot stamps of the one-tile kernel, and its timing ablations (diagnostics; make DIAG=1)
-    if (g.trace && kind == 3 && g.stamp_ends >= 1 && g.stamp_ends <= 4) return launch_gemm_x3s(kind, g, packed, nbs, 10 + g.stamp_ends, s);
-    if ((g_gemm_variant == 31 || g_gemm_variant == 33) && kind == 3) return launch_gemm_x3s(kind, g, packed, 4, g_gemm_variant - 30, s);
+    if (g.trace && kind == 3 && g.stamp_ends >= 1 && g.stamp_ends <= 4) return ran(7, nbs == 3 ? 192 : 256, launch_gemm_x3s(kind, g, packed, nbs, 10 + g.stamp_ends, s));
+    if ((g_gemm_variant == 31 || g_gemm_variant == 33) && kind == 3) return ran(7, 256, launch_gemm_x3s(kind, g, packed, 4, g_gemm_variant - 30, s));
 #endif
-    return launch_gemm_x3s(kind, g, packed, nbs, 0, s);
+    return ran(7, nbs == 3 ? 192 : 256, launch_gemm_x3s(kind, g, packed, nbs, 0, s));
   });
 }
 
@@ -206,7 +224,8 @@ int launch_x3(int kind, const GemmArgs& a, hipStream_t s) {
 // the small-problem kernel: 32 x 32 tiles while the 64 x 64 tiling has at most g_gemm_skinny_small_tiles workgroups
 int launch_gemm_skinny(const GemmArgs& a, hipStream_t s) {
   const long tiles64 = (long)((a.M + 63) / 64) * ((a.N + 63) / 64) * a.nz;
-  return profiled(a, 2, a.out_f32 ? 4 : 2, 1, s, [&] { return launch_gemm_skinny_tile(a, tiles64 <= g_gemm_skinny_small_tiles ? 32 : 64, s); });
+  const int tile = tiles64 <= g_gemm_skinny_small_tiles ? 32 : 64;
+  return profiled(a, 2, a.out_f32 ? 4 : 2, 1, s, [&] { return ran(1, tile, launch_gemm_skinny_tile(a, tile, s)); });
 }
 
 // prec: 0 = fp32 operands, exact fp32 MFMA; 1 = bf16 operands; 2 / 3 = fp32 operands in memory, bf16x3 / fp16x3
@@ -251,7 +270,9 @@ int launch_gemm(int prec_in, const GemmArgs& a, hipStream_t s) {
             mult(a.bias_z2, 4) && !((uintptr_t)a.bias & 15);
   // the register-staged kernel: 256 x 64 tiles for narrow outputs, 128 x 128 otherwise
   auto staged = [&] {
-    return profiled(g, prec ? 2 : 4, (g.out_f32 || !prec) ? 4 : 2, split ? 0 : 1, s, [&] { return launch_gemm_staged(prec_in, g, a.N <= 64 ? 64 : 128, s); });
+    const int bn = a.N <= 64 ? 64 : 128;
+    return profiled(g, prec ? 2 : 4, (g.out_f32 || !prec) ? 4 : 2, split ? 0 : 1, s,
+                    [&] { return ran(split ? 12 : 2, bn == 64 ? 256 : 128, launch_gemm_staged(prec_in, g, bn, s)); });   // (family 12 = 10000 + family 2)
   };
   if (a.gen) {
     const int kel = prec ? 64 : 32;

@@ -374,6 +374,8 @@ int launch_p1w_t(const GemmArgs& a, hipStream_t s) {
 
 }  // namespace
 
+// bm: 256 / 192, anything else 128; stamped forms: 256, anything else 192 (gemm_dispatch.hip, height_of_3 and its p1w call, names the height
+// that runs for svt_debug_set key 39: keep them in step)
 int launch_gemm_p1w(const GemmArgs& a, int bm, hipStream_t s) {
 #ifdef SVT_DIAG
   if (a.trace) {   // tools/gemm_trace.py --p1w (make DIAG=1): the two tile heights of the encoder's launches, without activation

@@ -293,7 +293,7 @@ int launch_pers(const GemmArgs& a, hipStream_t s) {
 }
 }  // namespace
 
-// bm: 256 / 192 / 128, anything else 64
+// bm: 256 / 192 / 128, anything else 64 (gemm_dispatch.hip, height_of_4, names the height that runs for svt_debug_set key 39: keep them in step)
 int launch_gemm_pers(const GemmArgs& a, int bm, hipStream_t s) {
   if (bm == 256) return launch_pers<256>(a, s);
   if (bm == 192) return launch_pers<192>(a, s);

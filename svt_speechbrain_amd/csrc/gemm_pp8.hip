@@ -309,6 +309,7 @@ int launch_pp8(const GemmArgs& a, hipStream_t s) {
 bool gemm_dma_eligible(const GemmArgs& a) { return a.K % 64 == 0 && a.N >= 128 && a.M >= 128 && a.c_vec && a.N % 8 == 0; }
 
 // bm: 256 / 192 / 128, anything else 64 (generalised addressing: 128); bn = 128 (generalised addressing only, 256-row tiles) or 256
+// (gemm_dispatch.hip, height_of_4 / height_of_3, names the height that runs for svt_debug_set key 39: keep them in step)
 int launch_gemm_pp8(const GemmArgs& a, int bm, int bn, hipStream_t s) {
   if (a.gen) {
     if (bn == 128) return launch_pp8<256, true, 2>(a, s);

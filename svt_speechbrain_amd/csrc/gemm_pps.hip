@@ -375,6 +375,7 @@ bool gemm_pps_eligible(const GemmArgs& a) {
          (a.a_rstride & 7) == 0 && (a.a_bstride & 7) == 0 && (a.ldw & 7) == 0;
 }
 
+// bm: 256 / 192, anything else 128 (gemm_dispatch.hip, height_of_3, names the height that runs for svt_debug_set key 39: keep them in step)
 int launch_gemm_pps(const GemmArgs& a, int bm, hipStream_t s) {
   if (a.act == ACT_GELU) {
     if (bm == 256) return launch_pps_t<256, ACT_GELU>(a, s);

@@ -1,6 +1,12 @@
 """GPU unit tests of the dense contraction kernels through the C-ABI test hook (svt_debug_gemm): every dispatch path
 (persistent LDS-DMA, one-tile LDS-DMA, register-staged bf16 / exact-fp32) against a torch fp32 reference of the same
-op, including implicit-conv row addressing, M / N / K tails, bias, GELU / ReLU and the fp32 residual epilogue."""
+op, including implicit-conv row addressing, M / N / K tails, bias, GELU / ReLU and the fp32 residual epilogue.
+
+Every case pins the kernel it runs on: the id svt_debug_set(39, 0) reports behind the launch, 1000 * family + tile rows
+(include/svt_mi355.h: 1 gemm_skinny_kernel, 2 register-staged gemm_kernel (+ 10000: split-operand), 3 gemm_pp8_kernel, 4 gemm_pers_kernel,
+5 gemm_pps_kernel, 6 gemm_p1w_kernel, 7 gemm_x3s_kernel, 8 gemm_x3p_kernel, 9 gemm_x3q_kernel, 10 gemm_p1x_kernel).  A threshold moved in
+csrc/gemm_dispatch.hip fails the pin instead of silently sending a case to another kernel.  (tests/test_gpu_gemm_kernels.py holds the 16-bit
+kernels to a per-element limit at small shapes, in both builds.)"""
 import pytest
 import torch
 
@@ -34,6 +40,7 @@ def run_gemm(prec, M, N, K, conv=None, act=0, out_f32=0, resid=False, bias=True,
     _lib.check(lib.svt_debug_gemm(prec, A.data_ptr(), W.data_ptr(), C.data_ptr(), b.data_ptr() if bias else None,
                                   R.data_ptr() if resid else None, M, N, K, rpb, bstr, rstr, K, act, out_f32, 0,
                                   torch.cuda.current_stream().cuda_stream), "svt_debug_gemm")
+    run_gemm.kernel_id = lib.svt_debug_set(39, 0)
     torch.cuda.synchronize()
     ref = (A_rows.double() @ W.cpu().double().t()).float() if prec >= 2 else A_rows @ W.cpu().float().t()
     if bias:
@@ -47,17 +54,34 @@ def run_gemm(prec, M, N, K, conv=None, act=0, out_f32=0, resid=False, bias=True,
     return C.cpu().float(), ref
 
 
+run_gemm.kernel_id = 0   # svt_debug_set(39, 0) behind the last run_gemm launch
+
+
+def assert_kernel(kid, what):
+    assert run_gemm.kernel_id == kid, f"{what}: kernel {run_gemm.kernel_id} ran, the case is pinned to kernel {kid}"
+
+
+# kernel id (svt_debug_set key 39) of every case below
+CASE_KERNEL = {
+    "p1w_bf16_gelu": 6192, "p1w_conv": 6256, "pers_f32out": 4256, "pp8_f32out_resid": 3192, "p1w_bf16": 6192, "pp8_relu": 3064,
+    "staged_bf16_small_k": 2128, "skinny_bf16_narrow": 1032, "pp8_bf16_ntail": 3064,
+    "fp32_exact": 2128, "fp32_conv": 2128, "fp32_tiny": 2256, "fp32_head": 2256,
+    "bf16x3": 7192, "bf16x3_conv": 7256, "bf16x3_tiny": 12256, "bf16x3_narrow_ktail": 12256,
+    "fp16x3": 7192, "fp16x3_conv": 7256, "fp16x3_ntail": 7256, "fp16x3_narrow_ktail": 12256,
+    "x3dma_bf16_conv": 7256, "x3dma_fp16_qkv": 7192, "x3dma_fp16_mtail_ntail": 7256, "x3dma_bf16_resid_k32": 7192, "x3dma_fp16_one_tile": 7256,
+}
+
 CASES = [
     # name, prec, M, N, K, conv, act, out_f32, resid
-    ("pers_bf16_gelu", 1, 70000, 512, 1536, None, 1, 0, False),        # >= 512 tiles -> persistent kernel, M tail
-    ("pers_conv", 1, 8 * 15999, 512, 1536, (31999, 15999, 2, 512), 1, 0, False),
-    ("pers_f32out", 1, 66000, 768, 768, None, 0, 1, False),
-    ("uring_f32out_resid", 1, 15968, 768, 768, None, 0, 1, True),      # single round -> one-tile kernel
-    ("uring_bf16", 1, 4999, 2304, 768, None, 0, 0, False),
-    ("uring_relu", 1, 998, 3072, 1024, None, 2, 0, False),
-    ("v1_bf16_small_k", 1, 300, 256, 96, None, 1, 0, False),           # K % 64 != 0 -> register-staged kernel
-    ("v1_bf16_narrow", 1, 499, 48, 6144, None, 1, 1, True),            # grouped pos-conv shape (N = 48)
-    ("v1_bf16_ntail", 1, 777, 200, 128, None, 0, 0, False),
+    ("p1w_bf16_gelu", 1, 70000, 512, 1536, None, 1, 0, False),         # >= 100 tiles, 16-bit output -> gemm_p1w_kernel, M tail
+    ("p1w_conv", 1, 8 * 15999, 512, 1536, (31999, 15999, 2, 512), 1, 0, False),
+    ("pers_f32out", 1, 66000, 768, 768, None, 0, 1, False),            # fp32 output, >= 512 tiles -> gemm_pers_kernel
+    ("pp8_f32out_resid", 1, 15968, 768, 768, None, 0, 1, True),      # single round -> one-tile kernel (gemm_pp8_kernel)
+    ("p1w_bf16", 1, 4999, 2304, 768, None, 0, 0, False),
+    ("pp8_relu", 1, 998, 3072, 1024, None, 2, 0, False),
+    ("staged_bf16_small_k", 1, 300, 256, 96, None, 1, 0, False),           # K % 64 != 0 -> register-staged kernel
+    ("skinny_bf16_narrow", 1, 499, 48, 6144, None, 1, 1, True),        # grouped pos-conv shape (N = 48): the small-problem kernel, 32 x 32 tiles
+    ("pp8_bf16_ntail", 1, 777, 200, 128, None, 0, 0, False),           # N % 16 != 0: no small-problem shape -> gemm_pp8_kernel, 64-row tiles
     ("fp32_exact", 0, 1000, 768, 512, None, 1, 0, True),
     ("fp32_conv", 0, 2 * 999, 512, 1024, (1999, 999, 2, 512), 1, 0, False),
     ("fp32_tiny", 0, 24, 64, 32, None, 0, 0, False),
@@ -83,6 +107,7 @@ CASES = [
 @pytest.mark.parametrize("name,prec,M,N,K,conv,act,out_f32,resid", CASES, ids=[c[0] for c in CASES])
 def test_gemm_vs_torch(name, prec, M, N, K, conv, act, out_f32, resid):
     got, ref = run_gemm(prec, M, N, K, conv, act, out_f32, resid)
+    assert_kernel(CASE_KERNEL[name], name)
     assert torch.isfinite(got).all(), "unwritten (NaN-poisoned) outputs"
     err = (got - ref).abs().max().item()
     # bf16 output rounding dominates in bf16 mode (values O(1..3)); fp32 path is an exact fp32 fma chain
@@ -105,13 +130,20 @@ PPS_CASES = [
 ]
 
 
+# the tile height the cost model picks for each of them (key 1 = 0)
+PPS_AUTO_HEIGHT = {"ffn1_gelu_3_tiles_per_cu": 256, "qkv_no_act": 192, "conv_gelu_mtail": 128, "conv_k1024": 128, "no_bias_two_slabs": 192,
+                   "many_tiles_per_cu": 192, "long_k_single_round": 192}
+
+
 @pytest.mark.parametrize("bm", [0, 256, 192, 128])
 @pytest.mark.parametrize("name,M,N,K,conv,act,bias", PPS_CASES, ids=[c[0] for c in PPS_CASES])
 def test_persistent_staggered_kernel(bm, name, M, N, K, conv, act, bias):
     """gemm_pps_kernel forced for every eligible launch (svt_debug_set key 3 = 70: write-through stores, the form the dispatch uses;
     key 1 = tile height, 0 = the dispatch's choice) against the torch reference: several tiles per workgroup (the ring and the
     source offsets carry over tile boundaries), M tails (rows >= M dropped by the buffer range check), conv rows, bias fetched
-    inside the stream, GELU."""
+    inside the stream, GELU.  The pinned id: gemm_pps_kernel at the forced height, or at the cost model's (PPS_AUTO_HEIGHT) -- except
+    one_tile_ragged, a small-problem shape (7 x 2 tiles of 128 x 256), which the dispatcher hands to gemm_skinny_kernel before key 3 is looked at
+    (tests/test_gpu_gemm_kernels.py runs gemm_pps_kernel on a single round of tiles with that kernel switched off)."""
     lib = _lib.load()
     lib.svt_debug_set(3, 70)
     lib.svt_debug_set(1, bm)
@@ -120,6 +152,7 @@ def test_persistent_staggered_kernel(bm, name, M, N, K, conv, act, bias):
     finally:
         lib.svt_debug_set(3, 0)
         lib.svt_debug_set(1, 0)
+    assert_kernel(1064 if name == "one_tile_ragged" else 5000 + (bm or PPS_AUTO_HEIGHT[name]), (name, bm))
     assert torch.isfinite(got).all(), "unwritten (NaN-poisoned) outputs"
     err = ((got - ref).abs() / (1.0 + ref.abs())).max().item()
     assert err < 8e-3, (name, bm, err)   # bf16 rounding of the stored value: 2^-9 relative
@@ -141,9 +174,11 @@ def test_persistent_kernel_exact_integers_under_load(variant):
     try:
         _lib.check(lib.svt_debug_gemm(1, A.data_ptr(), W.data_ptr(), C.data_ptr(), None, None, M, N, K, M, 0, K, K, 0, 0, 0,
                                       torch.cuda.current_stream().cuda_stream), "svt_debug_gemm")
+        kid = lib.svt_debug_set(39, 0)
         torch.cuda.synchronize()
     finally:
         lib.svt_debug_set(3, 0)
+    assert kid == 5256, f"kernel {kid} ran, the case is pinned to gemm_pps_kernel at 256 rows (5256)"
     ref = (A.float() @ W.float().t()).to(torch.bfloat16)
     assert torch.equal(C, ref)
 
@@ -160,6 +195,10 @@ X3P_CASES = [
 ]
 
 
+X3P_AUTO_KERNEL = {"fp16_conv_gelu_mtail": 7256, "bf16_conv_k1024": 7256, "fp16_qkv_3_tiles_per_cu": 7192, "fp16_ffn1_gelu": 8256,
+                   "bf16_two_slabs_no_bias": 7256, "fp16_one_tile_ragged": 7256, "fp16_n768_single_round": 7192}
+
+
 @pytest.mark.parametrize("variant", [0, 34])
 @pytest.mark.parametrize("name,prec,M,N,K,conv,act,bias", X3P_CASES, ids=[c[0] for c in X3P_CASES])
 def test_split_operand_persistent_kernel(variant, name, prec, M, N, K, conv, act, bias):
@@ -172,6 +211,8 @@ def test_split_operand_persistent_kernel(variant, name, prec, M, N, K, conv, act
         got, ref = run_gemm(prec, M, N, K, conv, act, 0, False, bias=bias)
     finally:
         lib.svt_debug_set(3, 0)
+    # forced: gemm_x3p_kernel (8256); the dispatcher's own choice is the one-tile gemm_x3s_kernel (256- or 192-column tiles) for all but FFN-1
+    assert_kernel(8256 if variant == 34 else X3P_AUTO_KERNEL[name], (name, variant))
     assert torch.isfinite(got).all(), "unwritten (NaN-poisoned) outputs"
     err = (got - ref).abs().max().item()
     assert err < {2: 3e-5, 3: 4e-6}[prec] * max(1.0, (K / 768) ** 0.5), (name, variant, err)
@@ -199,6 +240,7 @@ def run_gemm_pairs(prec, M, N, K, conv, act, out_kind, bias=True, seed=0, want_r
     C = torch.full((M, N), float("nan"), device=DEV)
     _lib.check(lib.svt_debug_gemm_pairs(prec, A.data_ptr(), A.numel(), W.data_ptr(), C.data_ptr(), b.data_ptr() if bias else None, M, N, K,
                                         rpb, bstr, rstr, act, out_kind, 0, torch.cuda.current_stream().cuda_stream, 0, None), "svt_debug_gemm_pairs", lib)
+    run_gemm_pairs.kernel_id = lib.svt_debug_set(39, 0)
     torch.cuda.synchronize()
     if not want_ref:
         return C.cpu(), None
@@ -209,6 +251,11 @@ def run_gemm_pairs(prec, M, N, K, conv, act, out_kind, bias=True, seed=0, want_r
         ref = torch.nn.functional.gelu(ref)
     return C.cpu(), ref.float()
 
+
+run_gemm_pairs.kernel_id = 0   # svt_debug_set(39, 0) behind the last run_gemm_pairs launch
+# the tile height the cost model picks for each X3Q case (key 1 = 0)
+X3Q_AUTO_HEIGHT = {"fp16_conv_gelu_mtail": 128, "bf16_conv_k1024": 128, "fp16_qkv_3_tiles_per_cu": 192, "fp16_ffn1_gelu": 256,
+                   "bf16_two_slabs_no_bias": 192, "fp16_one_tile_ragged": 128, "fp16_n768_single_round": 192, "fp16_three_slabs": 128}
 
 X3Q_CASES = [
     # name, prec, M, N, K, conv, act, bias -- gemm_x3q_kernel: pair-row operands, N % 256 == 0, K % 32 == 0, K >= 64, M >= 128
@@ -241,6 +288,8 @@ def test_pair_row_split_kernel(bm, out_kind, name, prec, M, N, K, conv, act, bia
         got, ref = run_gemm_pairs(prec, M, N, K, conv, act, out_kind, bias=bias)
     finally:
         lib.svt_debug_set(1, 0)
+    want = 9000 + (bm or X3Q_AUTO_HEIGHT[name])
+    assert run_gemm_pairs.kernel_id == want, f"kernel {run_gemm_pairs.kernel_id} ran, the case is pinned to gemm_x3q_kernel ({want})"
     assert torch.isfinite(got).all(), "unwritten (NaN-poisoned) outputs"
     err = (got - ref).abs().max().item()
     # (the bias is the accumulators' initial value: the fp32 partial sums round at the magnitude of bias + sum, not of the sum alone)
@@ -272,8 +321,10 @@ def test_pair_row_one_wave_kernel_equals_two_wave_kernel(bm, out_kind, name, pre
             return
         lib.svt_debug_set(30, 1)
         one, _ = run_gemm_pairs(prec, M, N, K, conv, act, out_kind, bias=bias, want_ref=False, lib=lib)
+        assert run_gemm_pairs.kernel_id == 10000 + bm, f"kernel {run_gemm_pairs.kernel_id} ran, this arm is gemm_p1x_kernel ({10000 + bm})"
         lib.svt_debug_set(30, 0)
         two, _ = run_gemm_pairs(prec, M, N, K, conv, act, out_kind, bias=bias, want_ref=False, lib=lib)
+        assert run_gemm_pairs.kernel_id == 9000 + bm, f"kernel {run_gemm_pairs.kernel_id} ran, this arm is gemm_x3q_kernel ({9000 + bm})"
     finally:
         lib.svt_debug_set(30, 0)
         lib.svt_debug_set(1, 0)
@@ -291,6 +342,9 @@ def test_gemm_rejects_unaligned():
 
 
 
+TILE_WALK_KERNEL = {"ffn1_base": 5256, "ragged_panels": 6192, "large_ffn1": 6256, "narrow": 6192}   # svt_debug_set key 39 of the cases below
+
+
 @pytest.mark.parametrize("name,M,N,K,act", [("ffn1_base", 15968, 3072, 768, 1),        # gemm_pps_kernel (GELU, K < 1024), 63 x 12 tiles of 256 rows
                                             ("ragged_panels", 5200, 2304, 768, 0),      # gemm_p1w_kernel, 28 tile rows: the last panel is short for pm = 3 / 5 / 8 / 16
                                             ("large_ffn1", 12000, 4096, 1024, 1),       # gemm_p1w_kernel<256, GELU>
@@ -306,6 +360,7 @@ def test_persistent_gemm_tile_walk_is_a_permutation(name, M, N, K, act):
         for pm in (0, 3, 5, 8, 16, 64):
             lib.svt_debug_set(34, pm)
             C, ref = run_gemm(1, M, N, K, None, act, 0, False, seed=5)
+            assert_kernel(TILE_WALK_KERNEL[name], (name, pm))
             assert torch.isfinite(C).all(), (name, pm)
             outs[pm] = C
     finally:
