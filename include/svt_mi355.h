@@ -51,8 +51,10 @@ typedef enum {
  *   SVT_PREC_BF16X3  fp32 activations / weights in memory; inside the product kernels every operand is cut into bf16
  *                    (hi, lo) and Ah*Wh + Al*Wh + Ah*Wl is accumulated in fp32 on the bf16 matrix pipe (3 MFMAs of 16
  *                    cycles instead of 8 fp32 MFMAs of 32): ~2^-17 relative operand error, fp32 range
- *   SVT_PREC_FP16X3  the same with fp16 pieces (~2^-22 relative; operands must stay below 65504 in magnitude, which
- *                    holds for the fp16-trained wav2vec2 / HuBERT / WavLM checkpoints the wrapper loads) */
+ *   SVT_PREC_FP16X3  the same with fp16 pieces: ~2^-22 relative for operands of magnitude 0.125 and above; below 0.125 the lo piece
+ *                    is a subnormal half (the device keeps it: conversion and MFMA are exact on subnormals) and carries an ABSOLUTE
+ *                    error of 2^-25 per operand instead (tests/test_gpu_gemm_split_kernels.py).  Operands must stay below 65504 in magnitude,
+ *                    which holds for the fp16-trained wav2vec2 / HuBERT / WavLM checkpoints the wrapper loads */
 typedef enum { SVT_PREC_FP32 = 0, SVT_PREC_BF16 = 1, SVT_PREC_BF16X3 = 2, SVT_PREC_FP16X3 = 3 } svt_precision;
 typedef enum { SVT_NORM_GROUP = 0, SVT_NORM_LAYER = 1 } svt_feat_norm;
 typedef enum { SVT_F32 = 0 } svt_dtype;
@@ -407,7 +409,9 @@ int svt_debug_rca_attn_bwd(int32_t precision, const void* qkv, const void* qc, c
  * tile_walk; same bits), 35 = the kernel-3 convolutions' K slabs tap-minor (1, default: the frame two neighbouring output rows share is
  * re-read out of L2) or tap-major (0) on gemm_p1w_kernel, 36 = FFN-2 of a small batch (<= 2048 rows) as a K-split small GEMM whose
  * partial products the following LayerNorm adds (1, default) or as one product (0), 37 = workgroups of a persistent GEMM launch (8 .. 256,
- * a multiple of 8; 256 = one per CU, default), 38 = query: returns the id of the fused attention kernel the last attention launch of
+ * a multiple of 8; 256 = one per CU, default) of gemm_pps_kernel, gemm_p1w_kernel, gemm_x3p_kernel, gemm_x3q_kernel and gemm_p1x_kernel
+ * (gemm_pers_kernel always launches one per CU): with few workgroups a small product gives each of them several tiles, 38 = query:
+ * returns the id of the fused attention kernel the last attention launch of
  * this process chose (value ignored; 0 = none yet): 1 = flash_attn_kernel<64>, 2 = flash_attn_kernel<128>, 3 = flash_attn_stag_kernel<64>
  * (head_dim 64, "wide" launches), 4 = flash_attn_kernel<64, true> (position bias), 5 = flash_attn_kernel<64, true, 8> (position bias,
  * wide), 6 = flash_attn_x3_kernel<64, .>, 7 = flash_attn_x3_kernel<128, .>, 8 = flash_attn_x3_stag_kernel<.> (split-operand modes;

@@ -314,8 +314,7 @@ int launch_p1x_t(const GemmArgs& a, const void* packed, hipStream_t s) {
   const int ntiles = tiles_m * tiles_n;
   const size_t lds_bytes = 5 * 32768;
   if (int r_ = ensure_dyn_lds((const void*)gemm_p1x_kernel<F16, BM, OUT>, (int)lds_bytes)) return r_;
-  // (one workgroup per CU: svt_debug_set key 37 does not apply to this kernel)
-  hipLaunchKernelGGL((gemm_p1x_kernel<F16, BM, OUT>), dim3(persistent_blocks(ntiles, 256)), dim3(256), lds_bytes, s, a, packed, tiles_n, ntiles);
+  hipLaunchKernelGGL((gemm_p1x_kernel<F16, BM, OUT>), dim3(persistent_blocks(ntiles, g_gemm_persist_wgs)), dim3(256), lds_bytes, s, a, packed, tiles_n, ntiles);
   SVT_LAUNCH_CHECK();
   return 0;
 }

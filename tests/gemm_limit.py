@@ -35,8 +35,9 @@ ETA = {"bf16": 2.0 ** -134, "f16": 2.0 ** -25}   # half the spacing of the 16-bi
 
 # svt_debug_set keys a case may touch, and their defaults: 1 tile height, 2 one-tile / persistent scheduler, 3 kernel arm (70 = gemm_pps_kernel
 # wherever eligible), 6 small-problem kernel on / off, 29 gemm_p1w_kernel (1 where it measured faster, 2 everywhere, 0 never), 33 the small-problem
-# kernel's 32 x 32 threshold, 34 tile walk, 37 workgroups of a persistent launch
-KEY_DEFAULTS = {1: 0, 2: 0, 3: 0, 6: 1, 29: 1, 33: 96, 34: -1, 37: 256}
+# kernel's 32 x 32 threshold, 34 tile walk, 37 workgroups of a persistent launch; the split-operand cases (tests/gemm_split.py) also 3 = 34 (gemm_x3p_kernel
+# wherever eligible), 11 the LDS-DMA split kernels on / off (off: the register-staged split kernel), 30 gemm_p1x_kernel in place of gemm_x3q_kernel
+KEY_DEFAULTS = {1: 0, 2: 0, 3: 0, 6: 1, 11: 1, 29: 1, 30: 0, 33: 96, 34: -1, 37: 256}
 
 # kid: the id svt_debug_set(39, 0) must report (1000 * family + tile rows; include/svt_mi355.h).  conv = (T_in, T_out, stride, cin): implicit-conv
 # rows over a channels-last (B, T_in, cin) tensor, B = M / T_out, K = taps * cin.  keys: {debug key: value} in force for the launch.

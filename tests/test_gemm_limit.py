@@ -1,11 +1,17 @@
 """CPU test of the per-element limit that tests/test_gpu_gemm_kernels.py holds the 16-bit GEMM kernels to (tests/gemm_limit.py): a correct
 kernel, simulated -- fp32 accumulation in 32-wide K chunks, fp32 activation, one round-to-nearest store -- stays inside it on every case
 shape in both builds, and the two defects the flat max-abs tolerances let through do not: a 16-bit store that truncates, and one row that
-misses one 32-element K block."""
+misses one 32-element K block.
+
+The second half does the same for the split-operand kernels (tests/gemm_split.py, tests/test_gpu_gemm_split_kernels.py): a correct simulated
+split kernel is bit-equal to the three-term value T on the exact operands and inside the random limit; four mutants fail the exact test, and
+the first of them -- one row loses Al Wh of one 32-block -- PASSES the random limit, which is why the exact cases exist; and T itself is
+within the mode's documented distance of the fp64 product."""
 import pytest
 import torch
 
 import gemm_limit as G
+import gemm_split as X
 
 
 def _shapes():
@@ -55,3 +61,93 @@ def test_case_tables_reach_every_kernel_and_both_sides_of_the_thresholds():
         assert any(dict(c.keys).get(3) == 70 or dict(c.keys).get(29) == 2 for c in mine) and any(set(dict(c.keys)) <= {1} for c in mine)
     assert {G.gelu_form(c) for c in G.CASES if c.act == 1} == {"fast", "poly"}
     assert {c.kid // 1000 for c in G.GELU_ALONE} == {1, 2, 3, 4, 5, 6}
+
+
+# ---------------- the split-operand kernels (tests/gemm_split.py) ----------------
+@pytest.mark.parametrize("prec,K", [(2, 512), (3, 512), (3, 192), (2, 192)])
+def test_split_exact_operands_on_a_simulated_kernel(prec, K):
+    """The longest K of the exact tables (IEEE-half pieces: P restricted to +-1 there; K = 192 is the longest with P from +-1, +-2): fp32 accumulation of
+    the three piece products in shuffled 32-block order is bit-equal to T, T differs from the fp64 product nearly everywhere, and every mutant is seen."""
+    c = X.S(7256, 128, 128, K)
+    inp = X.exact_inputs(c, prec)
+    exp = X.exact_expected(c, inp, prec)
+    rows = inp["rows"].float()
+    for seed in (0, 1):
+        assert torch.equal(X.simulate(rows, inp["W"], inp["bias"], prec, seed=seed), exp)
+    full = inp["rows"] @ inp["W"].double().t() + inp["bias"].double()
+    assert (exp.double() != full).float().mean().item() > 0.9, "T equals the fp64 product: the exact operands would not show a fourth term"
+    for mutant in X.MUTANTS:
+        got = X.simulate(rows, inp["W"], inp["bias"], prec, mutant=mutant)
+        assert not torch.equal(got, exp), f"the mutant {mutant} is bit-equal to T on the exact operands"
+    # pair / plane output: the cut of T read back is T itself only where T has few enough bits -- the expectation is the emulated cut
+    cp = X.S(9128, 128, 256, K, out_kind=1)
+    inp = X.exact_inputs(cp, prec)
+    exp = X.exact_expected(cp, inp, prec)
+    assert torch.equal(X.recombine(X.simulate(inp["rows"].float(), inp["W"], inp["bias"], prec), X.PIECE[prec][0]), exp)
+
+
+def test_split_exact_operands_refuse_a_k_that_is_too_long():
+    X.exact_inputs(X.S(12256, 24, 64, 772), 3)       # P from +-1: 772 (1 + 8 2^-14) 2^14 < 2^24
+    with pytest.raises(AssertionError, match="too long"):
+        X.exact_inputs(X.S(7256, 128, 128, 1024), 3)
+    with pytest.raises(AssertionError, match="too long"):
+        X.exact_inputs(X.S(7256, 128, 128, 4096), 2)
+
+
+@pytest.mark.parametrize("prec", [2, 3])
+@pytest.mark.parametrize("K", [64, 192, 768])
+def test_split_limit_on_a_simulated_kernel(K, prec):
+    """Random operands: the correct simulated kernel stays inside the limit; a lost K block does not.  A single lost term (Al Wh of one
+    32-block of one row) PASSES at K = 768 -- the limit's documented blindness."""
+    c = X.S(7256, 256, 256, K)
+    inp = G.make_inputs(c, torch.float32)
+    z, S3, ref = X.reference(c, inp, prec)
+    lim = X.limit(c, prec, z, S3, ref, None)
+    rows = inp["rows"].float()
+    ok, where = X.worst(c, X.simulate(rows, inp["W"], inp["bias"], prec), ref, lim)
+    print(f"[prec {prec}] K = {K}: correct kernel {ok:.4f} at {where}")
+    assert ok <= 1.0, (ok, where)
+    block, _ = X.worst(c, X.simulate(rows, inp["W"], inp["bias"], prec, mutant="lost_block"), ref, lim)
+    assert block > 1.0, "a row that misses a whole K block passes the limit"
+    term, _ = X.worst(c, X.simulate(rows, inp["W"], inp["bias"], prec, mutant="lost_term"), ref, lim)
+    print(f"[prec {prec}] K = {K}: one lost Al Wh term {term:.4f}")
+    if K == 768:
+        assert term <= 1.0, "the random limit sees a single lost term after all: say so in tests/gemm_split.py"
+
+
+@pytest.mark.parametrize("prec", [2, 3])
+@pytest.mark.parametrize("K", [64, 768])
+@pytest.mark.parametrize("wscale", ["sqrtK", 0.02])
+def test_split_mode_precision(wscale, K, prec):
+    """|T - fp64 product| stays inside X.mode_bound: on U(-1, 1) / sqrt K weights, and on weights scaled to 0.02, every one of which has a
+    subnormal IEEE-half lo piece (|w| < 0.125), so that the eta term dominates for that piece type."""
+    g = torch.Generator().manual_seed(2)
+    A = torch.rand(256, K, generator=g) * 2 - 1
+    W = (torch.rand(256, K, generator=g) * 2 - 1) * (K ** -0.5 if wscale == "sqrtK" else wscale)
+    T, _ = X.three_term(A, W, prec)
+    err = (T - A.double() @ W.double().t()).abs()
+    ratio = (err / X.mode_bound(A, W, prec)).max().item()
+    print(f"[prec {prec}] K = {K} weights {wscale}: |T - product| / bound {ratio:.3f}")
+    assert 0.0 < ratio <= 1.0
+    if prec == 3:
+        _, wl = X.cut(W, torch.float16)
+        assert (wl.float().abs() < 2.0 ** -14).all(), "these weights were meant to have subnormal lo pieces"
+
+
+def test_split_tables_reach_every_kernel():
+    """Removing the only case that reaches a kernel, a tile height, an output form or an epilogue fails here."""
+    want = {7256, 7192, 8256, 12128, 12256, 2128, 2256} | {f * 1000 + bm for f in (9, 10) for bm in (128, 192, 256)}
+    for table in (X.EXACT, X.RANDOM):
+        assert {c.kid for c in table} == want
+        for fam in (9, 10):
+            assert {(c.kid, c.out_kind) for c in table if c.kid // 1000 == fam} == {(fam * 1000 + bm, ok) for bm in (128, 192, 256) for ok in (0, 1, 2)}
+        for fam in (8, 9, 10):   # a workgroup that walks several tiles
+            assert any(dict(c.keys).get(37) == 8 for c in table if c.kid // 1000 == fam)
+    assert any(c.kid == 8256 and not c.keys for c in X.RANDOM), "gemm_x3p_kernel as the dispatcher's own choice"
+    assert any(c.kid // 1000 == 9 and 1 not in dict(c.keys) for c in X.RANDOM), "gemm_x3q_kernel at the cost model's own height"
+    assert {c.kid // 1000 for c in X.RANDOM if c.act == 1} >= {2, 7, 8, 9, 10, 12}
+    assert {c.kid // 1000 for c in X.ALONE} == {7, 8, 9, 10, 12}
+    assert max(c.K for c in X.EXACT if c.kid // 1000 in (7, 8, 9, 10)) == 512
+    for c in X.EXACT + X.RANDOM + X.ALONE:
+        assert set(dict(c.keys)) <= set(G.KEY_DEFAULTS), c
+    assert X.tile_shape(7192) == (256, 192) and X.tile_shape(12128) == (128, 128) and X.tile_shape(10192) == (192, 256)
