@@ -258,6 +258,33 @@ int svt_debug_gemm_pairs(int32_t precision, const float* a_dev, int64_t a_elems,
 /* (time_iters > 0 with ms_out: after the checked launch the product alone is launched time_iters more times between two HIP events;
  *  *ms_out = milliseconds per launch -- tools/x3q_bench.py) */
 
+/* The same hook for the BATCHED forms of the product (blockIdx.y = z; tests/test_gpu_gemm_batched.py): nz problems of one launch,
+ * z = z1 * nz2 + z2, problem z reading A at a + z1 * a_z1 + z2 * a_z2, W at w + z1 * w_z1 + z2 * w_z2 and the bias at bias + z2 * bias_z2
+ * and writing C (and reading resid, fp32, with C's indexing) at c + z1 * c_z1 + z2 * c_z2 with row pitch ldc:
+ *     C[z][m][n] = act(alpha * sum_k A[z][m][k] W[z][n][k] + bias[z2][n]) + resid[z][m][n],
+ * every stride in elements, rows of A addressed as for svt_debug_gemm.  These are the launches of the score-matrix attention
+ * (alpha = scale, ldc > n, slices of one packed projection), of the grouped positional convolution (a column slice per group of a wider
+ * row, a bias slice per group) and of its phase-folded form.  In the split-operand precisions with ldw == k and k % 32 == 0 the weight
+ * rows the batch spans are cut into (hi, lo) pieces for the call and forgotten after a stream synchronise.  struct_size = the size of
+ * the structure; act: 0 none, 1 GELU, 2 ReLU. */
+typedef struct svt_debug_gemm_desc {
+  int32_t struct_size;
+  const void* a;
+  const void* w;
+  void* c;
+  const float* bias;
+  const float* resid;
+  int32_t m, n, k;
+  int32_t a_rpb;
+  int64_t a_bstride, a_rstride;
+  int64_t ldw, ldc;
+  int32_t nz, nz2;
+  int64_t a_z1, a_z2, w_z1, w_z2, c_z1, c_z2, bias_z2;
+  float alpha;
+  int32_t act, out_f32;
+} svt_debug_gemm_desc;
+int svt_debug_gemm_batched(int32_t precision, const svt_debug_gemm_desc* d, int device, void* stream);
+
 /* ---- AV-HuBERT lip front-end: replaces SubModel / ResEncoder of N20EMv2/video_only/resnet.py:134-187 (the
  * `feature_extractor_video` of the AV-HuBERT model, hubert.py:344-346): 3-D stem + ResNet-18 trunk (PReLU) + Linear(512,
  * embed_dim), eval mode.  Parameter keys are SubModel.state_dict() keys ("resnet.frontend3D.0.weight", "resnet.trunk.layer1.0.
@@ -370,6 +397,17 @@ int svt_debug_attention(int32_t precision, const void* q, const void* k, const v
 int svt_debug_attention_bias(const void* q, const void* k, const void* v, void* o, int32_t batch, int32_t t, int32_t heads, int64_t ldq,
                              int64_t ldkv, int64_t ldo, float scale, const float* gate_dev, const float* pos_bias_dev, int device,
                              void* stream);
+/* The score-matrix attention alone (tests/test_gpu_attention_scores.py): what every attention outside the fused kernels' reach runs --
+ * the fp32 parity mode, 16-bit head sizes other than 64 / 128, WavLM's biased attention at head size 128 or 2 t - 1 > 8192, WavLM in the
+ * split-operand modes.  Two batched products (scale q k^T into fp32 scores with rows padded to a multiple of 8 keys, P V) around the
+ * bias add, the row softmax and the transpose of V.  precision 0 .. 3; q / k / v / o in the storage type of the precision (16-bit for
+ * SVT_PREC_BF16, fp32 otherwise), addressed as for svt_debug_attention; gate_dev (batch, heads, t) / pos_bias_dev (heads, 2 t - 1) f32 as
+ * for svt_debug_attention_bias, or both NULL.  The hook allocates the scores, the probabilities and V^T, fills them with 0xFF bytes (the
+ * encoder's workspace is uninitialised: a pad the kernels fail to write shows up as NaN), synchronises and frees.  A geometry the fused
+ * kernels serve is refused (SVT_ERR_INVALID, nothing is launched): this hook reaches the score-matrix path only. */
+int svt_debug_attention_scores(int32_t precision, const void* q, const void* k, const void* v, void* o, int32_t batch, int32_t t,
+                               int32_t heads, int32_t head_dim, int64_t ldq, int64_t ldkv, int64_t ldo, float scale,
+                               const float* gate_dev, const float* pos_bias_dev, int device, void* stream);
 /* The RCA training kernels alone (tests/test_gpu_fusion_train.py), precision 0 (fp32) or 1 (bf16 operands); workspace convention of
  * svt_linear_backward.  svt_debug_rca_wgrad: dw (n_out, n_in) = sum over the rows of one or two segments of dy_s^T x_s (dy f32 with row
  * strides ldy_s, x operand type (rows, n_in); dy1 / x1 NULL for one segment), db (may be NULL) = the column sums of dy.

@@ -53,6 +53,23 @@ class VideoTransformC(C.Structure):
     _fields_ = [("sub0", C.c_double), ("div0", C.c_double), ("mean", C.c_double), ("std", C.c_double), ("crop_h", C.c_int32), ("crop_w", C.c_int32)]
 
 
+class GemmDescC(C.Structure):
+    """svt_debug_gemm_desc: one batched launch of the dense product (svt_debug_gemm_batched); strides in elements."""
+    _fields_ = [
+        ("struct_size", C.c_int32),
+        ("a", C.c_void_p), ("w", C.c_void_p), ("c", C.c_void_p), ("bias", C.c_void_p), ("resid", C.c_void_p),
+        ("m", C.c_int32), ("n", C.c_int32), ("k", C.c_int32),
+        ("a_rpb", C.c_int32),
+        ("a_bstride", C.c_int64), ("a_rstride", C.c_int64),
+        ("ldw", C.c_int64), ("ldc", C.c_int64),
+        ("nz", C.c_int32), ("nz2", C.c_int32),
+        ("a_z1", C.c_int64), ("a_z2", C.c_int64), ("w_z1", C.c_int64), ("w_z2", C.c_int64), ("c_z1", C.c_int64), ("c_z2", C.c_int64),
+        ("bias_z2", C.c_int64),
+        ("alpha", C.c_float),
+        ("act", C.c_int32), ("out_f32", C.c_int32),
+    ]
+
+
 class FrameC(C.Structure):
     _fields_ = [("p_on", C.c_float), ("p_off", C.c_float), ("octave", C.c_int32), ("pitch_class", C.c_int32)]
 
@@ -98,6 +115,9 @@ SYMBOLS = {
                             C.c_float, C.c_float, C.c_float, _P, _P, C.c_size_t, C.c_int, _P]),
     "svt_debug_gemm": (C.c_int, [C.c_int32, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64,
                                  C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int, _P]),
+    "svt_debug_gemm_batched": (C.c_int, [C.c_int32, C.POINTER(GemmDescC), C.c_int, _P]),
+    "svt_debug_attention_scores": (C.c_int, [C.c_int32, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64,
+                                             C.c_int64, C.c_float, _P, _P, C.c_int, _P]),
     "svt_debug_gemm_pairs": (C.c_int, [C.c_int32, _P, C.c_int64, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64,
                                        C.c_int64, C.c_int32, C.c_int32, C.c_int, _P, C.c_int32, C.POINTER(C.c_float)]),
     "svt_video_create": (C.c_int, [C.c_int32, C.c_int32, C.c_int, C.POINTER(C.c_void_p)]),

@@ -339,6 +339,34 @@ int svt_debug_gemm(int32_t precision, const void* a, const void* w, void* c, con
   return rc ? SVT_ERR_INVALID : SVT_OK;
 }
 
+int svt_debug_gemm_batched(int32_t precision, const svt_debug_gemm_desc* d, int device, void* stream) {
+  if (!d || d->struct_size != (int32_t)sizeof(svt_debug_gemm_desc)) { set_error("svt_debug_gemm_batched: struct_size"); return SVT_ERR_INVALID; }
+  if (!d->a || !d->w || !d->c) { set_error("svt_debug_gemm_batched: null argument"); return SVT_ERR_INVALID; }
+  if (!valid_precision(precision)) { set_error("svt_debug_gemm_batched: precision"); return SVT_ERR_INVALID; }
+  if (d->nz < 1 || d->nz2 < 1 || d->k < 1) { set_error("svt_debug_gemm_batched: nz, nz2 and k must be positive"); return SVT_ERR_INVALID; }
+  SVT_HIP(hipSetDevice(device));
+  GemmArgs g;
+  g.A = d->a; g.W = d->w; g.C = d->c; g.bias = d->bias; g.resid = d->resid;
+  g.M = d->m; g.N = d->n; g.K = d->k; g.a_rpb = d->a_rpb; g.a_bstride = d->a_bstride; g.a_rstride = d->a_rstride;
+  g.ldw = d->ldw; g.ldc = d->ldc;
+  g.nz = d->nz; g.nz2 = d->nz2;
+  g.a_z1 = d->a_z1; g.a_z2 = d->a_z2; g.w_z1 = d->w_z1; g.w_z2 = d->w_z2; g.c_z1 = d->c_z1; g.c_z2 = d->c_z2; g.bias_z2 = d->bias_z2;
+  g.alpha = d->alpha; g.act = d->act; g.out_f32 = d->out_f32;
+  // split-operand modes: the weight rows the batch spans, cut per call (the product path does it once, at finalize); the row count is
+  // launch_x3's own (gemm_dispatch.hip, last_z_row)
+  const bool split = precision >= 2 && d->ldw == d->k && d->k % 32 == 0 && d->w_z1 >= 0 && d->w_z2 >= 0;
+  if (split) {
+    const size_t last_z_row = d->nz > 1 ? ((size_t)(d->nz / d->nz2 - 1) * d->w_z1 + (size_t)(d->nz2 - 1) * d->w_z2) / (size_t)d->k : 0;
+    if (split_weights_register(d->w, (long)last_z_row + d->n, d->k, precision, (hipStream_t)stream)) return SVT_ERR_HIP;
+  }
+  const int rc = launch_gemm(precision, g, (hipStream_t)stream);
+  if (split) {
+    SVT_HIP(hipStreamSynchronize((hipStream_t)stream));
+    split_weights_forget(d->w);
+  }
+  return rc ? SVT_ERR_INVALID : SVT_OK;
+}
+
 int svt_debug_gemm_pairs(int32_t precision, const float* a, int64_t a_elems, const float* w, float* c, const float* bias, int32_t m,
                          int32_t n, int32_t k, int32_t a_rpb, int64_t a_bstride, int64_t a_rstride, int32_t act, int32_t out_kind,
                          int device, void* stream, int32_t time_iters, float* ms_out) {
@@ -436,6 +464,39 @@ int svt_debug_attention_bias(const void* q, const void* k, const void* v, void* 
   if (launch_flash_attention(q, ldq, (long)t * ldq, k, v, ldkv, (long)t * ldkv, o, ldo, (long)t * ldo, batch, t, heads, 64, scale,
                              (hipStream_t)stream, gate_dev, pos_bias_dev)) return SVT_ERR_INVALID;
   return SVT_OK;
+}
+
+int svt_debug_attention_scores(int32_t precision, const void* q, const void* k, const void* v, void* o, int32_t batch, int32_t t,
+                               int32_t heads, int32_t head_dim, int64_t ldq, int64_t ldkv, int64_t ldo, float scale,
+                               const float* gate_dev, const float* pos_bias_dev, int device, void* stream) {
+  if (!q || !k || !v || !o) { set_error("svt_debug_attention_scores: null argument"); return SVT_ERR_INVALID; }
+  if (!valid_precision(precision)) { set_error("svt_debug_attention_scores: precision"); return SVT_ERR_INVALID; }
+  if (batch < 1 || t < 1 || heads < 1 || head_dim < 1) { set_error("svt_debug_attention_scores: batch, t, heads and head_dim must be positive"); return SVT_ERR_INVALID; }
+  if (!gate_dev != !pos_bias_dev) { set_error("svt_debug_attention_scores: gate and pos_bias come together"); return SVT_ERR_INVALID; }
+  if (use_flash(precision, head_dim, gate_dev != nullptr, t)) {
+    set_error("svt_debug_attention_scores: this geometry runs the fused kernel (svt_debug_attention / svt_debug_attention_bias)"); return SVT_ERR_INVALID; }
+  if (int r = check_device(device)) return r;
+  SVT_HIP(hipSetDevice(device));
+  hipStream_t s = (hipStream_t)stream;
+  const int prec = storage_prec(precision);
+  const int Tp = attn_tp(precision, head_dim, t, gate_dev != nullptr);
+  const size_t bh = (size_t)batch * heads;
+  const size_t bytes[3] = {bh * t * Tp * 4, bh * t * Tp * esize(prec), bh * head_dim * Tp * esize(prec)};
+  void* buf[3] = {nullptr, nullptr, nullptr};
+  int rc = 0;
+  for (int i = 0; i < 3 && !rc; ++i) {
+    rc = dev_alloc(&buf[i], bytes[i]);
+    if (!rc && hipMemsetAsync(buf[i], 0xFF, bytes[i], s) != hipSuccess) { set_error("svt_debug_attention_scores: hipMemsetAsync"); rc = SVT_ERR_HIP; }
+  }
+  if (!rc) {
+    AttnBufs ab{};
+    ab.S = (float*)buf[0]; ab.P = buf[1]; ab.Vt = buf[2];
+    rc = attention_scores_path(prec, q, ldq, k, v, ldkv, batch, t, heads, head_dim, scale, ab, false, o, ldo, s, gate_dev, pos_bias_dev,
+                               precision) ? SVT_ERR_INVALID : SVT_OK;
+  }
+  (void)hipStreamSynchronize(s);
+  for (int i = 0; i < 3; ++i) dev_free(buf[i]);
+  return rc;
 }
 
 int svt_debug_set(int key, int value) {

@@ -207,9 +207,11 @@ def three_term(rows, W, prec):
     return (ah + al) @ wh.t() + ah @ wl.t(), (ah.abs() + al.abs()) @ wh.abs().t() + ah.abs() @ wl.abs().t()
 
 
-def reference(c, inp, prec):
-    """(z, S3, ref) in fp64: ref = act(T + bias) + resid, and for pair / plane output its (hi, lo) cut read back as hi + lo."""
+def reference(c, inp, prec, alpha=1.0):
+    """(z, S3, ref) in fp64: ref = act(alpha T + bias) + resid, and for pair / plane output its (hi, lo) cut read back as hi + lo."""
     z, S3 = three_term(inp["rows"].float(), inp["W"], prec)
+    if alpha != 1.0:
+        z, S3 = z * alpha, S3 * abs(alpha)
     if inp["bias"] is not None:
         z = z + inp["bias"].double()
         S3 = S3 + inp["bias"].double().abs()
@@ -228,10 +230,10 @@ def exact_expected(c, inp, prec):
     return recombine(exp, PIECE[prec][0]) if c.out_kind else exp
 
 
-def limit(c, prec, z, S3, ref, resid):
-    """The per-element limit of a random case (module docstring; gemm_limit.py derives the form)."""
+def limit(c, prec, z, S3, ref, resid, alpha=1.0):
+    """The per-element limit of a random case (module docstring; gemm_limit.py derives the form, and the one more rounding of alpha != 1)."""
     terms = c.K if prec == 0 else 3 * c.K
-    lim = 2.0 ** -24 * ref.abs() + 1.13 * (terms + 2) * 2.0 ** -23 * S3
+    lim = 2.0 ** -24 * ref.abs() + 1.13 * (terms + 2 + (alpha != 1.0)) * 2.0 ** -23 * S3
     if c.act == 1:
         lim = lim + G.g_act("fast", None, z)   # every GELU of these kernels is gelu_erf / gelu_fast
     if resid is not None:

@@ -151,3 +151,98 @@ def test_split_tables_reach_every_kernel():
     for c in X.EXACT + X.RANDOM + X.ALONE:
         assert set(dict(c.keys)) <= set(G.KEY_DEFAULTS), c
     assert X.tile_shape(7192) == (256, 192) and X.tile_shape(12128) == (128, 128) and X.tile_shape(10192) == (192, 256)
+
+
+# ---------------- batched launches and the score-matrix attention (tests/test_gpu_gemm_batched.py, tests/test_gpu_attention_scores.py) ----------------
+def _batched_ratio(b, prec, build, dtype, bufs, mutant=None):
+    return G.batched_worst(b, prec, build, bufs, lambda z, ci: G.batched_simulate(b, bufs, z, prec, dtype, mutant).double())
+
+
+@pytest.mark.parametrize("b", G.BATCHED, ids=G.bcase_id)
+def test_batched_limit_on_a_simulated_kernel(b):
+    """Every z of every batched case: the launch stays inside its buffers, and a correct simulated kernel stays inside the limit."""
+    assert G.batched_in_bounds(b), "the case addresses memory outside its buffers"
+    _, dtype, prec, tag = G.batched_runs(b)[-1]   # (the IEEE-half build, or the last split precision)
+    bufs = G.batched_inputs(b, dtype)
+    ok, where = _batched_ratio(b, prec, tag, dtype, bufs)
+    print(f"[{tag}] {G.bcase_id(b)}: correct kernel {ok:.3f} at {where}")
+    assert ok <= 1.0, (ok, where)
+
+
+def _bcase(form, precs, alpha=False):
+    return next(b for b in G.BATCHED if b.geom.form == form and b.precs == precs and (b.alpha != 1.0) == alpha and b.geom.M < 1000)
+
+
+@pytest.mark.parametrize("form,precs,alpha,mutant", [("qk", "16", True, "prev_head"), ("qk", (0,), True, "prev_head"),
+                                                     ("posconv", "16", False, "no_bias_z2"), ("posconv", (2, 3), False, "no_bias_z2"),
+                                                     ("posconv", "16", True, "alpha_last"), ("posconv", (0,), True, "alpha_last"),
+                                                     ("posconv", (2, 3), True, "alpha_last")])
+def test_batched_mutants_fall_outside_the_limit(form, precs, alpha, mutant):
+    """A wrong z stride on the last clip's heads, a dropped bias_z2 and alpha applied after the bias are each seen on a case of the table."""
+    b = _bcase(form, precs, alpha)
+    for _, dtype, prec, tag in G.batched_runs(b):
+        bufs = G.batched_inputs(b, dtype)
+        good, _ = _batched_ratio(b, prec, tag, dtype, bufs)
+        bad, where = _batched_ratio(b, prec, tag, dtype, bufs, mutant)
+        print(f"[{tag}] {G.bcase_id(b)} {mutant}: {bad:.3g} at {where} (correct kernel {good:.3f})")
+        assert good <= 1.0 < bad
+
+
+def test_batched_table_reaches_the_batched_arms():
+    """Families 1, 2, 3, 7 and 12 (include/svt_mi355.h, svt_debug_set key 39) each with nz > 1; every form in every precision class it is served in."""
+    assert {b.kid // 1000 for b in G.BATCHED if b.geom.nz > 1} >= {1, 2, 3, 7, 12}
+    assert {b.kid for b in G.BATCHED} >= {1032, 2128, 2256, 3064, 3192, 7256, 7192, 12128, 12256}
+    assert {(b.geom.form, b.precs) for b in G.BATCHED} >= {(f, p) for f in ("posconv", "folded") for p in ("16", (0,), (2, 3))} | {
+        ("qk", "16"), ("qk", (0,)), ("pv", "16"), ("pv", (0,))}
+    assert any(b.geom.form == "qk" and b.geom.ldc > b.geom.N for b in G.BATCHED) and any(b.geom.form == "qk" and b.geom.ldc == b.geom.N for b in G.BATCHED)
+    assert any(b.geom.nz % b.geom.nz2 for b in G.BATCHED) and any(b.alpha != 1.0 and b.bias for b in G.BATCHED)
+    for b in G.BATCHED:
+        assert set(dict(b.keys)) <= set(G.KEY_DEFAULTS), b
+
+
+def _attn_ratio(c, prec, tag, dtype, parts, mutant=None):
+    x, gate, pb, q, k, v, o, A, delta, spread = parts
+    got = G.attn_simulate(c, prec, dtype, q, k, v, gate, pb, mutant).double()
+    ratio = (got - o).abs() / G.attn_limit(c, prec, tag if prec == 1 else None, v, o, A, delta, spread)
+    return torch.where(torch.isnan(ratio), torch.full_like(ratio, float("inf")), ratio).max().item()
+
+
+def _attn_parts(c, dtype, prec):
+    x, gate, pb = G.attn_inputs(c, dtype)
+    q, k, v = (t.reshape(c.B, c.T, c.H, c.dh) for t in x.split(c.H * c.dh, dim=-1))
+    o, A = G.attn_reference(q, k, v, G.attn_scale(c.dh), gate, pb)
+    return (x, gate, pb, q, k, v, o, A) + G.attn_row_terms(q, k, G.attn_scale(c.dh), gate, pb, prec)
+
+
+@pytest.mark.parametrize("c", [c for c in G.ATTN if c.layout == "packed"], ids=G.acase_id)
+def test_attention_limit_on_a_simulated_pipeline(c):
+    for _, dtype, prec, tag in G.attn_runs(c):
+        ok = _attn_ratio(c, prec, tag, dtype, _attn_parts(c, dtype, prec))
+        print(f"[{tag}] {G.acase_id(c)}: correct pipeline {ok:.3f}")
+        assert ok <= 1.0, (tag, ok)
+
+
+@pytest.mark.parametrize("c,mutant", [(G.AC(2256, 0, 2, 67, 3, 32), "pad_ones"), (G.AC(2256, 0, 2, 9, 2, 64), "pad_ones"), (G.AC(2128, "16", 2, 67, 3, 96), "pad_ones"),
+                                      (G.AC(2128, "16", 2, 65, 2, 128, bias=True), "rel_off_by_one"), (G.AC(12256, 3, 2, 65, 3, 64, bias=True), "rel_off_by_one"),
+                                      (G.AC(2128, "16", 2, 65, 2, 128, bias=True), "gate_next"), (G.AC(12256, 2, 2, 65, 3, 64, bias=True), "gate_next")],
+                         ids=lambda v: G.acase_id(v) if isinstance(v, G.ACase) else v)
+def test_attention_mutants_fall_outside_the_limit(c, mutant):
+    assert c in G.ATTN, "the mutant is shown on a case the GPU test runs"
+    for _, dtype, prec, tag in G.attn_runs(c):
+        bad = _attn_ratio(c, prec, tag, dtype, _attn_parts(c, dtype, prec), mutant)
+        print(f"[{tag}] {G.acase_id(c)} {mutant}: {bad:.3g}")
+        assert bad > 1.0
+
+
+def test_attention_table_reaches_every_route():
+    """fp32: every T % 8 class and both sides of the wave's 64-key stride; 16-bit: head sizes the fused kernels do not serve, and the biased geometries
+    they refuse; split modes: WavLM's route; the separate-q layout once per precision; no case is one the fused kernels would take."""
+    f32 = [c for c in G.ATTN if c.prec == 0]
+    assert {c.T % 8 for c in f32} >= {0, 1, 7} and {c.T for c in f32} >= {1, 63, 64, 65} and any(c.gain == 8.0 for c in f32)
+    assert {c.prec for c in G.ATTN if c.layout == "separate"} == {0, "16", 2, 3}
+    for c in G.ATTN:
+        if c.prec == "16":
+            assert c.dh not in (64, 128) or (c.bias and (c.dh == 128 or 2 * c.T - 1 > 8192)), c
+        if c.prec in (2, 3):
+            assert c.bias or c.layout == "separate"
+    assert any(c.prec == "16" and c.dh == 64 and c.bias and 2 * c.T - 1 == 8199 for c in G.ATTN)
