@@ -208,7 +208,7 @@ int attention_scores_path(int prec, const void* Q, long ldq, const void* K, cons
   if (gp >= 2 && !gate && flash_attention_x3_ok(dh) && ab.pl_qkv && ldkv == 3L * H * dh &&
       (const float*)V == (const float*)K + (long)H * dh) {
     // split-operand fused attention: cut the fp32 projections into 16-bit planes once, then three MFMAs per product
-    // (attention.hip flash_attn_x3_kernel) -- no (B, H, T, T) score tensor
+    // (attention_x3.hip flash_attn_x3_kernel) -- no (B, H, T, T) score tensor
     const long D = (long)H * dh, rows = (long)B * T;
     const float* kv0 = (const float*)K - D;                     // start of the packed (rows, 3D) projection
     const long pl3 = rows * 3 * D;

@@ -341,7 +341,7 @@ extern int g_gemm_kernel_id;     // key 39 (query): 1000 * family + tile rows of
 
 extern int g_ln_two_rows;  // (hi, lo) LayerNorm: half a wave per row, 16-byte accesses (1, default) or a wave per row (0)
 extern int g_flash_wide;  // fused attention: 8-wave (256-query) workgroups for head_dim 64 (1, default) or 4-wave ones (0)
-extern int g_flash_kernel_id;  // fused attention: id of the kernel the last launch chose (attention.hip; svt_debug_set key 38)
+extern int g_flash_kernel_id;  // fused attention: id of the kernel the last launch chose (attention_bf16.hip; svt_debug_set key 38)
 extern int g_ffn2_ksplit;   // svt_debug_set key 36 (api_encoder.hip): FFN-2 of a small batch as a K-split small GEMM + summing LayerNorm
 // switches of the host entry points, defined beside their users; hidden like the helpers of api.h (not part of the exported symbols)
 #pragma GCC visibility push(hidden)
@@ -458,7 +458,7 @@ int launch_relpos_gate(int prec, const void* u, int64_t rows, int T, int H, int 
 int launch_scores_add_relbias(float* S, int64_t BH, int H, int T, int Tp, const float* gate, const float* pb, hipStream_t s);
 int launch_clock_stamp(long long* out16, hipStream_t s);
 
-// ---- attention.hip ----
+// ---- attention_bf16.hip ----
 // fused attention (bf16, head_dim 64/128): Q/K row-major with row strides ldq/ldk and per-clip strides, V^T padded
 // Q/K/V row-major (K and V share row / clip strides); V is transposed on the fly by ds_read_b64_tr_b16
 // gate (B,H,T) / pb (H, 2T-1): WavLM's gated relative position bias, or nullptr
@@ -466,7 +466,8 @@ int launch_flash_attention(const void* Q, long ldq, long q_bstride, const void* 
                            void* O, long ldo, long o_bstride, int B, int T, int H, int dh, float scale, hipStream_t s,
                            const float* gate = nullptr, const float* pb = nullptr);
 
-// split-operand fused attention (attention.hip): fp32 -> 16-bit (hi, lo) planes, then softmax(scale Q K^T) V with three MFMAs
+// ---- attention_x3.hip ----
+// split-operand fused attention: fp32 -> 16-bit (hi, lo) planes, then softmax(scale Q K^T) V with three MFMAs
 // per product; kind = svt_precision (2 = bf16 pieces, 3 = fp16 pieces)
 int launch_split_planes(int kind, const float* src, long ld_src, long rows, int cols, void* dst, long ld_dst, long plane, hipStream_t s);
 bool flash_attention_x3_ok(int dh);

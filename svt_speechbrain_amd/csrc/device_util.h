@@ -1,6 +1,7 @@
 // What the files of HBM-bound kernels share (stats.hip, layernorm.hip, conv0.hip, encoder_ops.hip, small_ops.hip): wave64 shuffle
 // reductions, typed loads / stores, the pair-row cut of the split-operand modes, and two launch helpers.  The kernels are wave64 designs:
 // one wavefront per row where a row reduction is needed (shuffle reductions, no LDS), 16-byte accesses where the layout allows.
+// Also here, for gemm_ring.h and attention_core.h, which both include this file: the LDS-DMA pointer types and lds_base.
 #pragma once
 #include "common.h"
 
@@ -18,6 +19,12 @@ __device__ __forceinline__ float wave_max(float v) {
   for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
   return v;
 }
+
+// LDS-DMA (the GEMM ring of gemm_ring.h, the K / V stages of attention_core.h): the builtin's pointer types, and the LDS byte address
+// of a __shared__ array as the asm forms take it in m0
+typedef const void __attribute__((address_space(1)))* gptr_t;
+typedef void __attribute__((address_space(3)))* lptr_t;
+__device__ __forceinline__ unsigned lds_base(uint4* lds) { return __builtin_amdgcn_readfirstlane((unsigned)(size_t)(lptr_t)lds); }
 
 template <typename T> __device__ __forceinline__ float ld(const T* p, long i);
 template <> __device__ __forceinline__ float ld<float>(const float* p, long i) { return p[i]; }

@@ -13,13 +13,11 @@
 //   * W rows are fetched in MFMA order, permuted (free with per-lane DMA source addresses) so that a lane ends up with consecutive
 //     output columns of one row; every kernel has its own permutation, matched to its epilogue.
 #pragma once
-#include "device_util.h"   // cut_piece<PK>: one fp32 value -> its (hi, lo) 16-bit pieces
+#include "device_util.h"   // gptr_t, lptr_t, lds_base; cut_piece<PK>: one fp32 value -> its (hi, lo) 16-bit pieces
 
 namespace svt {
 namespace {
 
-typedef const void __attribute__((address_space(1)))* gptr_t;
-typedef void __attribute__((address_space(3)))* lptr_t;
 typedef unsigned u32x4v __attribute__((ext_vector_type(4)));   // register image of a 16-byte fragment (an ext vector: usable as an asm operand)
 typedef _Float16 f16x8v __attribute__((ext_vector_type(8)));
 
@@ -30,10 +28,9 @@ template <int N> __device__ __forceinline__ void wait_vm() { asm volatile("s_wai
 __device__ __forceinline__ void dma_sv(unsigned voff, const void* sbase, unsigned lds_addr) {
   asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" ::"s"(lds_addr), "v"(voff), "s"(sbase) : "memory");
 }
-// LDS byte address of the ring, and of the 1 KiB piece (8 rows x 128 B) that DMA instruction i of a wave fills in a slot: the eight
+// LDS byte address (lds_base of the ring) of the 1 KiB piece (8 rows x 128 B) that DMA instruction i of a wave fills in a slot: the eight
 // waves of a workgroup take the pieces of a unit round-robin.  (gemm_x3q, and the four-wave gemm_p1w / gemm_p1x with `wave + 4 * i`, keep
 // this expression in a lambda of their own: with the function hipcc schedules those kernels differently.)
-__device__ __forceinline__ unsigned lds_base(uint4* lds) { return __builtin_amdgcn_readfirstlane((unsigned)(size_t)(lptr_t)lds); }
 __device__ __forceinline__ unsigned lds_unit(unsigned lds0, int wave, int slot, int i) {
   return lds0 + (unsigned)(slot * 2048 + (wave + 8 * i) * 64) * 16u;
 }
