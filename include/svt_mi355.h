@@ -229,6 +229,29 @@ int svt_fbank(const float* wav_dev, int32_t batch, int64_t n_samples, int32_t sa
               int32_t win_length, int32_t hop_length, int32_t n_mels, float f_min, float f_max, float top_db,
               float* out_dev, void* workspace_dev, size_t workspace_bytes, int device, void* stream);
 
+/* ---- noise mixing at several SNRs: replaces the per-SNR chain of N20EMv2/audio_visual/synthesis_noise.py:123-137 (clone, scale,
+ * compute_amplitude, rescale the noise, add) over speechbrain.processing.signal_processing.compute_amplitude (mean |x| of the whole
+ * track) and dB_to_amplitude ----
+ * For clean a and noise v of n_samples each and the n_snr (1..8) ratios snr_db_host[s] (host memory, dB):
+ *     f_s = 1 / (10^(snr_s / 20) + 1) in double;  out_dev[s * ld_out + i] = (1 - f_s) a[i] + (f_s mean|a| / (mean|v| + 1e-14)) v[i]
+ * always from the ORIGINAL v (the reference rescales its noise tensor in place from one SNR to the next, which is the same formula
+ * with a few ulps of drift per step).  Two launches on `stream`, no synchronisation and no host round trip: sum |a| and sum |v| in fp64
+ * (per-workgroup partials added in workgroup order: reproducible bit for bit, no float atomics), then one pass that derives both
+ * coefficients of every row in fp64 on the device, rounds each ONCE to fp32 and evaluates fma(c2, v, c1 * a) in fp32; every element is
+ * within 3 * 2^-24 * (|a| (1 - f) + |v| f mean|a| / (mean|v| + 1e-14)) + 2^-149 of the formula in exact arithmetic.  mean|v| == 0
+ * (a silent noise track) takes c2 = 0, so out = c1 a.  clean_dev, noise_dev and out_dev need 4-byte alignment only; ld_out >= n_samples,
+ * and out_dev[s * ld_out + n_samples .. (s + 1) * ld_out) is not written.  amps_out_dev: NULL, or 2 doubles (8-byte aligned) that
+ * receive mean|a|, mean|v|; with them out_dev may be NULL: the amplitudes alone, no row is written.  workspace_dev: as many bytes as the workspace query returns, 8-byte aligned, contents irrelevant.
+ * n_samples < 1, n_snr outside 1..8, ld_out < n_samples or a non-finite ratio: SVT_ERR_INVALID; a smaller workspace: SVT_ERR_WORKSPACE.
+ * The sums use SVT_NOISE_AMP_WORKGROUPS workgroups per track at most and the mix SVT_NOISE_MIX_MAX_WORKGROUPS, of 256 threads x 4
+ * samples: longer tracks take further trips of the grid-stride loops. */
+#define SVT_NOISE_AMP_WORKGROUPS 256
+#define SVT_NOISE_MIX_MAX_WORKGROUPS 2048
+int64_t svt_noise_mix_workspace_bytes(int64_t n_samples, int32_t n_snr);
+int svt_noise_mix(const float* clean_dev, const float* noise_dev, int64_t n_samples, const float* snr_db_host, int32_t n_snr,
+                  float* out_dev, int64_t ld_out, double* amps_out_dev, void* workspace_dev, int64_t workspace_bytes, int device,
+                  void* stream);
+
 /* ======================================================================================================================
  * DIAGNOSTIC SURFACE: svt_debug_* and svt_prof_*.  These entry points exist for the unit tests of single kernels, the micro-benchmarks
  * under tools/ and the bench's per-launch timing.  They are the ONE exception to the conventions of the product entry points above:

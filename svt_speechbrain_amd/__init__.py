@@ -15,7 +15,10 @@ from . import video  # noqa: F401
 from . import dataio, scoring  # noqa: F401
 from .video import FairseqAVHubertPretrain, EvalTransform  # noqa: F401
 from .song import (SongTranscriber, utterance_bounds, save_song_features, feature_path, song_video_features,  # noqa: F401
-                   save_song_video_features, video_feature_path)
+                   save_song_video_features, video_feature_path, noisy_wav_path, NoiseSweep)
+from . import noise  # noqa: F401
+from .noise import (SNRS_DB, compute_amplitude, mix_at_snrs, assemble_noise_track, split_natural_files, natural_keep,  # noqa: F401
+                    babble_keep, babble_split, noise_pools, natural_pools, babble_pools)
 from . import training  # noqa: F401
 from .training import Adadelta, LinearProbe, FusionTrainer  # noqa: F401
 
@@ -23,4 +26,6 @@ __all__ = ["EncoderConfig", "PRESETS", "config_from_source", "HuggingFaceWav2Vec
            "decode_frames", "frame2note", "frames2note", "frames2note_batch", "frames_to_info", "ctc_greedy_decode", "filter_ctc_output", "AMTForward",
            "SongTranscriber", "utterance_bounds", "save_song_features", "feature_path", "song_video_features",
            "save_song_video_features", "video_feature_path", "EvalTransform", "FairseqAVHubertPretrain",
-           "Adadelta", "LinearProbe", "FusionTrainer"]
+           "Adadelta", "LinearProbe", "FusionTrainer",
+           "SNRS_DB", "compute_amplitude", "mix_at_snrs", "assemble_noise_track", "split_natural_files", "natural_keep", "babble_keep",
+           "babble_split", "noise_pools", "natural_pools", "babble_pools", "noisy_wav_path", "NoiseSweep"]

@@ -197,6 +197,31 @@ int svt_fbank(const float* wav, int32_t B, int64_t L, int32_t sr, int32_t n_fft,
   return launch_fbank_db(out, B, nf * n_mels, top_db, s);
 }
 
+// ---- noise mixing at several SNRs (noise_mix.hip) ----
+int64_t svt_noise_mix_workspace_bytes(int64_t n_samples, int32_t n_snr) {
+  if (n_samples < 1 || n_snr < 1 || n_snr > 8) return -1;
+  return (int64_t)noise_mix_scratch_bytes();
+}
+
+int svt_noise_mix(const float* clean, const float* noise, int64_t n_samples, const float* snr_db, int32_t n_snr, float* out,
+                  int64_t ld_out, double* amps_out, void* workspace, int64_t workspace_bytes, int device, void* stream) {
+  if (n_samples < 1) { set_error("svt_noise_mix: empty track"); return SVT_ERR_INVALID; }
+  if (n_snr < 1 || n_snr > 8) { set_error("svt_noise_mix: n_snr must be in 1..8"); return SVT_ERR_INVALID; }
+  if (!clean || !noise || !snr_db || (!out && !amps_out) || !workspace) { set_error("svt_noise_mix: null argument"); return SVT_ERR_INVALID; }
+  if (ld_out < n_samples) { set_error("svt_noise_mix: ld_out < n_samples"); return SVT_ERR_INVALID; }
+  if (((uintptr_t)clean | (uintptr_t)noise | (uintptr_t)out) & 3) { set_error("svt_noise_mix: tracks must be 4-byte aligned"); return SVT_ERR_INVALID; }
+  if (((uintptr_t)workspace | (uintptr_t)amps_out) & 7) { set_error("svt_noise_mix: workspace and amps_out must be 8-byte aligned"); return SVT_ERR_INVALID; }
+  if (workspace_bytes < svt_noise_mix_workspace_bytes(n_samples, n_snr)) { set_error("svt_noise_mix: workspace too small"); return SVT_ERR_WORKSPACE; }
+  double f[8];
+  for (int i = 0; i < n_snr; ++i) {
+    if (!std::isfinite(snr_db[i])) { set_error("svt_noise_mix: non-finite SNR"); return SVT_ERR_INVALID; }
+    f[i] = 1.0 / (std::pow(10.0, (double)snr_db[i] / 20.0) + 1.0);   // dB_to_amplitude in Python floats (signal_processing.py:354-369)
+  }
+  if (int r = check_device(device)) return r;
+  if (launch_noise_mix(clean, noise, n_samples, f, n_snr, out, ld_out, amps_out, workspace, (hipStream_t)stream)) return SVT_ERR_HIP;
+  return SVT_OK;
+}
+
 // ---- Fbank add-ons ----
 int svt_deltas(const float* x, int64_t ldx, int32_t batch, int32_t t, int32_t c, int32_t window_length, float* out, int64_t ldo,
                int device, void* stream) {

@@ -503,6 +503,12 @@ int launch_decode_frames(const float* logits, int64_t rows, int n_out, int n_oct
 int launch_ctc_greedy(const float* probs, int B, int T, int V, const float* rel_lens, int blank, int32_t* tokens,
                       int32_t* out_lens, hipStream_t s);
 
+// noise mixing at several SNRs (noise_mix.hip): out[s * ld + i] = (1 - f_s) clean[i] + (f_s mean|clean| / (mean|noise| + 1e-14)) noise[i] for
+// the n_snr <= 8 host factors f_s; two launches, no synchronisation; scratch = noise_mix_scratch_bytes() bytes (nothing to zero);
+// amps_out: null, or 2 doubles (mean|clean|, mean|noise|).  Any 4-byte-aligned clean / noise / out, any ld >= n
+size_t noise_mix_scratch_bytes();
+int launch_noise_mix(const float* clean, const float* noise, int64_t n, const double* factors, int n_snr, float* out, int64_t ld,
+                     double* amps_out, void* scratch, hipStream_t s);
 // lip front-end (video.hip)
 int launch_video_pad(int prec, const float* v, int B, int T, int H, int W, int Hp, int Wp, void* out, hipStream_t s);
 // the recipe's uint8 -> float32 pixel map, ((u - sub0) / div0 - mean) / std in float64 (video.hip, svt_video_forward_u8)

@@ -11,7 +11,9 @@
 * its video twin, ``N20EMv2/video_only/extract_ssl_feats.py:28-36,99-111``: the song's lip ROI (``np.load``: ``(T, H, W)`` uint8),
   ``transform_eval``, utterances of ``dur_threshold`` seconds at the video's ``sample_rate`` (50 frames/s; bounds as for the audio,
   ``train_video_ssl.py:537-546``), batch-1 AV-HuBERT forwards, ``feats[0]`` concatenated and saved as
-  ``<folder>/noise_data/video_feats.pt`` (``song_video_features`` / ``save_song_video_features``).
+  ``<folder>/noise_data/video_feats.pt`` (``song_video_features`` / ``save_song_video_features``);
+* the noisy inputs of the audio-visual recipe (``N20EMv2/audio_visual/synthesis_noise.py``): ``NoiseSweep`` mixes a song with a noise
+  track at the recipe's five SNRs on the GPU and transcribes every mixture.
 """
 from __future__ import annotations
 
@@ -21,6 +23,7 @@ from typing import List, Optional, Tuple
 import torch
 
 from .decode import decode_frames, frame2note, frames2note, frames2note_batch, frames_to_info
+from .noise import SNRS_DB, mix_at_snrs
 
 
 def utterance_bounds(n_samples: int, sample_rate: int = 16000, dur_threshold: float = 5.0) -> List[Tuple[int, int]]:
@@ -123,12 +126,46 @@ def feature_path(song_folder: str, add_noise: bool = False, noise_type: Optional
     return os.path.join(song_folder, "noise_data", "clean_feats.pt")
 
 
+def noisy_wav_path(song_folder: str, noise_type: str, snr_db: int) -> str:
+    """Where the reference's synthesis pass stores a noisy copy of the song (synthesis_noise.py:134, 183, 309, 471) -- the file
+    extract_ssl_feats.py:465-476 reads to make the features at ``feature_path(song_folder, True, noise_type, snr_db)``."""
+    return os.path.join(song_folder, "noise_data", str(noise_type), f"SNR_{snr_db}dB.wav")
+
+
 def save_song_features(feats: torch.Tensor, song_folder: str, add_noise: bool = False, noise_type: Optional[str] = None,
                        snr_db: Optional[int] = None) -> str:
     path = feature_path(song_folder, add_noise, noise_type, snr_db)
     os.makedirs(os.path.dirname(path), exist_ok=True)
     torch.save(feats.detach().cpu(), path)
     return path
+
+
+class NoiseSweep:
+    """One song at every SNR of the recipe without a noisy wav on disk: ONE ``mix_at_snrs`` call (noise.py: the arithmetic of
+    ``synthesis_noise.py:123-137`` for all SNRs in one pass over the two tracks), then ``transcriber.transcribe`` per row -- the same
+    streams and the same batched-utterance path as a clean song.  Utterances are not batched across SNR rows."""
+
+    def __init__(self, transcriber: SongTranscriber, snrs_db=SNRS_DB):
+        self.transcriber, self.snrs_db = transcriber, tuple(snrs_db)
+
+    @torch.no_grad()
+    def run(self, clean: torch.Tensor, noise_track: torch.Tensor, song_folder: Optional[str] = None, noise_type: Optional[str] = None):
+        """clean, noise_track: 1-D waveforms of one length on the GPU.  Returns ``{snr_db: (notes, feats)}``; with ``song_folder`` each
+        SNR's features are also written where ``train_rca_av.py:402-408`` looks for them (``feature_path(song_folder, True, noise_type,
+        snr_db)``)."""
+        if song_folder is not None and noise_type is None:
+            raise ValueError("noise_type names the folder the features are written to")
+        n = clean.shape[-1]
+        # rows on 16-byte boundaries, like the clean song of a fresh allocation
+        rows = torch.empty((len(self.snrs_db), (n + 3) // 4 * 4), dtype=torch.float32, device=clean.device)
+        mix = mix_at_snrs(clean, noise_track, self.snrs_db, out=rows[:, :n])
+        out = {}
+        for s, snr in enumerate(self.snrs_db):
+            notes, feats = self.transcriber.transcribe(mix[s], return_feats=True)
+            if song_folder is not None:
+                save_song_features(feats, song_folder, add_noise=True, noise_type=noise_type, snr_db=snr)
+            out[snr] = (notes, feats)
+        return out
 
 
 def video_feature_path(song_folder: str) -> str:
