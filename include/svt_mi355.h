@@ -252,6 +252,36 @@ int svt_noise_mix(const float* clean_dev, const float* noise_dev, int64_t n_samp
                   float* out_dev, int64_t ld_out, double* amps_out_dev, void* workspace_dev, int64_t workspace_bytes, int device,
                   void* stream);
 
+/* ---- polyphase resampling with an optional stereo downmix: replaces speechbrain.processing.speech_augmentation.Resample (Kaldi's
+ * LinearResample: a Python loop of conv1d / conv_transpose1d / pad / += over the P phases) and the `.mean(dim=0)` that follows it in
+ * MIR_ST500/prepare_benchmarks.py:49-72 and N20EMv2/audio_visual/synthesis_noise.py:18-48 (resample_wav) ----
+ * With g = gcd(orig, new), S = orig / g input samples per unit and P = new / g phases, and a host-built table of P filters of W taps
+ * (weights_dev: P x W fp32, row pitch W; first_dev: P int32, the input offset of each filter's first tap within its unit):
+ *     y[row][n * P + p] = sum_{j < W} x[row][n * S + first[p] + j] * weights[p][j]        x taken as 0 outside [0, n_in)
+ * for the n_out outputs the reference's tick rule gives (svt_resample_output_samples: the outputs at times in [0, n_in / orig)).
+ * downmix != 0: rows come in channel pairs (2 r, 2 r + 1) and output row r is 0.5 * (y[2 r] + y[2 r + 1]) of the two fp32 sums, which
+ * is resample-then-mean (the halving is exact).  One launch on `stream` for any number of rows; no synchronisation, no allocation.
+ * Each output is ONE fp32 sum over the W taps in ascending order (fused multiply-adds); two calls give the same bits.
+ * in_dev: rows x n_in, row pitch ld_in >= n_in; out_dev: (downmix ? rows / 2 : rows) x n_out, row pitch ld_out >= n_out; nothing is
+ * read outside a row's n_in samples and nothing is written at out_dev[r * ld_out + n_out .. (r + 1) * ld_out).  All pointers need
+ * 4-byte alignment only.  The table stays in device memory and is not read by the host: entries of first_dev outside [-W, S] (which no
+ * table of the reference's rule has) are taken at the nearer end of that range.
+ * SVT_ERR_INVALID (nothing is written): rows < 1 or n_in < 1; P, W or S < 1; P == S (equal rates: nothing to do); a table and input
+ * span that do not fit SVT_RESAMPLE_LDS_BYTES of LDS even at one unit per workgroup; downmix with an odd number of rows; ld_in < n_in
+ * or ld_out < n_out; a null or misaligned pointer; n_out != the tick rule's value.
+ * svt_resample_output_samples is host-only: the tick rule for n_in samples at orig_freq resampled to new_freq; -1 for n_in < 0 or a
+ * rate < 1.
+ * A workgroup of 256 threads takes G units = G * P consecutive outputs of a row at a time, G the smallest with
+ * G * P >= SVT_RESAMPLE_TILE_OUTPUTS for which the table and the input span fit SVT_RESAMPLE_LDS_BYTES; the grid holds at most
+ * SVT_RESAMPLE_MAX_WORKGROUPS workgroups, which stage the table once and take further tiles beyond that. */
+#define SVT_RESAMPLE_LDS_BYTES 65536
+#define SVT_RESAMPLE_TILE_OUTPUTS 1024
+#define SVT_RESAMPLE_MAX_WORKGROUPS 768
+int64_t svt_resample_output_samples(int64_t n_in, int32_t orig_freq, int32_t new_freq);
+int svt_resample(const float* in_dev, int32_t rows, int64_t n_in, int64_t ld_in, const float* weights_dev, const int32_t* first_dev,
+                 int32_t P, int32_t W, int32_t S, float* out_dev, int64_t n_out, int64_t ld_out, int32_t downmix, int device,
+                 void* stream);
+
 /* ======================================================================================================================
  * DIAGNOSTIC SURFACE: svt_debug_* and svt_prof_*.  These entry points exist for the unit tests of single kernels, the micro-benchmarks
  * under tools/ and the bench's per-launch timing.  They are the ONE exception to the conventions of the product entry points above:

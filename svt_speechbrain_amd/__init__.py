@@ -19,6 +19,8 @@ from .song import (SongTranscriber, utterance_bounds, save_song_features, featur
 from . import noise  # noqa: F401
 from .noise import (SNRS_DB, compute_amplitude, mix_at_snrs, assemble_noise_track, split_natural_files, natural_keep,  # noqa: F401
                     babble_keep, babble_split, noise_pools, natural_pools, babble_pools)
+from . import resample  # noqa: F401
+from .resample import Resample, SpeedPerturb, resample_table, resample_to_mono  # noqa: F401
 from . import training  # noqa: F401
 from .training import Adadelta, LinearProbe, FusionTrainer  # noqa: F401
 
@@ -28,4 +30,5 @@ __all__ = ["EncoderConfig", "PRESETS", "config_from_source", "HuggingFaceWav2Vec
            "save_song_video_features", "video_feature_path", "EvalTransform", "FairseqAVHubertPretrain",
            "Adadelta", "LinearProbe", "FusionTrainer",
            "SNRS_DB", "compute_amplitude", "mix_at_snrs", "assemble_noise_track", "split_natural_files", "natural_keep", "babble_keep",
-           "babble_split", "noise_pools", "natural_pools", "babble_pools", "noisy_wav_path", "NoiseSweep"]
+           "babble_split", "noise_pools", "natural_pools", "babble_pools", "noisy_wav_path", "NoiseSweep",
+           "Resample", "SpeedPerturb", "resample_table", "resample_to_mono"]

@@ -115,6 +115,9 @@ SYMBOLS = {
                             C.c_float, C.c_float, C.c_float, _P, _P, C.c_size_t, C.c_int, _P]),
     "svt_noise_mix_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int32]),
     "svt_noise_mix": (C.c_int, [_P, _P, C.c_int64, C.POINTER(C.c_float), C.c_int32, _P, C.c_int64, _P, _P, C.c_int64, C.c_int, _P]),
+    "svt_resample_output_samples": (C.c_int64, [C.c_int64, C.c_int32, C.c_int32]),
+    "svt_resample": (C.c_int, [_P, C.c_int32, C.c_int64, C.c_int64, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int64, C.c_int64,
+                               C.c_int32, C.c_int, _P]),
     "svt_debug_gemm": (C.c_int, [C.c_int32, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64,
                                  C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int, _P]),
     "svt_debug_gemm_batched": (C.c_int, [C.c_int32, C.POINTER(GemmDescC), C.c_int, _P]),

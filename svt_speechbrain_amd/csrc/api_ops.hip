@@ -222,6 +222,44 @@ int svt_noise_mix(const float* clean, const float* noise, int64_t n_samples, con
   return SVT_OK;
 }
 
+// ---- polyphase resampling with an optional stereo downmix (resample.hip) ----
+namespace {
+int64_t gcd64(int64_t a, int64_t b) { while (b) { const int64_t t = a % b; a = b; b = t; } return a; }
+// Resample._output_samples (LinearResample::GetNumOutputSamples): time in ticks of 1 / lcm(orig, new); an input period is new / g
+// ticks, an output period orig / g; the outputs at ticks in [0, n_in * new / g)
+int64_t tick_rule(int64_t n_in, int64_t orig, int64_t fresh) {
+  const int64_t g = gcd64(orig, fresh), per_in = fresh / g, per_out = orig / g;
+  const int64_t interval = n_in * per_in;
+  if (interval <= 0) return 0;
+  int64_t last = interval / per_out;
+  if (last * per_out == interval) --last;
+  return last + 1;
+}
+}  // namespace
+
+int64_t svt_resample_output_samples(int64_t n_in, int32_t orig_freq, int32_t new_freq) {
+  if (n_in < 0 || orig_freq < 1 || new_freq < 1) return -1;
+  return tick_rule(n_in, orig_freq, new_freq);
+}
+
+int svt_resample(const float* in, int32_t rows, int64_t n_in, int64_t ld_in, const float* weights, const int32_t* first, int32_t P, int32_t W,
+                 int32_t S, float* out, int64_t n_out, int64_t ld_out, int32_t downmix, int device, void* stream) {
+  if (rows < 1 || n_in < 1) { set_error("svt_resample: empty input"); return SVT_ERR_INVALID; }
+  if (P < 1 || W < 1 || S < 1) { set_error("svt_resample: P, W and S must be positive"); return SVT_ERR_INVALID; }
+  if (P == S) { set_error("svt_resample: P == S, the rates are equal and there is nothing to resample"); return SVT_ERR_INVALID; }
+  if (resample_units_per_tile(P, W, S, downmix != 0) < 1) { set_error("svt_resample: the filter table does not fit SVT_RESAMPLE_LDS_BYTES of LDS"); return SVT_ERR_INVALID; }
+  if (downmix && (rows & 1)) { set_error("svt_resample: downmix takes channel pairs, rows must be even"); return SVT_ERR_INVALID; }
+  if (ld_in < n_in) { set_error("svt_resample: ld_in < n_in"); return SVT_ERR_INVALID; }
+  if (ld_out < n_out) { set_error("svt_resample: ld_out < n_out"); return SVT_ERR_INVALID; }
+  if (!in || !weights || !first || !out) { set_error("svt_resample: null argument"); return SVT_ERR_INVALID; }
+  if (((uintptr_t)in | (uintptr_t)weights | (uintptr_t)first | (uintptr_t)out) & 3) { set_error("svt_resample: pointers must be 4-byte aligned"); return SVT_ERR_INVALID; }
+  if (n_out != tick_rule(n_in, S, P)) { set_error("svt_resample: n_out is not what svt_resample_output_samples gives for n_in"); return SVT_ERR_INVALID; }
+  if (int r = check_device(device)) return r;
+  const int rows_out = downmix ? rows / 2 : rows;
+  if (launch_resample(in, rows_out, n_in, ld_in, weights, first, P, W, S, out, n_out, ld_out, downmix != 0, (hipStream_t)stream)) return SVT_ERR_HIP;
+  return SVT_OK;
+}
+
 // ---- Fbank add-ons ----
 int svt_deltas(const float* x, int64_t ldx, int32_t batch, int32_t t, int32_t c, int32_t window_length, float* out, int64_t ldo,
                int device, void* stream) {

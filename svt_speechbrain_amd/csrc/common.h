@@ -509,6 +509,12 @@ int launch_ctc_greedy(const float* probs, int B, int T, int V, const float* rel_
 size_t noise_mix_scratch_bytes();
 int launch_noise_mix(const float* clean, const float* noise, int64_t n, const double* factors, int n_snr, float* out, int64_t ld,
                      double* amps_out, void* scratch, hipStream_t s);
+// polyphase resampling (resample.hip): out[r][n * P + p] = sum_j in[r][n * S + first[p] + j] * w[p][j], zeros outside [0, n_in); downmix:
+// out[r] = 0.5 * (y[2 r] + y[2 r + 1]).  One launch; rows_out rows of n_out outputs.  resample_units_per_tile: the G of the launch
+// (units per workgroup), 0 when the table does not fit the LDS cap at G = 1
+int resample_units_per_tile(int P, int W, int S, bool downmix);
+int launch_resample(const float* in, int rows_out, int64_t n_in, int64_t ld_in, const float* w, const int32_t* first, int P, int W, int S,
+                    float* out, int64_t n_out, int64_t ld_out, bool downmix, hipStream_t s);
 // lip front-end (video.hip)
 int launch_video_pad(int prec, const float* v, int B, int T, int H, int W, int Hp, int Wp, void* out, hipStream_t s);
 // the recipe's uint8 -> float32 pixel map, ((u - sub0) / div0 - mean) / std in float64 (video.hip, svt_video_forward_u8)

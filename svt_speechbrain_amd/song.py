@@ -24,6 +24,7 @@ import torch
 
 from .decode import decode_frames, frame2note, frames2note, frames2note_batch, frames_to_info
 from .noise import SNRS_DB, mix_at_snrs
+from .resample import resample_to_mono
 
 
 def utterance_bounds(n_samples: int, sample_rate: int = 16000, dur_threshold: float = 5.0) -> List[Tuple[int, int]]:
@@ -72,8 +73,14 @@ class SongTranscriber:
         return self._encoders, [torch.cuda.current_stream(device)] + self._side
 
     @torch.no_grad()
-    def transcribe(self, song: torch.Tensor, return_feats: bool = False):
-        """song: 1-D waveform on the GPU.  Returns notes [[on_s, off_s, midi], ...] (and the (T_song, D) features)."""
+    def transcribe(self, song: torch.Tensor, return_feats: bool = False, sample_rate: Optional[int] = None):
+        """song: 1-D waveform on the GPU.  Returns notes [[on_s, off_s, midi], ...] (and the (T_song, D) features).
+
+        sample_rate: None (the default) -- ``song`` is mono at ``self.sample_rate``, as ever.  Otherwise ``song`` is ``(n,)`` or ``(C, n)``
+        (C = 1 or 2) at that rate and first goes through ``resample_to_mono`` to ``self.sample_rate``: the preparation scripts' Resample and
+        channel mean (``MIR_ST500/prepare_benchmarks.py:49-72``), one launch on the GPU."""
+        if sample_rate is not None:
+            song = resample_to_mono(song, sample_rate, self.sample_rate)
         if song.dim() != 1:
             raise ValueError("expected a mono 1-D waveform")
         encs, lanes = self._lanes(song.device)
