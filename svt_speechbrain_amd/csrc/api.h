@@ -2,6 +2,7 @@
 // the attention score path and the argument checks every entry point family uses.  Included by the api*.hip files only.
 #pragma once
 #include "common.h"
+#include "host.h"
 
 #include <cstddef>
 #include <cstdint>
@@ -35,6 +36,10 @@ int upload_operand(int prec, DevBuf& b, const float* h, size_t n);
 // weight matrix (rows x K, K contiguous): storage copy as upload_operand + in the split-operand modes the packed (hi, lo)
 // pieces the LDS-DMA split kernels read (split_weights.hip); `precision` is the svt_precision of the object
 int upload_weight(int precision, DevBuf& b, const float* h, size_t rows, size_t K);
+// parameter intake of the svt_*_finalize steps: the loaded tensor `key`, which must have exactly the shape (C) / (rows, K) (need():
+// SVT_ERR_KEY when it is missing, SVT_ERR_INVALID when mis-shaped), uploaded as upload_f32 / upload_weight do
+int upload_vec(const ParamMap& P, const std::string& key, int C, DevBuf* out);
+int upload_mat(int precision, const ParamMap& P, const std::string& key, int rows, int K, DevBuf* out);
 // first step of every svt_*_finalize: waits for the forwards still in flight before a RE-upload changes live buffers
 int begin_upload(bool& uploaded);
 

@@ -180,6 +180,17 @@ int upload_weight(int precision, DevBuf& b, const float* h, size_t rows, size_t 
   return 0;
 }
 
+int upload_vec(const ParamMap& P, const std::string& key, int C, DevBuf* out) {
+  const Param* p = nullptr;
+  if (int r = need(P, key, {C}, &p)) return r;
+  return upload_f32(*out, p->v.data(), p->v.size());
+}
+int upload_mat(int precision, const ParamMap& P, const std::string& key, int rows, int K, DevBuf* out) {
+  const Param* p = nullptr;
+  if (int r = need(P, key, {rows, K}, &p)) return r;
+  return upload_weight(precision, *out, p->v.data(), (size_t)rows, (size_t)K);
+}
+
 // A RE-upload overwrites live weight buffers in place (DevBuf::alloc keeps a buffer of unchanged size; the uploads and conversions run
 // on the null stream, which does not order against the callers' non-blocking streams): wait for every forward still in flight on this
 // device -- replica() lanes share these buffers -- before the first byte changes (tests/test_gpu_uploads.py)

@@ -1,6 +1,9 @@
 // C ABI of the encoder (include/svt_mi355.h): parameter intake by HF key, the one-time re-layout / fold / cast at finalize, workspace
 // carving and the launch sequence of a forward, with or without the fused frame-head tail.  Host code only: no allocation and no
 // synchronisation inside a forward call.
+//   finalize: finalize_conv_stack -> finalize_projection -> finalize_pos_conv(_stack) -> encoder LayerNorm -> finalize_layer
+//   forward:  plan_encoder -> carve_encoder -> input_statistics -> choose_pair_rows -> conv_layer0 -> conv_stack -> feature_projection
+//             -> positional_conv -> encoder_layers (post_ln_layers / pre_ln_layers) -> forward_tail
 #include "../../include/svt_mi355.h"
 #include "api.h"
 #include "common.h"
@@ -17,7 +20,7 @@ int svt::g_conv_ln_bf16 = 1;     // svt_debug_set(9, 0): fp32 conv output + Laye
 
 struct ConvLayerW {
   DevBuf w;      // layer 0: fp32 (C,k); others: operand type (Cout, k*Cin) tap-major
-  DevBuf w_kperm;   // 16-bit modes, kernel 3 / stride 2: the same matrix with its K axis in tap-minor slab order (svt_encoder_finalize)
+  DevBuf w_kperm;   // 16-bit modes, kernel 3 / stride 2: the same matrix with its K axis in tap-minor slab order (finalize_conv_stack)
   DevBuf bias;   // fp32 or empty
   DevBuf gamma, beta;
 };
@@ -46,6 +49,210 @@ struct svt_encoder {
   void* reduce_user = nullptr;
   int64_t reduce_global_clips = 0;
 };
+
+// every mode but plain fp32 (16-bit storage, or fp32 storage with split-operand products): conv layer 0 on the matrix pipe, the
+// multi-frame positional conv, and a residual stream kept in fp32 beside the products' operand copy
+static bool reduced_mode(const svt_encoder_config& c) { return c.precision != SVT_PREC_FP32; }
+
+// frames the conv stack makes of n_samples (features-in mode: n_samples itself), 0 for a waveform shorter than the receptive field;
+// frames[i] = output frames of conv layer i
+static int64_t conv_frames(const svt_encoder_config& c, int64_t n_samples, int64_t* frames = nullptr) {
+  int64_t t = n_samples;
+  for (int i = 0; i < c.num_conv_layers; ++i) {
+    if (t < c.conv_kernel[i]) return 0;
+    t = (t - c.conv_kernel[i]) / c.conv_stride[i] + 1;
+    if (frames) frames[i] = t;
+  }
+  return t;
+}
+
+// ---------------------------------------------------------------- finalize: one step per parameter group
+namespace {
+
+int finalize_conv_stack(svt_encoder* e) {
+  const svt_encoder_config& c = e->cfg;
+  const ParamMap& P = e->params;
+  if ((int)e->conv.size() != c.num_conv_layers) { e->conv.clear(); e->conv.resize(c.num_conv_layers); }   // a re-upload keeps the buffers
+  int cin = 1;
+  for (int i = 0; i < c.num_conv_layers; ++i) {
+    const std::string pre = "feature_extractor.conv_layers." + std::to_string(i) + ".";
+    const int co = c.conv_dim[i], k = c.conv_kernel[i];
+    const Param* p = nullptr;
+    if (int r = need(P, pre + "conv.weight", {co, cin, k}, &p)) return r;
+    ConvLayerW& L = e->conv[i];
+    if (i == 0) {
+      if (int r = upload_f32(L.w, p->v.data(), p->v.size())) return r;
+    } else {
+      const std::vector<float> wt = tap_major(p->v.data(), co, cin, k);
+      if (int r = upload_weight(c.precision, L.w, wt.data(), (size_t)co, (size_t)k * cin)) return r;
+      // 16-bit modes, kernel 3: a second copy with the K axis in TAP-MINOR slab order -- slab g = tap g % 3 of channels [(g / 3) * 64, + 64)
+      // -- for gemm_p1w_kernel (GemmArgs::k_taps): the input frame two neighbouring output rows share is re-read two slabs later instead
+      // of sixteen, i.e. out of L2 (1.5 MiB per layer)
+      if (storage_prec(c.precision) && k == 3 && cin % 64 == 0 && c.conv_stride[i] == 2) {
+        const std::vector<float> wp = tap_minor_slabs(wt.data(), co, cin, k);
+        if (int r = upload_weight(c.precision, L.w_kperm, wp.data(), (size_t)co, (size_t)k * cin)) return r;
+      } else L.w_kperm.release();
+    }
+    if (c.conv_bias)
+      if (int r = upload_vec(P, pre + "conv.bias", co, &L.bias)) return r;
+    if (c.feat_extract_norm == SVT_NORM_LAYER || i == 0) {
+      if (int r = upload_vec(P, pre + "layer_norm.weight", co, &L.gamma)) return r;
+      if (int r = upload_vec(P, pre + "layer_norm.bias", co, &L.beta)) return r;
+    }
+    cin = co;
+  }
+  return SVT_OK;
+}
+
+int finalize_projection(svt_encoder* e) {
+  const svt_encoder_config& c = e->cfg;
+  const ParamMap& P = e->params;
+  const int cin = c.conv_dim[c.num_conv_layers > 0 ? c.num_conv_layers - 1 : 0];   // features-in mode: the projection reads the given features
+  if (c.feat_proj_layer_norm) {
+    if (int r = upload_vec(P, "feature_projection.layer_norm.weight", cin, &e->fp_g)) return r;
+    if (int r = upload_vec(P, "feature_projection.layer_norm.bias", cin, &e->fp_b)) return r;
+  }
+  if (int r = upload_mat(c.precision, P, "feature_projection.projection.weight", c.hidden_size, cin, &e->proj_w)) return r;
+  return upload_vec(P, "feature_projection.projection.bias", c.hidden_size, &e->proj_b);
+}
+
+// data2vec-audio: plain grouped convs "encoder.pos_conv_embed.layers.<i>.conv.{weight,bias}", (D, cg, kp) -> per group
+// (cg_out, kp*cg_in) tap-major like the single-layer form
+int finalize_pos_conv_stack(svt_encoder* e) {
+  const svt_encoder_config& c = e->cfg;
+  const ParamMap& P = e->params;
+  const int D = c.hidden_size, kp = c.pos_conv_kernel, cg = D / c.pos_conv_groups;
+  if ((int)e->pos_ws.size() != c.pos_conv_depth) { e->pos_ws.clear(); e->pos_bs.clear(); e->pos_ws.resize(c.pos_conv_depth); e->pos_bs.resize(c.pos_conv_depth); }
+  for (int i = 0; i < c.pos_conv_depth; ++i) {
+    const std::string pl = "encoder.pos_conv_embed.layers." + std::to_string(i) + ".conv.";
+    const Param* p = nullptr;
+    if (int r = need(P, pl + "weight", {D, cg, kp}, &p)) return r;
+    const std::vector<float> wt = tap_major(p->v.data(), D, cg, kp);
+    if (int r = upload_operand(storage_prec(c.precision), e->pos_ws[i], wt.data(), wt.size())) return r;
+    if (int r = upload_vec(P, pl + "bias", D, &e->pos_bs[i])) return r;
+  }
+  const std::vector<float> one((size_t)D, 1.f), zero((size_t)D, 0.f);
+  if (int r = upload_f32(e->ones, one.data(), one.size())) return r;
+  if (int r = upload_f32(e->zeros, zero.data(), zero.size())) return r;
+  e->pos_P = 0;
+  return SVT_OK;
+}
+
+// the single positional conv: weight-norm (dim=2) folded, W[:,:,j] = g[j] v[:,:,j] / ||v[:,:,j]||_F ; both spellings are accepted
+int pos_conv_weight(const svt_encoder* e, std::vector<float>* w) {
+  const svt_encoder_config& c = e->cfg;
+  const ParamMap& P = e->params;
+  const int D = c.hidden_size, kp = c.pos_conv_kernel, cg = D / c.pos_conv_groups;
+  const std::string pc = "encoder.pos_conv_embed.conv.";
+  const Param *g = find(P, pc + "parametrizations.weight.original0"), *v = find(P, pc + "parametrizations.weight.original1");
+  if (!g || !v) { g = find(P, pc + "weight_g"); v = find(P, pc + "weight_v"); }
+  if (g && v) {
+    if (g->numel() != kp || v->shape != std::vector<int64_t>({D, cg, kp})) { set_error("pos_conv weight-norm tensors have the wrong shape"); return SVT_ERR_INVALID; }
+    *w = weight_norm_fold(g->v.data(), v->v.data(), v->v.size(), kp);
+  } else if (const Param* pw = find(P, pc + "weight")) {
+    if (pw->shape != std::vector<int64_t>({D, cg, kp})) { set_error("pos_conv weight has the wrong shape"); return SVT_ERR_INVALID; }
+    *w = pw->v;
+  } else {
+    set_error("missing parameter: " + pc + "parametrizations.weight.original0/1 (or weight_g/weight_v)");
+    return SVT_ERR_KEY;
+  }
+  return SVT_OK;
+}
+
+int finalize_pos_conv(svt_encoder* e) {
+  const svt_encoder_config& c = e->cfg;
+  const ParamMap& P = e->params;
+  const int prec = storage_prec(c.precision);
+  const int D = c.hidden_size, kp = c.pos_conv_kernel, G = c.pos_conv_groups, cg = D / G;
+  std::vector<float> w;
+  if (int r = pos_conv_weight(e, &w)) return r;
+  // (D, cg, kp) -> per group (cg_out, kp*cg_in) tap-major
+  const std::vector<float> wt = tap_major(w.data(), D, cg, kp);
+  if (int r = upload_operand(prec, e->pos_w, wt.data(), wt.size())) return r;
+  const Param* bias = nullptr;
+  if (int r = need(P, "encoder.pos_conv_embed.conv.bias", {D}, &bias)) return r;
+  if (int r = upload_f32(e->pos_b, bias->v.data(), bias->v.size())) return r;
+  if (c.pos_conv_batch_norm) {
+    // y = (x - running_mean) / sqrt(running_var + 1e-5) * weight + bias   (nn.BatchNorm1d defaults, eval mode)
+    const std::string bn = "encoder.pos_conv_embed.batch_norm.";
+    const Param *bw, *bb, *bm, *bv;
+    if (int r = need(P, bn + "weight", {D}, &bw)) return r;
+    if (int r = need(P, bn + "bias", {D}, &bb)) return r;
+    if (int r = need(P, bn + "running_mean", {D}, &bm)) return r;
+    if (int r = need(P, bn + "running_var", {D}, &bv)) return r;
+    std::vector<float> sc, sh;
+    batch_norm_fold(bw->v.data(), bb->v.data(), bm->v.data(), bv->v.data(), D, &sc, &sh);
+    if (int r = upload_f32(e->pos_bn_sc, sc.data(), sc.size())) return r;
+    if (int r = upload_f32(e->pos_bn_sh, sh.data(), sh.size())) return r;
+  }
+  // Multi-frame form (throughput mode).  The grouped conv has only cg = D/G (48 / 64) output channels per group: a
+  // 64-wide product.  With Pf consecutive output frames per GEMM row the product is Pf*cg (240 / 256) wide and K grows
+  // only from kp*cg to (kp+Pf-1)*cg (+3 %, the kernel is 128 taps long): row j*cg+co of a group holds the same filter
+  // shifted by j taps.  That runs on the LDS-DMA kernel instead of the 64-wide register-staged one.
+  e->pos_P = 0;
+  const int Pf = cg > 0 ? 256 / cg : 0;
+  // (split modes, round 4: the same form in fp32 storage -- the batched one-tile split kernel, gemm_x3s_kernel with blockIdx.y = group,
+  //  replaces 512 register-staged (clip, group) products of 48 columns: 963 us of a 14.8 ms fp16x3 step)
+  if (reduced_mode(c) && Pf >= 2 && cg % 8 == 0 && ((kp + Pf - 1) * cg) % 64 == 0) {
+    std::vector<float> wp, bp;
+    posconv_multiframe(w.data(), bias->v.data(), G, cg, kp, Pf, &wp, &bp);
+    if (prec) { if (int r = upload_operand(1, e->pos_wP, wp.data(), wp.size())) return r; }
+    else { if (int r = upload_weight(c.precision, e->pos_wP, wp.data(), (size_t)G * Pf * cg, (size_t)(kp + Pf - 1) * cg)) return r; }
+    if (int r = upload_f32(e->pos_bP, bp.data(), bp.size())) return r;
+    e->pos_P = Pf;
+  }
+  return SVT_OK;
+}
+
+int finalize_layer(svt_encoder* e, int l) {
+  const svt_encoder_config& c = e->cfg;
+  const ParamMap& P = e->params;
+  const int D = c.hidden_size, F = c.intermediate_size, gp = c.precision;
+  const std::string pre = "encoder.layers." + std::to_string(l) + ".";
+  EncLayerW& L = e->layers[l];
+  // q, k and v projections packed into one (3D, D) product
+  std::vector<float> wqkv((size_t)3 * D * D), bqkv((size_t)3 * D);
+  const char* names[3] = {"q_proj", "k_proj", "v_proj"};
+  for (int i = 0; i < 3; ++i) {
+    const Param* p = nullptr;
+    if (int r = need(P, pre + "attention." + names[i] + ".weight", {D, D}, &p)) return r;
+    memcpy(wqkv.data() + (size_t)i * D * D, p->v.data(), (size_t)D * D * 4);
+    if (int r = need(P, pre + "attention." + names[i] + ".bias", {D}, &p)) return r;
+    memcpy(bqkv.data() + (size_t)i * D, p->v.data(), (size_t)D * 4);
+  }
+  if (int r = upload_weight(gp, L.wqkv, wqkv.data(), (size_t)3 * D, (size_t)D)) return r;
+  if (int r = upload_f32(L.bqkv, bqkv.data(), bqkv.size())) return r;
+  if (int r = upload_mat(gp, P, pre + "attention.out_proj.weight", D, D, &L.wo)) return r;
+  if (int r = upload_vec(P, pre + "attention.out_proj.bias", D, &L.bo)) return r;
+  if (int r = upload_vec(P, pre + "layer_norm.weight", D, &L.ln1g)) return r;
+  if (int r = upload_vec(P, pre + "layer_norm.bias", D, &L.ln1b)) return r;
+  if (int r = upload_mat(gp, P, pre + "feed_forward.intermediate_dense.weight", F, D, &L.w1)) return r;
+  if (int r = upload_vec(P, pre + "feed_forward.intermediate_dense.bias", F, &L.b1)) return r;
+  if (int r = upload_mat(gp, P, pre + "feed_forward.output_dense.weight", D, F, &L.w2)) return r;
+  if (int r = upload_vec(P, pre + "feed_forward.output_dense.bias", D, &L.b2)) return r;
+  if (int r = upload_vec(P, pre + "final_layer_norm.weight", D, &L.ln2g)) return r;
+  if (int r = upload_vec(P, pre + "final_layer_norm.bias", D, &L.ln2b)) return r;
+  if (!c.rel_pos_buckets) return SVT_OK;
+  // gate = a (b const - 1) + 2, a / b = sigmoid of the sums of rows 0-3 / 4-7 of gru_rel_pos_linear(x_head): fold the row sums
+  const int H = c.num_heads, dh = D / H;
+  const Param *gw = nullptr, *gb = nullptr, *gc = nullptr;
+  if (int r = need(P, pre + "attention.gru_rel_pos_linear.weight", {8, dh}, &gw)) return r;
+  if (int r = need(P, pre + "attention.gru_rel_pos_linear.bias", {8}, &gb)) return r;
+  if (int r = need(P, pre + "attention.gru_rel_pos_const", {1, H, 1, 1}, &gc)) return r;
+  std::vector<float> wab, bab;
+  gate_rowsum_fold(gw->v.data(), gb->v.data(), dh, &wab, &bab);
+  if (int r = upload_f32(L.g_wab, wab.data(), wab.size())) return r;
+  if (int r = upload_f32(L.g_bab, bab.data(), bab.size())) return r;
+  if (int r = upload_f32(L.g_const, gc->v.data(), gc->v.size())) return r;
+  if (l == 0) {
+    const Param* p = nullptr;
+    if (int r = need(P, pre + "attention.rel_attn_embed.weight", {c.rel_pos_buckets, H}, &p)) return r;
+    if (int r = upload_f32(e->rel_embed, p->v.data(), p->v.size())) return r;
+  }
+  return SVT_OK;
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -96,234 +303,82 @@ int svt_encoder_finalize(svt_encoder* e) {
   SVT_HIP(hipSetDevice(e->device));
   if (int r = begin_upload(e->uploaded)) return r;
   const svt_encoder_config& c = e->cfg;
-  const int prec = storage_prec(c.precision);
-  const ParamMap& P = e->params;
-  const Param* p = nullptr;
-  if ((int)e->conv.size() != c.num_conv_layers) { e->conv.clear(); e->conv.resize(c.num_conv_layers); }   // a re-upload keeps the buffers
-  int cin = c.num_conv_layers == 0 ? c.conv_dim[0] : 1;  // features-in mode: the projection reads the given features
-  for (int i = 0; i < c.num_conv_layers; ++i) {
-    const std::string pre = "feature_extractor.conv_layers." + std::to_string(i) + ".";
-    const int co = c.conv_dim[i], k = c.conv_kernel[i];
-    if (int r = need(P, pre + "conv.weight", {co, cin, k}, &p)) return r;
-    ConvLayerW& L = e->conv[i];
-    if (i == 0) {
-      if (int r = upload_f32(L.w, p->v.data(), p->v.size())) return r;
-    } else {
-      // (Cout, Cin, k) -> (Cout, k*Cin) tap-major: the implicit-GEMM row of output frame t is the
-      // contiguous channels-last slice x[t*s : t*s+k, :]
-      std::vector<float> wt((size_t)co * k * cin);
-      for (int o = 0; o < co; ++o)
-        for (int ci = 0; ci < cin; ++ci)
-          for (int j = 0; j < k; ++j) wt[((size_t)o * k + j) * cin + ci] = p->v[((size_t)o * cin + ci) * k + j];
-      if (int r = upload_weight(c.precision, L.w, wt.data(), (size_t)co, (size_t)k * cin)) return r;
-      // 16-bit modes, kernel 3: a second copy with the K axis in TAP-MINOR slab order -- slab g = tap g % 3 of channels [(g / 3) * 64, + 64)
-      // -- for gemm_p1w_kernel (GemmArgs::k_taps): the input frame two neighbouring output rows share is re-read two slabs later instead
-      // of sixteen, i.e. out of L2 (1.5 MiB per layer)
-      if (prec && k == 3 && cin % 64 == 0 && c.conv_stride[i] == 2) {
-        std::vector<float> wp((size_t)co * k * cin);
-        const int nb = cin / 64;
-        for (int o = 0; o < co; ++o)
-          for (int cb = 0; cb < nb; ++cb)
-            for (int j = 0; j < k; ++j)
-              memcpy(&wp[((size_t)o * k * nb + (size_t)cb * k + j) * 64], &wt[((size_t)o * k + j) * cin + (size_t)cb * 64], 64 * sizeof(float));
-        if (int r = upload_weight(c.precision, L.w_kperm, wp.data(), (size_t)co, (size_t)k * cin)) return r;
-      } else L.w_kperm.release();
-    }
-    if (c.conv_bias) {
-      if (int r = need(P, pre + "conv.bias", {co}, &p)) return r;
-      if (int r = upload_f32(L.bias, p->v.data(), p->v.size())) return r;
-    }
-    const bool has_norm = c.feat_extract_norm == SVT_NORM_LAYER || i == 0;
-    if (has_norm) {
-      if (int r = need(P, pre + "layer_norm.weight", {co}, &p)) return r;
-      if (int r = upload_f32(L.gamma, p->v.data(), p->v.size())) return r;
-      if (int r = need(P, pre + "layer_norm.bias", {co}, &p)) return r;
-      if (int r = upload_f32(L.beta, p->v.data(), p->v.size())) return r;
-    }
-    cin = co;
-  }
-  const int D = c.hidden_size, F = c.intermediate_size;
-  if (c.feat_proj_layer_norm) {
-    if (int r = need(P, "feature_projection.layer_norm.weight", {cin}, &p)) return r;
-    if (int r = upload_f32(e->fp_g, p->v.data(), p->v.size())) return r;
-    if (int r = need(P, "feature_projection.layer_norm.bias", {cin}, &p)) return r;
-    if (int r = upload_f32(e->fp_b, p->v.data(), p->v.size())) return r;
-  }
-  if (int r = need(P, "feature_projection.projection.weight", {D, cin}, &p)) return r;
-  if (int r = upload_weight(c.precision, e->proj_w, p->v.data(), (size_t)D, (size_t)cin)) return r;
-  if (int r = need(P, "feature_projection.projection.bias", {D}, &p)) return r;
-  if (int r = upload_f32(e->proj_b, p->v.data(), p->v.size())) return r;
-
-  if (c.pos_conv_depth > 1) {
-    // data2vec-audio: plain grouped convs "encoder.pos_conv_embed.layers.<i>.conv.{weight,bias}", (D, cg, kp) -> per group
-    // (cg_out, kp*cg_in) tap-major like the single-layer form
-    const int kp = c.pos_conv_kernel, G = c.pos_conv_groups, cg = D / G;
-    if ((int)e->pos_ws.size() != c.pos_conv_depth) { e->pos_ws.clear(); e->pos_bs.clear(); e->pos_ws.resize(c.pos_conv_depth); e->pos_bs.resize(c.pos_conv_depth); }
-    for (int i = 0; i < c.pos_conv_depth; ++i) {
-      const std::string pl = "encoder.pos_conv_embed.layers." + std::to_string(i) + ".conv.";
-      if (int r = need(P, pl + "weight", {D, cg, kp}, &p)) return r;
-      std::vector<float> wt(p->v.size());
-      for (int o = 0; o < D; ++o)
-        for (int ci = 0; ci < cg; ++ci)
-          for (int j = 0; j < kp; ++j) wt[((size_t)o * kp + j) * cg + ci] = p->v[((size_t)o * cg + ci) * kp + j];
-      if (int r = upload_operand(prec, e->pos_ws[i], wt.data(), wt.size())) return r;
-      if (int r = need(P, pl + "bias", {D}, &p)) return r;
-      if (int r = upload_f32(e->pos_bs[i], p->v.data(), p->v.size())) return r;
-    }
-    std::vector<float> one((size_t)D, 1.f), zero((size_t)D, 0.f);
-    if (int r = upload_f32(e->ones, one.data(), one.size())) return r;
-    if (int r = upload_f32(e->zeros, zero.data(), zero.size())) return r;
-    e->pos_P = 0;
-  } else
-  // positional conv: fold weight-norm (dim=2): W[:,:,j] = g[j] v[:,:,j] / ||v[:,:,j]||_F ; accept both spellings
-  {
-    const int kp = c.pos_conv_kernel, G = c.pos_conv_groups, cg = D / G;
-    const std::string pc = "encoder.pos_conv_embed.conv.";
-    std::vector<float> w((size_t)D * cg * kp);
-    const Param *g = find(P, pc + "parametrizations.weight.original0"), *v = find(P, pc + "parametrizations.weight.original1");
-    if (!g || !v) { g = find(P, pc + "weight_g"); v = find(P, pc + "weight_v"); }
-    if (g && v) {
-      if (g->numel() != kp || v->shape != std::vector<int64_t>({D, cg, kp})) { set_error("pos_conv weight-norm tensors have the wrong shape"); return SVT_ERR_INVALID; }
-      std::vector<double> nrm(kp, 0.0);
-      for (size_t i = 0; i < v->v.size(); ++i) nrm[i % kp] += (double)v->v[i] * (double)v->v[i];
-      for (int j = 0; j < kp; ++j) nrm[j] = std::sqrt(nrm[j]);
-      for (size_t i = 0; i < v->v.size(); ++i) w[i] = (float)((double)g->v[i % kp] * (double)v->v[i] / nrm[i % kp]);
-    } else if (const Param* pw = find(P, pc + "weight")) {
-      if (pw->shape != std::vector<int64_t>({D, cg, kp})) { set_error("pos_conv weight has the wrong shape"); return SVT_ERR_INVALID; }
-      w = pw->v;
-    } else {
-      set_error("missing parameter: " + pc + "parametrizations.weight.original0/1 (or weight_g/weight_v)");
-      return SVT_ERR_KEY;
-    }
-    // (D, cg, kp) -> per group (cg_out, kp*cg_in) tap-major
-    std::vector<float> wt(w.size());
-    for (int o = 0; o < D; ++o)
-      for (int ci = 0; ci < cg; ++ci)
-        for (int j = 0; j < kp; ++j) wt[((size_t)o * kp + j) * cg + ci] = w[((size_t)o * cg + ci) * kp + j];
-    if (int r = upload_operand(prec, e->pos_w, wt.data(), wt.size())) return r;
-    if (int r = need(P, pc + "bias", {D}, &p)) return r;
-    if (int r = upload_f32(e->pos_b, p->v.data(), p->v.size())) return r;
-    if (c.pos_conv_batch_norm) {
-      // y = (x - running_mean) / sqrt(running_var + 1e-5) * weight + bias   (nn.BatchNorm1d defaults, eval mode)
-      const std::string bn = "encoder.pos_conv_embed.batch_norm.";
-      const Param *bw, *bb, *bm, *bv;
-      if (int r = need(P, bn + "weight", {D}, &bw)) return r;
-      if (int r = need(P, bn + "bias", {D}, &bb)) return r;
-      if (int r = need(P, bn + "running_mean", {D}, &bm)) return r;
-      if (int r = need(P, bn + "running_var", {D}, &bv)) return r;
-      std::vector<float> sc(D), sh(D);
-      for (int i = 0; i < D; ++i) {
-        const double k = (double)bw->v[i] / std::sqrt((double)bv->v[i] + 1e-5);
-        sc[i] = (float)k;
-        sh[i] = (float)((double)bb->v[i] - (double)bm->v[i] * k);
-      }
-      if (int r = upload_f32(e->pos_bn_sc, sc.data(), sc.size())) return r;
-      if (int r = upload_f32(e->pos_bn_sh, sh.data(), sh.size())) return r;
-    }
-    // Multi-frame form (throughput mode).  The grouped conv has only cg = D/G (48 / 64) output channels per group: a
-    // 64-wide product.  With Pf consecutive output frames per GEMM row the product is Pf*cg (240 / 256) wide and K grows
-    // only from kp*cg to (kp+Pf-1)*cg (+3 %, the kernel is 128 taps long): row j*cg+co of a group holds the same filter
-    // shifted by j taps.  That runs on the LDS-DMA kernel instead of the 64-wide register-staged one.
-    e->pos_P = 0;
-    const int Pf = cg > 0 ? 256 / cg : 0;
-    // (split modes, round 4: the same form in fp32 storage -- the batched one-tile split kernel, gemm_x3s_kernel with blockIdx.y = group,
-    //  replaces 512 register-staged (clip, group) products of 48 columns: 963 us of a 14.8 ms fp16x3 step)
-    if ((prec || c.precision >= 2) && Pf >= 2 && cg % 8 == 0 && ((kp + Pf - 1) * cg) % 64 == 0) {
-      const size_t Np = (size_t)Pf * cg, Kp = (size_t)(kp + Pf - 1) * cg;
-      std::vector<float> wp((size_t)G * Np * Kp, 0.f), bp((size_t)G * Np);
-      for (int g = 0; g < G; ++g)
-        for (int j = 0; j < Pf; ++j)
-          for (int co = 0; co < cg; ++co) {
-            const int o = g * cg + co;
-            bp[(size_t)g * Np + (size_t)j * cg + co] = p->v[o];
-            float* row = wp.data() + ((size_t)g * Np + (size_t)j * cg + co) * Kp;
-            for (int k = 0; k < kp; ++k)
-              for (int ci = 0; ci < cg; ++ci) row[(size_t)(k + j) * cg + ci] = w[((size_t)o * cg + ci) * kp + k];
-          }
-      if (prec) { if (int r = upload_operand(1, e->pos_wP, wp.data(), wp.size())) return r; }
-      else { if (int r = upload_weight(c.precision, e->pos_wP, wp.data(), (size_t)G * Np, Kp)) return r; }
-      if (int r = upload_f32(e->pos_bP, bp.data(), bp.size())) return r;
-      e->pos_P = Pf;
-    }
-  }
-  if (int r = need(P, "encoder.layer_norm.weight", {D}, &p)) return r;
-  if (int r = upload_f32(e->enc_g, p->v.data(), p->v.size())) return r;
-  if (int r = need(P, "encoder.layer_norm.bias", {D}, &p)) return r;
-  if (int r = upload_f32(e->enc_b, p->v.data(), p->v.size())) return r;
-
+  if (int r = finalize_conv_stack(e)) return r;
+  if (int r = finalize_projection(e)) return r;
+  if (int r = c.pos_conv_depth > 1 ? finalize_pos_conv_stack(e) : finalize_pos_conv(e)) return r;
+  if (int r = upload_vec(e->params, "encoder.layer_norm.weight", c.hidden_size, &e->enc_g)) return r;
+  if (int r = upload_vec(e->params, "encoder.layer_norm.bias", c.hidden_size, &e->enc_b)) return r;
   if ((int)e->layers.size() != c.num_layers) { e->layers.clear(); e->layers.resize(c.num_layers); }
-  for (int l = 0; l < c.num_layers; ++l) {
-    const std::string pre = "encoder.layers." + std::to_string(l) + ".";
-    EncLayerW& L = e->layers[l];
-    std::vector<float> wqkv((size_t)3 * D * D), bqkv((size_t)3 * D);
-    const char* names[3] = {"q_proj", "k_proj", "v_proj"};
-    for (int i = 0; i < 3; ++i) {
-      if (int r = need(P, pre + "attention." + names[i] + ".weight", {D, D}, &p)) return r;
-      memcpy(wqkv.data() + (size_t)i * D * D, p->v.data(), (size_t)D * D * 4);
-      if (int r = need(P, pre + "attention." + names[i] + ".bias", {D}, &p)) return r;
-      memcpy(bqkv.data() + (size_t)i * D, p->v.data(), (size_t)D * 4);
-    }
-    if (int r = upload_weight(c.precision, L.wqkv, wqkv.data(), (size_t)3 * D, (size_t)D)) return r;
-    if (int r = upload_f32(L.bqkv, bqkv.data(), bqkv.size())) return r;
-    if (int r = need(P, pre + "attention.out_proj.weight", {D, D}, &p)) return r;
-    if (int r = upload_weight(c.precision, L.wo, p->v.data(), (size_t)D, (size_t)D)) return r;
-    if (int r = need(P, pre + "attention.out_proj.bias", {D}, &p)) return r;
-    if (int r = upload_f32(L.bo, p->v.data(), p->v.size())) return r;
-    if (int r = need(P, pre + "layer_norm.weight", {D}, &p)) return r;
-    if (int r = upload_f32(L.ln1g, p->v.data(), p->v.size())) return r;
-    if (int r = need(P, pre + "layer_norm.bias", {D}, &p)) return r;
-    if (int r = upload_f32(L.ln1b, p->v.data(), p->v.size())) return r;
-    if (int r = need(P, pre + "feed_forward.intermediate_dense.weight", {F, D}, &p)) return r;
-    if (int r = upload_weight(c.precision, L.w1, p->v.data(), (size_t)F, (size_t)D)) return r;
-    if (int r = need(P, pre + "feed_forward.intermediate_dense.bias", {F}, &p)) return r;
-    if (int r = upload_f32(L.b1, p->v.data(), p->v.size())) return r;
-    if (int r = need(P, pre + "feed_forward.output_dense.weight", {D, F}, &p)) return r;
-    if (int r = upload_weight(c.precision, L.w2, p->v.data(), (size_t)D, (size_t)F)) return r;
-    if (int r = need(P, pre + "feed_forward.output_dense.bias", {D}, &p)) return r;
-    if (int r = upload_f32(L.b2, p->v.data(), p->v.size())) return r;
-    if (int r = need(P, pre + "final_layer_norm.weight", {D}, &p)) return r;
-    if (int r = upload_f32(L.ln2g, p->v.data(), p->v.size())) return r;
-    if (int r = need(P, pre + "final_layer_norm.bias", {D}, &p)) return r;
-    if (int r = upload_f32(L.ln2b, p->v.data(), p->v.size())) return r;
-    if (c.rel_pos_buckets) {
-      // gate = a (b const - 1) + 2, a / b = sigmoid of the sums of rows 0-3 / 4-7 of gru_rel_pos_linear(x_head): fold the row sums
-      const int Hh = c.num_heads, dhh = D / Hh;
-      const Param *gw = nullptr, *gb = nullptr, *gc = nullptr;
-      if (int r = need(P, pre + "attention.gru_rel_pos_linear.weight", {8, dhh}, &gw)) return r;
-      if (int r = need(P, pre + "attention.gru_rel_pos_linear.bias", {8}, &gb)) return r;
-      if (int r = need(P, pre + "attention.gru_rel_pos_const", {1, Hh, 1, 1}, &gc)) return r;
-      std::vector<float> wab((size_t)2 * dhh, 0.f), bab(2, 0.f);
-      for (int j = 0; j < 8; ++j) {
-        for (int d = 0; d < dhh; ++d) wab[(size_t)(j / 4) * dhh + d] += gw->v[(size_t)j * dhh + d];
-        bab[j / 4] += gb->v[j];
-      }
-      if (int r = upload_f32(L.g_wab, wab.data(), wab.size())) return r;
-      if (int r = upload_f32(L.g_bab, bab.data(), bab.size())) return r;
-      if (int r = upload_f32(L.g_const, gc->v.data(), gc->v.size())) return r;
-      if (l == 0) {
-        if (int r = need(P, pre + "attention.rel_attn_embed.weight", {c.rel_pos_buckets, Hh}, &p)) return r;
-        if (int r = upload_f32(e->rel_embed, p->v.data(), p->v.size())) return r;
-      }
-    }
-  }
+  for (int l = 0; l < c.num_layers; ++l)
+    if (int r = finalize_layer(e, l)) return r;
   SVT_HIP(hipDeviceSynchronize());
   e->finalized = true;
   return SVT_OK;
 }
 
 int64_t svt_encoder_num_frames(const svt_encoder* e, int64_t n_samples) {
-  if (!e) return -1;
-  int64_t t = n_samples;
-  for (int i = 0; i < e->cfg.num_conv_layers; ++i) {
-    if (t < e->cfg.conv_kernel[i]) return 0;
-    t = (t - e->cfg.conv_kernel[i]) / e->cfg.conv_stride[i] + 1;
-  }
-  return t;
+  return e ? conv_frames(e->cfg, n_samples) : -1;
 }
 
 }  // extern "C"
 
+// ---------------------------------------------------------------- plan and workspace of a forward
 namespace {
+
+// FFN-2 of a small batch splits K four ways over workgroups and leaves the sum to the LayerNorm behind it (gemm_skinny.hip, ksplit;
+// svt_debug_set key 36 = 0 switches it off): up to this many rows (8 utterances of 5 s)
+const size_t kKsplitMaxRows = 2048;
+
+// Everything a forward of (encoder, B, L) decides from the configuration alone, computed once: carve_encoder, svt_debug_encoder_layout
+// and every stage of the forward read it.  (The pair-row decisions also need buffer addresses: choose_pair_rows, after the carve.)
+struct EncPlan {
+  int B = 0;
+  int64_t L = 0;
+  int64_t frames[SVT_MAX_CONV_LAYERS] = {};   // output frames of conv layer i
+  int64_t t1 = 1;          // frames of conv layer 0 (1 in features-in mode)
+  int64_t T = 0, rows = 0; // encoder frames per clip (features-in mode: L), B * T
+  int C = 0;               // width of the feature projection's input
+  int D = 0, F = 0, H = 0, dh = 0;
+  int sp = 0;              // storage type of activations / weights (storage_prec)
+  int gp = 0;              // engine of the dense products (launch_gemm)
+  bool reduced = false;    // reduced_mode()
+  bool rel = false;        // WavLM relative position bias
+  bool flash = false;      // fused 16-bit attention: no score matrix
+  bool planes = false;     // fused split attention: no score matrix, the QKV projection's epilogue writes the (hi, lo) planes it reads
+  int attn_Tp = 0;         // padded key length of the score / V^T buffers
+  int Pf = 0;              // frames per row of the multi-frame positional conv the encoder holds (0: none)
+  int64_t pos_Tq = 0;      // ... its GEMM rows per clip
+  int64_t pos_Tp = 0;      // frames per clip the gathered positional-conv input is carved for: pos_Tq * Pf + kernel (multi-frame), else T + kernel
+  bool pos_multi = false;  // this batch has enough rows for the multi-frame form
+  bool hilo = false;       // post-LN encoder with the residual stream as a bf16 (hi, lo) pair
+  bool ksplit_ws = false;  // few enough rows for the K-split FFN-2: its partial products get workspace
+};
+
+// false: the waveform is shorter than the receptive field
+bool plan_encoder(const svt_encoder* e, int B, int64_t L, EncPlan* out) {
+  const svt_encoder_config& c = e->cfg;
+  EncPlan p;
+  p.B = B; p.L = L;
+  p.T = conv_frames(c, L, p.frames);
+  if (p.T < 1) return false;
+  p.rows = (int64_t)B * p.T;
+  p.t1 = c.num_conv_layers > 0 ? p.frames[0] : 1;
+  p.C = c.conv_dim[c.num_conv_layers > 0 ? c.num_conv_layers - 1 : 0];
+  p.D = c.hidden_size; p.F = c.intermediate_size; p.H = c.num_heads; p.dh = p.D / p.H;
+  p.sp = storage_prec(c.precision); p.gp = c.precision; p.reduced = reduced_mode(c);
+  p.rel = c.rel_pos_buckets > 0;
+  p.flash = use_flash(p.sp, p.dh, p.rel, p.T);
+  p.planes = p.gp >= 2 && flash_attention_x3_ok(p.dh) && !p.rel;
+  p.attn_Tp = attn_tp(p.sp, p.dh, (int)p.T, p.rel);
+  p.Pf = e->pos_P;
+  p.pos_Tq = p.Pf ? (p.T + p.Pf - 1) / p.Pf : 0;
+  p.pos_Tp = p.Pf ? p.pos_Tq * p.Pf + c.pos_conv_kernel : p.T + c.pos_conv_kernel;
+  p.pos_multi = p.Pf && (int64_t)B * p.pos_Tq >= 128;
+  p.hilo = !c.stable_layer_norm && p.sp && layernorm_hilo_ok(p.D) && c.num_layers > 0;
+  p.ksplit_ws = p.sp && (size_t)p.rows <= kKsplitMaxRows;
+  *out = p;
+  return true;
+}
 
 struct EncWs {
   double* mom;      // [0..1] wav, [2..3] out, [4 ..] window moments B*65
@@ -353,75 +408,55 @@ struct EncWs {
   size_t total;
 };
 
-// FFN-2 of a small batch splits K four ways over workgroups and leaves the sum to the LayerNorm behind it (gemm_skinny.hip, ksplit;
-// svt_debug_set key 36 = 0 switches it off): up to this many rows (8 utterances of 5 s)
-static const size_t kKsplitMaxRows = 2048;
-
-EncWs carve_encoder(const svt_encoder* e, int B, int64_t L, void* base) {
+EncWs carve_encoder(const svt_encoder* e, const EncPlan& p, void* base) {
   const svt_encoder_config& c = e->cfg;
-  const int sp = storage_prec(c.precision);
-  const size_t es = esize(sp);
+  const size_t es = esize(p.sp);
+  const size_t B = (size_t)p.B, rows = (size_t)p.rows, T = (size_t)p.T, D = (size_t)p.D, H = (size_t)p.H;
   Carver cv(base);
   EncWs w;
   // 2 x (sum, sumsq) per norm group (<= B groups) + conv0 window moments, then the scratch of the three ordered sums (tickets + per-workgroup
   // partials: stats.hip, last_workgroup); the whole region is zeroed at the start of every forward (the tickets must be)
-  {
-    const int64_t t1 = c.num_conv_layers > 0 ? (L - c.conv_kernel[0]) / c.conv_stride[0] + 1 : 1;
-    w.mom_scr[0] = align_up((4 * (size_t)B + (size_t)B * 65) * sizeof(double));
-    w.mom_scr[1] = w.mom_scr[0] + align_up(moments_scratch_bytes(B));
-    w.mom_scr[2] = w.mom_scr[1] + align_up(moments_scratch_bytes(B));
-    w.mom_scr[3] = w.mom_scr[2] + align_up(conv0_window_moments_scratch_bytes(B, t1 > 0 ? t1 : 1));
-    w.mom_zero = w.mom_scr[3] + 256;   // ... up to and including the fused tail's ticket: what a forward zeroes
-    int64_t t = L;
-    for (int i = 0; i < c.num_conv_layers; ++i) t = (t - c.conv_kernel[i]) / c.conv_stride[i] + 1;
-    w.mom_bytes = w.mom_scr[3] + align_up(head_scratch_bytes((int64_t)B * (t > 0 ? t : 1), B));
-  }
+  w.mom_scr[0] = align_up((4 * B + B * 65) * sizeof(double));
+  w.mom_scr[1] = w.mom_scr[0] + align_up(moments_scratch_bytes(p.B));
+  w.mom_scr[2] = w.mom_scr[1] + align_up(moments_scratch_bytes(p.B));
+  w.mom_scr[3] = w.mom_scr[2] + align_up(conv0_window_moments_scratch_bytes(p.B, p.t1));
+  w.mom_zero = w.mom_scr[3] + 256;   // ... up to and including the fused tail's ticket: what a forward zeroes
+  w.mom_bytes = w.mom_scr[3] + align_up(head_scratch_bytes(p.rows, p.B));
   w.mom = (double*)cv.take(w.mom_bytes);
-  w.coef = (float*)cv.take((size_t)B * c.conv_dim[0] * 11 * 4);
-  w.c0tab = (sp || c.precision >= 2) ? cv.take(conv0_mfma_table_bytes(B)) : nullptr;
+  w.coef = (float*)cv.take(B * c.conv_dim[0] * 11 * 4);
+  w.c0tab = p.reduced ? cv.take(conv0_mfma_table_bytes(p.B)) : nullptr;
   size_t max_act = 0, max_f = 0;
-  int64_t t = L;
   for (int i = 0; i < c.num_conv_layers; ++i) {
-    t = (t - c.conv_kernel[i]) / c.conv_stride[i] + 1;
-    const size_t n = (size_t)B * t * c.conv_dim[i];
+    const size_t n = B * p.frames[i] * c.conv_dim[i];
     if (n * es > max_act) max_act = n * es;
     if (i > 0 && n * 4 > max_f) max_f = n * 4;
   }
-  const int64_t T = t;
-  if (c.num_conv_layers == 0) max_act = (size_t)B * T * c.conv_dim[0] * es;
+  if (c.num_conv_layers == 0) max_act = rows * c.conv_dim[0] * es;
   w.act[0] = cv.take(max_act);
   w.act[1] = cv.take(max_act);
   w.convF = c.feat_extract_norm == SVT_NORM_LAYER ? (float*)cv.take(max_f) : nullptr;
-  const int D = c.hidden_size, F = c.intermediate_size, H = c.num_heads, dh = D / H;
-  const size_t rows = (size_t)B * T;
-  const int Tp = attn_tp(sp, dh, (int)T, c.rel_pos_buckets > 0);
-  const bool flash = use_flash(sp, dh, c.rel_pos_buckets > 0, (int64_t)T);
-  w.xln = cv.take(rows * c.conv_dim[c.num_conv_layers > 0 ? c.num_conv_layers - 1 : 0] * es);
+  w.xln = cv.take(rows * p.C * es);
   w.hF = (float*)cv.take(rows * D * 4);
   w.preF = (float*)cv.take(rows * D * 4);
   w.xb = cv.take(rows * D * es);
-  // split modes: xb holds the layer input as pair rows (the products' operand) and xF the fp32 residual stream beside it
-  w.xF = (sp || c.precision >= 2) ? (float*)cv.take(rows * D * 4) : (float*)w.xb;
-  w.xlo = sp ? cv.take(rows * D * 2) : nullptr;  // low half of the (hi, lo) bf16 residual stream (post-LN, bf16 mode)
-  {
-    const int Pf = e->pos_P;
-    const size_t Tq = Pf ? (T + Pf - 1) / Pf : 0;
-    const size_t Tp = Pf ? Tq * Pf + c.pos_conv_kernel : (size_t)(T + c.pos_conv_kernel);
-    w.posg = cv.take((size_t)B * Tp * D * es);
-    w.posy = Pf ? cv.take((size_t)B * Tq * Pf * D * es) : nullptr;
-  }
+  // reduced modes: xb holds the layer input in the products' operand form and xF the fp32 residual stream beside it; in plain fp32 they
+  // are one buffer (the split modes without pair rows use xb alone all the same: choose_pair_rows)
+  w.xF = p.reduced ? (float*)cv.take(rows * D * 4) : (float*)w.xb;
+  w.xlo = p.sp ? cv.take(rows * D * 2) : nullptr;  // low half of the (hi, lo) bf16 residual stream (post-LN, bf16 mode)
+  w.posg = cv.take(B * p.pos_Tp * D * es);
+  w.posy = p.Pf ? cv.take(B * p.pos_Tq * p.Pf * D * es) : nullptr;
   w.qkv = cv.take(rows * 3 * D * es);
-  const bool flash3 = c.precision >= 2 && flash_attention_x3_ok(dh) && !c.rel_pos_buckets;
-  w.ab.S = (flash || flash3) ? nullptr : (float*)cv.take((size_t)B * H * T * Tp * 4);
-  w.ab.P = (flash || flash3) ? nullptr : cv.take((size_t)B * H * T * Tp * es);
-  w.ab.Vt = cv.take((size_t)B * H * dh * Tp * es);
-  w.ab.pl_qkv = (c.precision >= 2 && flash_attention_x3_ok(dh) && !c.rel_pos_buckets) ? cv.take(rows * 3 * D * 4) : nullptr;
+  const bool scores = !(p.flash || p.planes);
+  w.ab.S = scores ? (float*)cv.take(B * H * T * p.attn_Tp * 4) : nullptr;
+  w.ab.P = scores ? cv.take(B * H * T * p.attn_Tp * es) : nullptr;
+  w.ab.Vt = cv.take(B * H * p.dh * p.attn_Tp * es);
+  w.ab.pl_qkv = p.planes ? cv.take(rows * 3 * D * 4) : nullptr;
   w.attn_o = cv.take(rows * D * es);
-  w.ffn = cv.take(rows * F * es);
-  w.gate = c.rel_pos_buckets ? (float*)cv.take((size_t)B * H * T * 4) : nullptr;
-  w.relpb = c.rel_pos_buckets ? (float*)cv.take((size_t)H * (2 * T - 1) * 4) : nullptr;
+  w.ffn = cv.take(rows * p.F * es);
+  w.gate = p.rel ? (float*)cv.take(B * H * T * 4) : nullptr;
+  w.relpb = p.rel ? (float*)cv.take(H * (2 * T - 1) * 4) : nullptr;
   w.dots = (float*)cv.take(rows * 32 * 4);
-  w.ksplit = (sp && rows <= kKsplitMaxRows) ? (float*)cv.take((size_t)4 * rows * D * 4) : nullptr;
+  w.ksplit = p.ksplit_ws ? (float*)cv.take((size_t)4 * rows * D * 4) : nullptr;
   w.total = cv.off;
   return w;
 }
@@ -442,9 +477,10 @@ extern "C" {
 
 int svt_debug_encoder_layout(const svt_encoder* e, int32_t batch, int64_t n_samples, int64_t* offsets, int n) {
   if (!e || batch < 1 || !offsets || n < 1) { set_error("svt_debug_encoder_layout: bad argument"); return SVT_ERR_INVALID; }
-  if (svt_encoder_num_frames(e, n_samples) < 1) { set_error("waveform shorter than the receptive field"); return SVT_ERR_INVALID; }
+  EncPlan p;
+  if (!plan_encoder(e, batch, n_samples, &p)) { set_error("waveform shorter than the receptive field"); return SVT_ERR_INVALID; }
   char* const fake = (char*)(uintptr_t)(1ull << 40);   // never dereferenced: carve_encoder only adds offsets to it
-  const EncWs w = carve_encoder(e, batch, n_samples, fake);
+  const EncWs w = carve_encoder(e, p, fake);
   const void* r[24] = {w.mom, w.coef, w.c0tab, w.act[0], w.act[1], w.convF, w.xln, w.hF, w.preF, w.xb, w.xF, w.xlo, w.posg, w.posy, w.qkv,
                        w.ab.S, w.ab.P, w.ab.Vt, w.ab.pl_qkv, w.attn_o, w.ffn, w.gate, w.relpb, w.dots};
   int k = 0;
@@ -455,14 +491,558 @@ int svt_debug_encoder_layout(const svt_encoder* e, int32_t batch, int64_t n_samp
 
 int64_t svt_encoder_workspace_bytes(const svt_encoder* e, int32_t batch, int64_t n_samples) {
   if (!e || batch < 1) { set_error("workspace_bytes: bad argument"); return -1; }
-  if (svt_encoder_num_frames(e, n_samples) < 1) { set_error("waveform shorter than the receptive field"); return -1; }
-  return (int64_t)carve_encoder(e, batch, n_samples, nullptr).total;
+  EncPlan p;
+  if (!plan_encoder(e, batch, n_samples, &p)) { set_error("waveform shorter than the receptive field"); return -1; }
+  return (int64_t)carve_encoder(e, p, nullptr).total;
 }
 
 }  // extern "C"
 
-static int encoder_forward_impl(svt_encoder* e, const float* wav, int32_t B, int64_t L, const TailSpec& tail, void* workspace,
-                                size_t workspace_bytes, void* stream, int32_t clips_per_norm_group);
+// ---------------------------------------------------------------- the forward, stage by stage
+namespace {
+
+struct ReduceCtx { const svt_encoder* e; double* mom; hipStream_t s; };
+// "global-batch-equivalent" norms (optional): the batch is a shard of a larger one; the caller's function sums the
+// (sum, sum of squares) pair over the ranks -- 16 bytes per norm -- and the statistics are then those of the whole global batch
+int reduce_now(void* a) {
+  ReduceCtx* rc = (ReduceCtx*)a;
+  if (rc->e->reduce_fn(rc->mom, 2, (void*)rc->s, rc->e->reduce_user)) { set_error("encoder_forward: the norm-reduce callback reported an error"); return SVT_ERR_INVALID; }
+  return 0;
+}
+
+// one forward in flight: what every stage reads
+struct EncRun {
+  const svt_encoder* e;
+  const svt_encoder_config& c;
+  const EncPlan& p;
+  EncWs w;
+  hipStream_t s;
+  // the wrapper's two whole-tensor layer norms run over groups of `cpg` consecutive clips: cpg = B is the reference on a
+  // batch (and per device shard under DataParallel / DDP), cpg = 1 makes a batch of B clips equal to B batch-1 forwards --
+  // the reference's evaluation loop (train_audio_ssl.py:90 asserts batch 1) without its one-utterance-at-a-time cost
+  int cpg = 0, groups = 1;
+  // input_statistics
+  double* wav_mom = nullptr;   // 2 per group, or null without the input norm
+  double* out_mom = nullptr;
+  double* win_mom = nullptr;   // conv layer 0 window moments
+  int64_t n_wav = 0;           // samples behind one pair of wav_mom
+  bool global_norm = false;
+  ReduceCtx rctx{nullptr, nullptr, nullptr};
+  // choose_pair_rows
+  int pk_front = 0, pk_enc = 0;  // pair rows (kind of the pieces: 2 = bf16, 3 = fp16; 0 = none) for conv 1..n-1 + the feature projection / the encoder layers
+  float* resid = nullptr;      // the fp32 residual stream of the encoder layers: w.xF, or w.xb where the layer input is itself fp32
+};
+
+LnArgs ln_f32(const EncRun& x, const void* in, int64_t rows, int D, const DevBuf& gamma, const DevBuf& beta, float eps) {
+  LnArgs a;
+  a.prec = x.p.sp; a.x = in; a.rows = rows; a.D = D; a.gamma = gamma.as<float>(); a.beta = beta.as<float>(); a.eps = eps;
+  return a;
+}
+
+// the checks that need the batch: norm groups
+int check_norm_groups(EncRun& x, int32_t clips_per_norm_group) {
+  const svt_encoder_config& c = x.c;
+  x.cpg = clips_per_norm_group > 0 ? clips_per_norm_group : x.p.B;
+  if (x.p.B % x.cpg) { set_error("encoder_forward: batch must be a multiple of clips_per_norm_group"); return SVT_ERR_INVALID; }
+  x.groups = x.p.B / x.cpg;
+  if (x.groups > 1 && c.num_conv_layers > 0 && (x.p.L & 3)) {
+    set_error("encoder_forward: norm groups need a waveform length that is a multiple of 4 samples");
+    return SVT_ERR_INVALID;
+  }
+  if (x.groups > 1 && c.num_conv_layers == 0 && c.normalize_wav) {
+    set_error("encoder_forward: features-in mode has no input norm to group");
+    return SVT_ERR_INVALID;
+  }
+  return SVT_OK;
+}
+
+// zeroes the statistics region, takes the waveform moments and (optionally) reduces them over the ranks
+int input_statistics(EncRun& x, const float* wav) {
+  const svt_encoder_config& c = x.c;
+  const EncWs& w = x.w;
+  const size_t B = (size_t)x.p.B;
+  if (launch_zero_bytes(w.mom, w.mom_zero, x.s)) return SVT_ERR_HIP;   // (a kernel, not a memset node: see encoder_ops.hip)
+  x.wav_mom = c.normalize_wav ? w.mom : nullptr;
+  x.out_mom = w.mom + 2 * B;
+  x.win_mom = w.mom + 4 * B;
+  x.n_wav = (int64_t)x.cpg * x.p.L;
+  if (c.normalize_wav)
+    if (int r = launch_moments(wav, x.n_wav, x.wav_mom, (char*)w.mom + w.mom_scr[0], x.p.B, x.s, x.groups)) return r;
+  x.rctx = ReduceCtx{x.e, nullptr, x.s};
+  x.global_norm = x.e->reduce_fn != nullptr;
+  if (x.global_norm) {
+    if (x.groups != 1) { set_error("encoder_forward: the cross-rank norm reduction applies to whole-batch norms (clips_per_norm_group = 0)"); return SVT_ERR_INVALID; }
+    if (x.e->reduce_global_clips < x.p.B) { set_error("encoder_forward: global_clips of the norm reduction is smaller than this batch"); return SVT_ERR_INVALID; }
+    if (c.normalize_wav) {
+      x.rctx.mom = x.wav_mom;
+      if (int r = reduce_now(&x.rctx)) return r;
+      x.n_wav = x.e->reduce_global_clips * x.p.L;
+    }
+  }
+  return SVT_OK;
+}
+
+bool x3q_fits(const void* A, int M, int N, int K, int a_rpb, long a_bstride, long a_rstride, const void* Wp, int c_pairs, long ldc) {
+  GemmArgs g;
+  g.A = A; g.W = Wp; g.C = const_cast<void*>(A); g.M = M; g.N = N; g.K = K; g.a_rpb = a_rpb; g.a_bstride = a_bstride; g.a_rstride = a_rstride;
+  g.ldw = K; g.ldc = ldc; g.a_pairs = 1; g.c_pairs = c_pairs;
+  return gemm_x3q_eligible(g);
+}
+
+// Split modes: which products take PAIR ROWS (gemm_x3q.hip: operands cut by their producers).  front = conv 1..n-1 and the feature
+// projection, enc = the four products of every encoder layer; a section switches as a whole, and only when every product in it fits
+// gemm_x3q_kernel's contract, alignment of its buffers included (otherwise its activations stay fp32 and the products cut them).
+void choose_pair_rows(EncRun& x) {
+  const svt_encoder_config& c = x.c;
+  const EncPlan& p = x.p;
+  const EncWs& w = x.w;
+  const svt_encoder* e = x.e;
+  const int B = p.B, D = p.D, F = p.F, rows = (int)p.rows;
+  const int pk_mode = (p.gp >= 2 && g_x3_pairs && g_gemm_x3) ? p.gp : 0;
+  bool front = pk_mode != 0 && c.num_conv_layers >= 2 && c.conv_dim[0] % 32 == 0 && c.conv_dim[0] <= 512 && c.conv_stride[0] <= 5;
+  for (int i = 1; i < c.num_conv_layers && front; ++i) {
+    const int cin = c.conv_dim[i - 1], co = c.conv_dim[i], k = c.conv_kernel[i], st = c.conv_stride[i];
+    const int64_t ti = p.frames[i - 1], to = p.frames[i];
+    front = (int64_t)B * to <= 2147483647LL &&
+            x3q_fits(w.act[0], (int)((int64_t)B * to), co, k * cin, (int)to, ti * cin, (long)st * cin, e->conv[i].w.p, 1, co) &&
+            (c.feat_extract_norm != SVT_NORM_LAYER || co == 512 || co == 768 || co == 1024);
+  }
+  front = front && x3q_fits(w.xln, rows, D, p.C, rows, 0, p.C, e->proj_w.p, 0, D) &&
+          (!c.feat_proj_layer_norm || p.C == 512 || p.C == 768 || p.C == 1024);
+  x.pk_front = front ? pk_mode : 0;
+  // encoder layers on pair rows: the layer input (LayerNorm output), the attention output and the FFN intermediate are written as
+  // pair rows by their producers; the residual stream stays fp32 beside them (w.xF)
+  const bool enc = pk_mode != 0 && p.planes && c.num_layers > 0 && (D == 512 || D == 768 || D == 1024) && p.dh % 32 == 0 &&
+                   x3q_fits(w.xb, rows, 3 * D, D, rows, 0, D, e->layers[0].wqkv.p, 0, 3 * D) &&
+                   x3q_fits(w.attn_o, rows, D, D, rows, 0, D, e->layers[0].wo.p, 0, D) &&
+                   x3q_fits(w.xb, rows, F, D, rows, 0, D, e->layers[0].w1.p, 1, F) &&
+                   x3q_fits(w.ffn, rows, D, F, rows, 0, F, e->layers[0].w2.p, 0, D);
+  x.pk_enc = enc ? pk_mode : 0;
+  // fp32 storage without pair rows: the layer input IS the residual stream (one buffer, w.xb), also where the carve gave a split
+  // mode a w.xF of its own (that one then only serves as the stacked positional conv's scratch)
+  x.resid = (!p.sp && !x.pk_enc) ? (float*)w.xb : w.xF;
+}
+
+// conv layer 0 with its norm (group or layer) and GELU, from the waveform into w.act[0] (channels-last)
+int conv_layer0(const EncRun& x, const float* wav) {
+  const svt_encoder_config& c = x.c;
+  const EncWs& w = x.w;
+  const int B = x.p.B, k = c.conv_kernel[0], st = c.conv_stride[0], C0 = c.conv_dim[0], prec = x.p.sp;
+  const int64_t L = x.p.L, t1 = x.p.t1;
+  const ConvLayerW& c0 = x.e->conv[0];
+  const float* b0 = c.conv_bias ? c0.bias.as<float>() : nullptr;
+  const bool mfma = conv0_mfma_ok(prec, x.pk_front, k, st, C0) && w.c0tab;
+  if (c.feat_extract_norm == SVT_NORM_GROUP) {
+    if (int r = launch_conv0_window_moments(wav, B, L, k, st, t1, x.win_mom, (char*)w.mom + w.mom_scr[2], x.s)) return r;
+    if (int r = launch_conv0_group_coef(x.wav_mom, x.n_wav, x.win_mom, B, t1, C0, k, c0.w.as<float>(), b0, c0.gamma.as<float>(),
+                                        c0.beta.as<float>(), 1e-5f, 1e-5f, w.coef, x.s, x.cpg)) return r;
+    if (mfma) return launch_conv0_mfma_group(wav, B, L, st, t1, w.coef, w.c0tab, w.act[0], x.s, x.pk_front);
+    return launch_conv0_group_apply(prec, wav, B, L, k, st, t1, C0, w.coef, w.act[0], x.s, x.pk_front);
+  }
+  if (mfma)
+    return launch_conv0_mfma_layer(wav, B, L, st, t1, x.wav_mom, x.n_wav, 1e-5f, c0.w.as<float>(), b0, c0.gamma.as<float>(),
+                                   c0.beta.as<float>(), 1e-5f, w.c0tab, w.act[0], x.s, x.cpg, x.pk_front);
+  return launch_conv0_layer(prec, wav, B, L, k, st, t1, C0, x.wav_mom, x.n_wav, 1e-5f, c0.w.as<float>(), b0, c0.gamma.as<float>(),
+                            c0.beta.as<float>(), 1e-5f, w.act[0], x.s, x.cpg, x.pk_front);
+}
+
+// conv layers 1..n-1 as implicit GEMMs between w.act[0] and w.act[1]; *cur = the buffer the last one wrote
+int conv_stack(const EncRun& x, int* cur_out) {
+  const svt_encoder_config& c = x.c;
+  const EncWs& w = x.w;
+  const int prec = x.p.sp, gp = x.p.gp, pk = x.pk_front;
+  const bool layer_norm = c.feat_extract_norm == SVT_NORM_LAYER;
+  int cur = 0;
+  for (int i = 1; i < c.num_conv_layers; ++i) {
+    const int cin = c.conv_dim[i - 1], co = c.conv_dim[i], k = c.conv_kernel[i], st = c.conv_stride[i];
+    const int64_t tin = x.p.frames[i - 1], tout = x.p.frames[i], rows = (int64_t)x.p.B * tout;
+    const ConvLayerW& Lw = x.e->conv[i];
+    void* const out = w.act[cur ^ 1];
+    if (rows > 2147483647LL) { set_error("encoder_forward: batch*frames exceeds 2^31"); return SVT_ERR_INVALID; }
+    GemmArgs g;
+    g.A = w.act[cur]; g.W = Lw.w.p;
+    g.M = (int)rows; g.N = co; g.K = k * cin;
+    g.a_rpb = (int)tout; g.a_bstride = tin * cin; g.a_rstride = (long)st * cin;
+    g.ldw = g.K; g.ldc = co;
+    if (Lw.w_kperm.p) { g.W_kperm = Lw.w_kperm.p; g.kperm_taps = k; g.kperm_cin = cin; }
+    g.bias = c.conv_bias ? Lw.bias.as<float>() : nullptr;
+    // pair rows: this layer reads them; it writes them too unless the feature projection's LayerNorm (an fp32 reader) comes next
+    g.a_pairs = pk ? 1 : 0;
+    const bool pairs_out = pk && !(i + 1 == c.num_conv_layers && c.feat_proj_layer_norm);
+    LnArgs n = ln_f32(x, w.convF, rows, co, Lw.gamma, Lw.beta, 1e-5f);
+    n.gelu = 1;
+    if (pk && layer_norm) {
+      g.C = w.convF; g.out_f32 = 1; g.act = ACT_NONE;
+      if (int r = launch_gemm(gp, g, x.s)) return r;
+      (pairs_out ? n.yP : n.yT) = out; n.pair_kind = pk;
+      if (int r = launch_layernorm(n, x.s)) return r;
+    } else if (pk) {
+      g.C = out; g.act = ACT_GELU; g.out_f32 = 1; g.c_pairs = pairs_out ? 1 : 0;
+      if (int r = launch_gemm(gp, g, x.s)) return r;
+    } else if (layer_norm && prec && co == 512 && g_conv_ln_bf16) {
+      // throughput mode: the conv output goes to HBM once, in the operand type, and is normalised in place (a wave owns a
+      // row: it reads all of it before it writes) -- the fp32 round trip below moves 3x the bytes (conv1 at 64 x 10 s:
+      // 2.1 GB written + 2.1 GB read + 1.05 GB written)
+      g.C = out; g.out_f32 = 0; g.act = ACT_NONE;
+      if (int r = launch_gemm(gp, g, x.s)) return r;
+      n.x = out; n.x_is_f32 = 0; n.yT = out;
+      if (int r = launch_layernorm(n, x.s)) return r;
+    } else if (layer_norm) {
+      g.C = w.convF; g.out_f32 = 1; g.act = ACT_NONE;
+      if (int r = launch_gemm(gp, g, x.s)) return r;
+      n.yT = out;
+      if (int r = launch_layernorm(n, x.s)) return r;
+    } else {
+      g.C = out; g.act = ACT_GELU;
+      if (int r = launch_gemm(gp, g, x.s)) return r;
+    }
+    cur ^= 1;
+  }
+  *cur_out = cur;
+  return SVT_OK;
+}
+
+// optional LayerNorm over the conv channels, then the projection to the hidden size: w.act[cur] -> w.hF (fp32)
+int feature_projection(const EncRun& x, int cur) {
+  const svt_encoder_config& c = x.c;
+  const EncWs& w = x.w;
+  const int C = x.p.C, D = x.p.D, rows = (int)x.p.rows, pk = x.pk_front;
+  const void* proj_in = w.act[cur];
+  if (c.feat_proj_layer_norm) {
+    LnArgs n = ln_f32(x, w.act[cur], rows, C, x.e->fp_g, x.e->fp_b, c.layer_norm_eps);
+    n.x_is_f32 = x.p.sp ? 0 : 1;
+    (pk ? n.yP : n.yT) = w.xln; n.pair_kind = pk;
+    if (int r = launch_layernorm(n, x.s)) return r;
+    proj_in = w.xln;
+  }
+  GemmArgs g;
+  g.A = proj_in; g.W = x.e->proj_w.p; g.C = w.hF; g.bias = x.e->proj_b.as<float>();
+  g.M = rows; g.N = D; g.K = C; g.a_rpb = rows; g.a_rstride = C; g.ldw = C; g.ldc = D; g.out_f32 = 1;
+  g.a_pairs = pk ? 1 : 0;
+  return launch_gemm(x.p.gp, g, x.s);
+}
+
+// the grouped conv over the gathered input w.posg as one batched product per (clip, group): kp*cg -> cg columns of C (fp32, row stride D)
+GemmArgs posconv_gemm(const EncRun& x, const DevBuf& W, const DevBuf& bias) {
+  const int T = (int)x.p.T, D = x.p.D, G = x.c.pos_conv_groups, cg = D / G, kp = x.c.pos_conv_kernel;
+  GemmArgs g;
+  g.A = x.w.posg; g.W = W.p; g.C = x.w.preF; g.bias = bias.as<float>();
+  g.M = T; g.N = cg; g.K = kp * cg;
+  g.a_rpb = T; g.a_rstride = cg;
+  g.ldw = g.K; g.ldc = D;
+  g.nz = x.p.B * G; g.nz2 = G;
+  g.a_z1 = (long)G * (T + kp) * cg; g.a_z2 = (long)(T + kp) * cg;
+  g.w_z1 = 0; g.w_z2 = (long)cg * g.K;
+  g.c_z1 = (long)T * D; g.c_z2 = cg; g.bias_z2 = cg;
+  g.out_f32 = 1;
+  return g;
+}
+
+// positional conv embedding, w.hF -> w.preF: pre = h + gelu(grouped_conv(h) + b), in one of three forms
+int positional_conv(const EncRun& x) {
+  const svt_encoder_config& c = x.c;
+  const svt_encoder* e = x.e;
+  const EncWs& w = x.w;
+  const int prec = x.p.sp, gp = x.p.gp, B = x.p.B, T = (int)x.p.T, D = x.p.D, kp = c.pos_conv_kernel, G = c.pos_conv_groups, cg = D / G;
+  const float* bn_sc = c.pos_conv_batch_norm ? e->pos_bn_sc.as<float>() : nullptr;
+  const float* bn_sh = c.pos_conv_batch_norm ? e->pos_bn_sh.as<float>() : nullptr;
+  if (c.pos_conv_depth > 1) {
+    // data2vec-audio: pos = stack of [grouped conv -> LayerNorm(no affine, eps 1e-5) -> GELU]; pre = h + pos
+    const float* cur = w.hF;
+    float* lnout = w.xF;  // fp32 scratch (rows x D): free until the encoder's first LayerNorm
+    for (int i = 0; i < c.pos_conv_depth; ++i) {
+      if (int r = launch_posconv_gather(prec, cur, B, T, D, G, kp, T + kp, w.posg, x.s)) return r;
+      GemmArgs g = posconv_gemm(x, e->pos_ws[i], e->pos_bs[i]);
+      g.act = ACT_NONE;
+      if (int r = launch_gemm(gp, g, x.s)) return r;
+      LnArgs n = ln_f32(x, w.preF, x.p.rows, D, e->ones, e->zeros, 1e-5f);
+      n.gelu = 1; n.yF = lnout;
+      if (int r = launch_layernorm(n, x.s)) return r;
+      cur = lnout;
+    }
+    return launch_add_f32(w.hF, cur, w.preF, x.p.rows * (int64_t)D, x.s);
+  }
+  if (x.p.pos_multi) {
+    // multi-frame form (finalize_pos_conv): Pf output frames per GEMM row, 16-bit result scattered back onto h
+    const int Pf = x.p.Pf, Tq = (int)x.p.pos_Tq, Tp = (int)x.p.pos_Tp;
+    if (int r = launch_posconv_gather(prec, w.hF, B, T, D, G, kp, Tp, w.posg, x.s, bn_sc, bn_sh)) return r;
+    GemmArgs g;
+    g.A = w.posg; g.W = e->pos_wP.p; g.C = w.posy; g.bias = e->pos_bP.as<float>();
+    g.M = B * Tq; g.N = Pf * cg; g.K = (kp + Pf - 1) * cg;
+    g.a_rpb = Tq; g.a_bstride = (long)G * Tp * cg; g.a_rstride = (long)Pf * cg;
+    g.ldw = g.K; g.ldc = g.N;
+    g.nz = G; g.nz2 = G;
+    g.a_z2 = (long)Tp * cg; g.w_z2 = (long)g.N * g.K; g.c_z2 = (long)B * Tq * g.N; g.bias_z2 = g.N;
+    g.act = ACT_GELU; g.out_f32 = 0;
+    if (int r = launch_gemm(gp, g, x.s)) return r;
+    return launch_posconv_scatter_add(w.hF, w.posy, B, T, D, G, Pf, Tq, w.preF, x.s, prec ? 0 : 1);
+  }
+  if (int r = launch_posconv_gather(prec, w.hF, B, T, D, G, kp, T + kp, w.posg, x.s, bn_sc, bn_sh)) return r;
+  GemmArgs g = posconv_gemm(x, e->pos_w, e->pos_b);
+  g.resid = w.hF; g.act = ACT_GELU;
+  return launch_gemm(gp, g, x.s);
+}
+
+// ---- encoder layers.  Every family runs the same five products per layer; they differ in the type the products leave in and in the
+// LayerNorm step between them.
+struct LayerForm {
+  int branch_f32 = 1;      // out-projection and FFN-2 leave in fp32 (1) or in the operand type (0) in w.hF, for the LayerNorm to add
+  int ffn1_f32 = 0;        // FFN-1's out_f32 flag
+  int ffn1_pairs = 0;      // FFN-1 writes pair rows
+  bool ffn2_ksplit = false;  // FFN-2 as a K-split small GEMM: raw partial products in w.ksplit, summed by the LayerNorm behind it
+};
+
+// a product over all rows: (rows, K) x W^T + bias -> (rows, N)
+// planes: the product additionally / instead leaves as 16-bit (hi, lo) planes for the fused split attention (QKV projection)
+int rows_gemm(const EncRun& x, const void* A, int K, const DevBuf& W, const DevBuf& bias, int N, void* Cout, int out_f32, int act,
+              unsigned short* planes = nullptr, int c_pairs = 0) {
+  const int rows = (int)x.p.rows;
+  GemmArgs g;
+  g.A = A; g.W = W.p; g.C = Cout; g.bias = bias.as<float>();
+  g.M = rows; g.N = N; g.K = K; g.a_rpb = rows; g.a_rstride = K; g.ldw = K; g.ldc = N;
+  g.out_f32 = out_f32; g.act = act;
+  g.planes = planes; g.plane_stride = (long)rows * N;
+  g.a_pairs = x.pk_enc ? 1 : 0; g.c_pairs = c_pairs;
+  return launch_gemm(x.p.gp, g, x.s);
+}
+
+// QKV projection -> attention -> out-projection: w.xb -> the attention branch in w.hF
+int attention_block(const EncRun& x, const EncLayerW& Lw, const LayerForm& f) {
+  const EncPlan& p = x.p;
+  const EncWs& w = x.w;
+  const int D = p.D;
+  // split-operand modes with the fused attention: the QKV projection's epilogue writes the planes the attention reads
+  if (int r = rows_gemm(x, w.xb, D, Lw.wqkv, Lw.bqkv, 3 * D, w.qkv, 0, ACT_NONE, p.planes ? (unsigned short*)w.ab.pl_qkv : nullptr)) return r;
+  const float* gate = nullptr;
+  if (p.rel) {
+    // WavLM: the gate of the relative position bias is a function of the attention INPUT (w.xb, operand type)
+    if (int r = launch_relpos_gate(p.sp, w.xb, p.rows, (int)p.T, p.H, p.dh, Lw.g_wab.as<float>(), Lw.g_bab.as<float>(),
+                                   Lw.g_const.as<float>(), w.gate, x.s)) return r;
+    gate = w.gate;
+  }
+  if (int r = attention_scores_path(p.sp, w.qkv, 3L * D, (const char*)w.qkv + (size_t)D * esize(p.sp),
+                                    (const char*)w.qkv + (size_t)2 * D * esize(p.sp), 3L * D, p.B, (int)p.T, p.H, p.dh,
+                                    1.0f / std::sqrt((float)p.dh), w.ab, p.planes, w.attn_o, D, x.s, gate, w.relpb, p.gp, x.pk_enc ? 1 : 0)) return r;
+  // (rounds 1-2 fused this projection with the residual add and the LayerNorm in one row-complete kernel, 44 us against 29 + 23; with
+  //  the projection on gemm_pps_kernel the pair costs 20.6 + 23.9 us and the fused kernel -- every workgroup streaming all of W,
+  //  0.16 of the matrix pipe -- is gone: C2 6 093-6 110 against 6 066-6 074 clips/s on one box)
+  return rows_gemm(x, w.attn_o, D, Lw.wo, Lw.bo, D, w.hF, f.branch_f32, ACT_NONE);
+}
+
+// FFN-1 (GELU) -> FFN-2: w.xb -> the feed-forward branch in w.hF (K-split form: in w.ksplit)
+int ffn_block(const EncRun& x, const EncLayerW& Lw, const LayerForm& f) {
+  const EncWs& w = x.w;
+  const int D = x.p.D, F = x.p.F, rows = (int)x.p.rows;
+  if (int r = rows_gemm(x, w.xb, D, Lw.w1, Lw.b1, F, w.ffn, f.ffn1_f32, ACT_GELU, nullptr, f.ffn1_pairs)) return r;
+  if (!f.ffn2_ksplit) return rows_gemm(x, w.ffn, F, Lw.w2, Lw.b2, D, w.hF, f.branch_f32, ACT_NONE);
+  // a few utterances: K = F split four ways over workgroups, raw fp32 partial tiles, summed (+ bias, rounded to the operand type
+  // like the un-split product's stored result) by the LayerNorm that reads them
+  GemmArgs g;
+  g.A = w.ffn; g.W = Lw.w2.p; g.C = w.ksplit; g.M = rows; g.N = D; g.K = F; g.a_rpb = rows; g.a_rstride = F; g.ldw = F; g.ldc = D;
+  g.out_f32 = 1; g.ksplit = 4; g.ksplit_stride = (long)rows * D;
+  return launch_gemm_skinny(g, x.s);
+}
+
+// Post-LN: x = LN0(pre); per layer x = LN1(x + attention(x)), x = LN2(x + ffn(x)).  ln0() is the family's first LayerNorm,
+// ln(Lw, second, last) the one behind a branch: the residual add lives in the LayerNorm kernel (LN(x + branch)), not in the GEMM
+// epilogue, which is then store-only (fire-and-forget under the next tile's MFMAs in the persistent kernel).  The branch sits in w.hF,
+// free after the positional conv.  The last LayerNorm also leaves the fp32 result in x.resid for the whole-batch output norm.
+template <class Ln0, class Ln>
+int post_ln_layers(const EncRun& x, const LayerForm& f, Ln0&& ln0, Ln&& ln) {
+  if (int r = ln0()) return r;
+  for (int l = 0; l < x.c.num_layers; ++l) {
+    const EncLayerW& Lw = x.e->layers[l];
+    if (int r = attention_block(x, Lw, f)) return r;
+    if (int r = ln(Lw, false, false)) return r;
+    if (int r = ffn_block(x, Lw, f)) return r;
+    if (int r = ln(Lw, true, l + 1 == x.c.num_layers)) return r;
+  }
+  return SVT_OK;
+}
+
+// FFN-2 as a K-split small GEMM: when the one-utterance kernel would serve it with less than one workgroup per CU (gemm_skinny.hip)
+bool ffn2_ksplit_ok(const EncRun& x) {
+  const int D = x.p.D, F = x.p.F, rows = (int)x.p.rows;
+  if (!(g_ffn2_ksplit && x.w.ksplit && x.p.gp == 1 && F % 256 == 0 && F >= 2048 && g_ln_two_rows)) return false;
+  GemmArgs g;
+  g.A = x.w.ffn; g.W = x.e->layers[0].w2.p; g.C = x.w.hF; g.M = rows; g.N = D; g.K = F; g.a_rpb = rows; g.a_rstride = F; g.ldw = F; g.ldc = D;
+  return g_gemm_skinny && gemm_skinny_eligible(g) && (long)((x.p.rows + 31) / 32) * (D / 32) <= 256;
+}
+
+// throughput mode: the residual stream lives as a bf16 (hi, lo) pair -- hi IS the operand copy the next GEMM
+// reads -- so a LayerNorm moves 10 bytes per element instead of 12 (see layernorm.hip, layernorm_hilo_kernel)
+int post_ln_hilo(const EncRun& x) {
+  const EncWs& w = x.w;
+  const int64_t rows = x.p.rows;
+  const int D = x.p.D;
+  const float eps = x.c.layer_norm_eps;
+  bf16_t* const xh = (bf16_t*)w.xb;
+  bf16_t* const xl = (bf16_t*)w.xlo;
+  LayerForm f;
+  // branch outputs (out-proj / FFN-2) are stored in the operand type (bf16: half the store burst of the GEMM epilogue and half the
+  // read of the LayerNorm) and widened when added to the residual stream
+  f.branch_f32 = 0;
+  f.ffn2_ksplit = ffn2_ksplit_ok(x);
+  return post_ln_layers(x, f,
+    [&] { return launch_layernorm_hilo(nullptr, nullptr, nullptr, w.preF, rows, D, x.e->enc_g.as<float>(), x.e->enc_b.as<float>(), eps, xh, xl, nullptr, x.s); },
+    [&](const EncLayerW& Lw, bool second, bool last) {
+      const float *g = (second ? Lw.ln2g : Lw.ln1g).as<float>(), *b = (second ? Lw.ln2b : Lw.ln1b).as<float>();
+      float* const yF = last ? x.resid : nullptr;
+      if (second && f.ffn2_ksplit)
+        return launch_layernorm_hilo_parts(w.ksplit, 4, (long)rows * D, Lw.b2.as<float>(), xh, xl, rows, D, g, b, eps, xh, xl, yF, x.s);
+      return launch_layernorm_hilo((const bf16_t*)w.hF, xh, xl, nullptr, rows, D, g, b, eps, xh, xl, yF, x.s);
+    });
+}
+
+// split modes on pair rows.  fp16 pieces (kind 3): the layer input w.xb (pair rows) IS the residual stream -- LN(branch + (hi + lo))
+// -> (hi', lo') in place, 12 bytes per element and pass instead of 16 with an fp32 copy beside it: hi + lo of two IEEE halves
+// carries 22 of fp32's 24 mantissa bits.  bf16 pieces (kind 2) carry 16: there the residual stream stays fp32 (x.resid, updated in
+// place) beside the pair rows the products read, as in round 3.  The products see exactly the same pieces either way; the last
+// layer also leaves the fp32 result for the whole-batch output norm.
+int post_ln_pairs(const EncRun& x) {
+  const EncWs& w = x.w;
+  const bool pair_resid = x.pk_enc == 3;
+  LayerForm f;
+  f.branch_f32 = 1; f.ffn1_f32 = 1; f.ffn1_pairs = 1;
+  return post_ln_layers(x, f,
+    [&] {
+      LnArgs n = ln_f32(x, w.preF, x.p.rows, x.p.D, x.e->enc_g, x.e->enc_b, x.c.layer_norm_eps);
+      n.yP = w.xb; n.pair_kind = x.pk_enc; n.yF = pair_resid ? nullptr : x.resid;
+      return launch_layernorm(n, x.s);
+    },
+    [&](const EncLayerW& Lw, bool second, bool last) {
+      LnArgs n = ln_f32(x, w.hF, x.p.rows, x.p.D, second ? Lw.ln2g : Lw.ln1g, second ? Lw.ln2b : Lw.ln1b, x.c.layer_norm_eps);
+      n.yP = w.xb; n.pair_kind = x.pk_enc;
+      if (pair_resid) { n.addP = w.xb; n.yF = last ? x.resid : nullptr; }
+      // every lane holds its part of the row in registers before anything is stored: add and yF may be the same buffer
+      else { n.add = x.resid; n.yF = x.resid; }
+      return launch_layernorm(n, x.s);
+    });
+}
+
+// plain post-LN: operand copy in w.xb, fp32 residual stream in x.resid (fp32 storage: the same buffer, written once as yT)
+int post_ln_plain(const EncRun& x, int branch_f32) {
+  const EncWs& w = x.w;
+  LayerForm f;
+  f.branch_f32 = branch_f32;
+  auto out = [&](LnArgs n) { n.yT = w.xb; n.yF = x.p.sp ? x.resid : nullptr; return launch_layernorm(n, x.s); };
+  return post_ln_layers(x, f,
+    [&] { return out(ln_f32(x, w.preF, x.p.rows, x.p.D, x.e->enc_g, x.e->enc_b, x.c.layer_norm_eps)); },
+    [&](const EncLayerW& Lw, bool second, bool) {
+      LnArgs n = ln_f32(x, w.hF, x.p.rows, x.p.D, second ? Lw.ln2g : Lw.ln1g, second ? Lw.ln2b : Lw.ln1b, x.c.layer_norm_eps);
+      n.x_is_f32 = branch_f32; n.add = x.resid;
+      return out(n);
+    });
+}
+
+// Pre-LN (stable_layer_norm): h = pre; per layer h += attention(LN1(h)), h += ffn(LN2(h)); result LN(h) in fp32 (*final_x).  Each
+// branch is added by the LayerNorm that follows it: the fp32 residual stream h (w.preF) is updated in place (sumF) and the
+// products' operand copy of LN(h) goes to w.xb.
+int pre_ln_layers(const EncRun& x, int branch_f32, float** final_x) {
+  const EncWs& w = x.w;
+  float* const h = w.preF;
+  LayerForm f;
+  f.branch_f32 = branch_f32; f.ffn1_pairs = x.pk_enc ? 1 : 0;
+  // y = LN(h + branch) with h += branch, to the operand copy y_op or (the last one) to fp32 y_f32
+  auto ln_add = [&](const DevBuf& g_, const DevBuf& b_, const void* branch, void* y_op, float* y_f32) -> int {
+    LnArgs n = ln_f32(x, h, x.p.rows, x.p.D, g_, b_, x.c.layer_norm_eps);
+    n.sumF = (branch && y_op) ? h : nullptr;
+    if (x.pk_enc && y_op) {   // pair rows for the products; h (fp32) += branch in place
+      n.add = (const float*)branch; n.yP = y_op; n.pair_kind = x.pk_enc;
+    } else if (!branch) {
+      n.yT = y_op; n.yF = y_f32;
+    } else if (!branch_f32) {  // x = bf16 branch, add = fp32 residual, sumF = residual updated in place
+      n.x = branch; n.x_is_f32 = 0; n.add = h; n.yT = y_op; n.yF = y_f32;
+    } else {
+      n.add = (const float*)branch;
+      if (y_op) n.yT = y_op; else { n.prec = 0; n.yT = y_f32; }
+    }
+    return launch_layernorm(n, x.s);
+  };
+  const void* pending = nullptr;  // branch output not yet added to h
+  for (int l = 0; l < x.c.num_layers; ++l) {
+    const EncLayerW& Lw = x.e->layers[l];
+    if (int r = ln_add(Lw.ln1g, Lw.ln1b, pending, w.xb, nullptr)) return r;
+    if (int r = attention_block(x, Lw, f)) return r;
+    if (int r = ln_add(Lw.ln2g, Lw.ln2b, w.hF, w.xb, nullptr)) return r;
+    if (int r = ffn_block(x, Lw, f)) return r;
+    pending = w.hF;
+  }
+  // final LN(h + last FFN branch) -> fp32 (xF is unused in this family when prec == 0 it aliases xb: use qkv space)
+  *final_x = (float*)w.qkv;
+  return ln_add(x.e->enc_g, x.e->enc_b, pending, nullptr, *final_x);
+}
+
+// the transformer layers, w.preF -> *final_x (fp32, un-normalised encoder output)
+int encoder_layers(const EncRun& x, float** final_x) {
+  const EncPlan& p = x.p;
+  if (p.rel)
+    if (int r = launch_relpos_table(x.e->rel_embed.as<float>(), p.H, (int)p.T, x.c.rel_pos_buckets, x.c.rel_pos_max_distance, x.w.relpb, x.s)) return r;
+  // branch outputs (out-proj / FFN-2) are stored in the operand type (bf16 in throughput mode: half the store burst of
+  // the GEMM epilogue and 2 of the 14 bytes per element the LayerNorm moves) and widened when added to the fp32 residual stream
+  const bool vecD = (p.D == 512 || p.D == 768 || p.D == 1024);
+  const int branch_f32 = (p.sp && vecD) ? 0 : 1;
+  if (x.c.stable_layer_norm) return pre_ln_layers(x, branch_f32, final_x);
+  *final_x = x.resid;
+  if (p.hilo) return post_ln_hilo(x);
+  if (x.pk_enc) return post_ln_pairs(x);
+  return post_ln_plain(x, branch_f32);
+}
+
+// the wrapper's whole-batch output LayerNorm (+ frame head + decode when a head was given)
+int forward_tail(EncRun& x, float* final_x, const TailSpec& tail) {
+  const svt_encoder_config& c = x.c;
+  const EncWs& w = x.w;
+  const int64_t rows = x.p.rows, n_out = rows * x.p.D;
+  const double n_out_stat = x.global_norm ? (double)x.e->reduce_global_clips * (double)x.p.T * (double)x.p.D : 0.0;
+  x.rctx.mom = x.out_mom;
+  if (tail.head) {
+    static_assert(sizeof(svt_frame) == sizeof(FrameOut), "frame layout");
+    if (launch_head_fused(final_x, rows, x.p.D, tail.head->w.as<float>(), tail.head->wsum.as<float>(),
+                          tail.head->has_bias ? tail.head->b.as<float>() : nullptr, tail.head->out_f, w.dots,
+                          c.output_norm ? x.out_mom : nullptr, rows / x.groups, 1e-5f, tail.logits, (FrameOut*)tail.frames, tail.n_oct,
+                          tail.n_cls, x.s, n_out_stat, x.global_norm && c.output_norm ? reduce_now : nullptr, &x.rctx,
+                          (char*)w.mom + w.mom_scr[3])) return SVT_ERR_HIP;
+    return SVT_OK;
+  }
+  if (c.output_norm) {
+    if (int r = launch_moments(final_x, n_out / x.groups, x.out_mom, (char*)w.mom + w.mom_scr[1], x.p.B, x.s, x.groups)) return r;
+    if (x.global_norm) { if (int r = reduce_now(&x.rctx)) return r; }
+    return launch_global_norm(final_x, tail.feats, n_out / x.groups, x.out_mom, 1e-5f, x.s, x.groups, n_out_stat);
+  }
+  return launch_copy_f32(final_x, tail.feats, n_out, x.s) ? SVT_ERR_HIP : SVT_OK;
+}
+
+int encoder_forward_impl(svt_encoder* e, const float* wav, int32_t B, int64_t L, const TailSpec& tail, void* workspace,
+                         size_t workspace_bytes, void* stream, int32_t clips_per_norm_group) {
+  if (!e || !wav || !workspace) { set_error("encoder_forward: null argument"); return SVT_ERR_INVALID; }
+  if (!e->finalized) { set_error("encoder_forward: parameters not finalized"); return SVT_ERR_STATE; }
+  if (B < 1) { set_error("encoder_forward: batch < 1"); return SVT_ERR_INVALID; }
+  EncPlan plan;
+  if (!plan_encoder(e, B, L, &plan)) { set_error("encoder_forward: waveform shorter than the receptive field"); return SVT_ERR_INVALID; }
+  EncRun x{e, e->cfg, plan, carve_encoder(e, plan, workspace), (hipStream_t)stream};
+  if (x.w.total > workspace_bytes) { set_error("encoder_forward: workspace too small (" + std::to_string(workspace_bytes) + " < " + std::to_string(x.w.total) + ")"); return SVT_ERR_WORKSPACE; }
+  SVT_HIP(hipSetDevice(e->device));
+  if (int r = check_norm_groups(x, clips_per_norm_group)) return r;
+  if (int r = input_statistics(x, wav)) return r;
+  choose_pair_rows(x);
+  int cur = 0;
+  if (e->cfg.num_conv_layers == 0) {   // features-in mode: `wav` is the (B, T, C) fp32 feature tensor
+    const int64_t n = plan.rows * e->cfg.conv_dim[0];
+    if (plan.sp) { if (int r = launch_f32_to_bf16(wav, (bf16_t*)x.w.act[0], n, x.s)) return r; }
+    else if (launch_copy_f32(wav, (float*)x.w.act[0], n, x.s)) return SVT_ERR_HIP;
+  } else {
+    if (int r = conv_layer0(x, wav)) return r;
+    if (int r = conv_stack(x, &cur)) return r;
+  }
+  if (int r = feature_projection(x, cur)) return r;
+  if (int r = positional_conv(x)) return r;
+  float* final_x = nullptr;
+  if (int r = encoder_layers(x, &final_x)) return r;
+  return forward_tail(x, final_x, tail);
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -496,430 +1076,3 @@ int svt_encoder_forward_head(svt_encoder* e, const svt_linear* head, const float
 }
 
 }  // extern "C"
-
-static int encoder_forward_impl(svt_encoder* e, const float* wav, int32_t B, int64_t L, const TailSpec& tail, void* workspace,
-                                size_t workspace_bytes, void* stream, int32_t clips_per_norm_group) {
-  float* feats = tail.feats;
-  if (!e || !wav || !workspace) { set_error("encoder_forward: null argument"); return SVT_ERR_INVALID; }
-  if (!e->finalized) { set_error("encoder_forward: parameters not finalized"); return SVT_ERR_STATE; }
-  if (B < 1) { set_error("encoder_forward: batch < 1"); return SVT_ERR_INVALID; }
-  const int64_t T = svt_encoder_num_frames(e, L);
-  if (T < 1) { set_error("encoder_forward: waveform shorter than the receptive field"); return SVT_ERR_INVALID; }
-  const svt_encoder_config& c = e->cfg;
-  const int prec = storage_prec(c.precision);  // storage type of activations / weights
-  const int gp = c.precision;                  // engine of the dense products (launch_gemm)
-  EncWs w = carve_encoder(e, B, L, workspace);
-  if (w.total > workspace_bytes) { set_error("encoder_forward: workspace too small (" + std::to_string(workspace_bytes) + " < " + std::to_string(w.total) + ")"); return SVT_ERR_WORKSPACE; }
-  hipStream_t s = (hipStream_t)stream;
-  SVT_HIP(hipSetDevice(e->device));
-  // the wrapper's two whole-tensor layer norms run over groups of `cpg` consecutive clips: cpg = B is the reference on a
-  // batch (and per device shard under DataParallel / DDP), cpg = 1 makes a batch of B clips equal to B batch-1 forwards --
-  // the reference's evaluation loop (train_audio_ssl.py:90 asserts batch 1) without its one-utterance-at-a-time cost
-  const int cpg = clips_per_norm_group > 0 ? clips_per_norm_group : B;
-  if (B % cpg) { set_error("encoder_forward: batch must be a multiple of clips_per_norm_group"); return SVT_ERR_INVALID; }
-  const int groups = B / cpg;
-  if (groups > 1 && c.num_conv_layers > 0 && (L & 3)) {
-    set_error("encoder_forward: norm groups need a waveform length that is a multiple of 4 samples");
-    return SVT_ERR_INVALID;
-  }
-  if (groups > 1 && c.num_conv_layers == 0 && c.normalize_wav) {
-    set_error("encoder_forward: features-in mode has no input norm to group");
-    return SVT_ERR_INVALID;
-  }
-  if (launch_zero_bytes(w.mom, w.mom_zero, s)) return SVT_ERR_HIP;   // (a kernel, not a memset node: see encoder_ops.hip)
-  double* wav_mom = c.normalize_wav ? w.mom : nullptr;
-  double* out_mom = w.mom + 2 * (size_t)B;
-  double* wm = w.mom + 4 * (size_t)B;
-  int64_t n_wav = (int64_t)cpg * L;
-  if (c.normalize_wav)
-    if (int r = launch_moments(wav, n_wav, wav_mom, (char*)w.mom + w.mom_scr[0], B, s, groups)) return r;
-  // "global-batch-equivalent" norms (optional): the batch is a shard of a larger one; the caller's function sums the
-  // (sum, sum of squares) pair over the ranks -- 16 bytes per norm -- and the statistics are then those of the whole global batch
-  struct ReduceCtx { svt_encoder* e; double* mom; hipStream_t s; } rctx{e, nullptr, s};
-  auto reduce_now = [](void* a) -> int {
-    ReduceCtx* rc = (ReduceCtx*)a;
-    if (rc->e->reduce_fn(rc->mom, 2, (void*)rc->s, rc->e->reduce_user)) { set_error("encoder_forward: the norm-reduce callback reported an error"); return SVT_ERR_INVALID; }
-    return 0;
-  };
-  const bool global_norm = e->reduce_fn != nullptr;
-  if (global_norm) {
-    if (groups != 1) { set_error("encoder_forward: the cross-rank norm reduction applies to whole-batch norms (clips_per_norm_group = 0)"); return SVT_ERR_INVALID; }
-    if (e->reduce_global_clips < B) { set_error("encoder_forward: global_clips of the norm reduction is smaller than this batch"); return SVT_ERR_INVALID; }
-    if (c.normalize_wav) {
-      rctx.mom = wav_mom;
-      if (int r = reduce_now(&rctx)) return r;
-      n_wav = e->reduce_global_clips * L;
-    }
-  }
-
-  // ---- split modes: which products take PAIR ROWS (gemm_x3q.hip: operands cut by their producers) ----
-  // front = conv 1..n-1 and the feature projection, enc = the four products of every encoder layer; a section switches as a whole,
-  // and only when every product in it fits gemm_x3q_kernel's contract (otherwise its activations stay fp32 and the products cut them)
-  const int pk_mode = (gp >= 2 && g_x3_pairs && g_gemm_x3) ? gp : 0;
-  auto x3q_fits = [&](const void* A, int M, int N, int K, int a_rpb, long a_bstride, long a_rstride, const void* Wp, int c_pairs, long ldc) -> bool {
-    GemmArgs g;
-    g.A = A; g.W = Wp; g.C = const_cast<void*>(A); g.M = M; g.N = N; g.K = K; g.a_rpb = a_rpb; g.a_bstride = a_bstride; g.a_rstride = a_rstride;
-    g.ldw = K; g.ldc = ldc; g.a_pairs = 1; g.c_pairs = c_pairs;
-    return gemm_x3q_eligible(g);
-  };
-  bool pk_front_ok = pk_mode != 0 && c.num_conv_layers >= 2 && c.conv_dim[0] % 32 == 0 && c.conv_dim[0] <= 512 && c.conv_stride[0] <= 5;
-  if (pk_front_ok) {
-    int64_t ti_ = (L - c.conv_kernel[0]) / c.conv_stride[0] + 1;
-    for (int i = 1; i < c.num_conv_layers && pk_front_ok; ++i) {
-      const int cin = c.conv_dim[i - 1], co = c.conv_dim[i], k = c.conv_kernel[i], st = c.conv_stride[i];
-      const int64_t to_ = (ti_ - k) / st + 1;
-      if ((int64_t)B * to_ > 2147483647LL) { pk_front_ok = false; break; }
-      pk_front_ok = x3q_fits(w.act[0], (int)((int64_t)B * to_), co, k * cin, (int)to_, ti_ * cin, (long)st * cin, e->conv[i].w.p, 1, co) &&
-                    (c.feat_extract_norm != SVT_NORM_LAYER || co == 512 || co == 768 || co == 1024);
-      ti_ = to_;
-    }
-    const int Cl = c.conv_dim[c.num_conv_layers - 1];
-    const int64_t rows_ = (int64_t)B * T;
-    pk_front_ok = pk_front_ok && x3q_fits(w.xln, (int)rows_, c.hidden_size, Cl, (int)rows_, 0, Cl, e->proj_w.p, 0, c.hidden_size) &&
-                  (!c.feat_proj_layer_norm || Cl == 512 || Cl == 768 || Cl == 1024);
-  }
-  const int pk_front = pk_front_ok ? pk_mode : 0;
-
-  // ---- conv feature extractor (channels-last activations) ----
-  int64_t tin = L;
-  int cur = 0;
-  if (c.num_conv_layers == 0) {
-    // features-in mode: `wav` is the (B, T, C) fp32 feature tensor
-    const int64_t n = (int64_t)B * L * c.conv_dim[0];
-    if (prec) { if (int r = launch_f32_to_bf16(wav, (bf16_t*)w.act[0], n, s)) return r; }
-    else if (launch_copy_f32(wav, (float*)w.act[0], n, s)) return SVT_ERR_HIP;
-  } else {
-  int64_t t1 = (L - c.conv_kernel[0]) / c.conv_stride[0] + 1;
-  const ConvLayerW& c0 = e->conv[0];
-  if (c.feat_extract_norm == SVT_NORM_GROUP) {
-    if (int r = launch_conv0_window_moments(wav, B, L, c.conv_kernel[0], c.conv_stride[0], t1, wm, (char*)w.mom + w.mom_scr[2], s)) return r;
-    if (int r = launch_conv0_group_coef(wav_mom, n_wav, wm, B, t1, c.conv_dim[0], c.conv_kernel[0], c0.w.as<float>(),
-                                        c.conv_bias ? c0.bias.as<float>() : nullptr, c0.gamma.as<float>(),
-                                        c0.beta.as<float>(), 1e-5f, 1e-5f, w.coef, s, cpg)) return r;
-    if (conv0_mfma_ok(prec, pk_front, c.conv_kernel[0], c.conv_stride[0], c.conv_dim[0]) && w.c0tab) {
-      if (int r = launch_conv0_mfma_group(wav, B, L, c.conv_stride[0], t1, w.coef, w.c0tab, w.act[0], s, pk_front)) return r;
-    } else
-    if (int r = launch_conv0_group_apply(prec, wav, B, L, c.conv_kernel[0], c.conv_stride[0], t1, c.conv_dim[0], w.coef,
-                                         w.act[0], s, pk_front)) return r;
-  } else {
-    if (conv0_mfma_ok(prec, pk_front, c.conv_kernel[0], c.conv_stride[0], c.conv_dim[0]) && w.c0tab) {
-      if (int r = launch_conv0_mfma_layer(wav, B, L, c.conv_stride[0], t1, wav_mom, n_wav, 1e-5f, c0.w.as<float>(),
-                                          c.conv_bias ? c0.bias.as<float>() : nullptr, c0.gamma.as<float>(), c0.beta.as<float>(), 1e-5f,
-                                          w.c0tab, w.act[0], s, cpg, pk_front)) return r;
-    } else
-    if (int r = launch_conv0_layer(prec, wav, B, L, c.conv_kernel[0], c.conv_stride[0], t1, c.conv_dim[0], wav_mom, n_wav,
-                                   1e-5f, c0.w.as<float>(), c.conv_bias ? c0.bias.as<float>() : nullptr,
-                                   c0.gamma.as<float>(), c0.beta.as<float>(), 1e-5f, w.act[0], s, cpg, pk_front)) return r;
-  }
-  tin = t1;
-  }
-  for (int i = 1; i < c.num_conv_layers; ++i) {
-    const int cin = c.conv_dim[i - 1], co = c.conv_dim[i], k = c.conv_kernel[i], st = c.conv_stride[i];
-    const int64_t tout = (tin - k) / st + 1;
-    const ConvLayerW& Lw = e->conv[i];
-    GemmArgs g;
-    g.A = w.act[cur]; g.W = Lw.w.p;
-    g.M = (int)((int64_t)B * tout); g.N = co; g.K = k * cin;
-    g.a_rpb = (int)tout; g.a_bstride = tin * cin; g.a_rstride = (long)st * cin;
-    g.ldw = g.K; g.ldc = co;
-    if (Lw.w_kperm.p) { g.W_kperm = Lw.w_kperm.p; g.kperm_taps = k; g.kperm_cin = cin; }
-    g.bias = c.conv_bias ? Lw.bias.as<float>() : nullptr;
-    if ((int64_t)B * tout > 2147483647LL) { set_error("encoder_forward: batch*frames exceeds 2^31"); return SVT_ERR_INVALID; }
-    // pair rows: this layer reads them; it writes them too unless the feature projection's LayerNorm (an fp32 reader) comes next
-    g.a_pairs = pk_front ? 1 : 0;
-    const bool pairs_out = pk_front && !(i + 1 == c.num_conv_layers && c.feat_proj_layer_norm);
-    if (pk_front && c.feat_extract_norm == SVT_NORM_LAYER) {
-      g.C = w.convF; g.out_f32 = 1; g.act = ACT_NONE;
-      if (int r = launch_gemm(gp, g, s)) return r;
-      if (int r = launch_layernorm(prec, w.convF, 1, (int64_t)B * tout, co, Lw.gamma.as<float>(), Lw.beta.as<float>(), 1e-5f, 1,
-                                   pairs_out ? nullptr : w.act[cur ^ 1], nullptr, s, nullptr, nullptr, pairs_out ? w.act[cur ^ 1] : nullptr,
-                                   pk_front)) return r;
-    } else if (pk_front) {
-      g.C = w.act[cur ^ 1]; g.act = ACT_GELU; g.out_f32 = 1; g.c_pairs = pairs_out ? 1 : 0;
-      if (int r = launch_gemm(gp, g, s)) return r;
-    } else
-    if (c.feat_extract_norm == SVT_NORM_LAYER && prec && co == 512 && g_conv_ln_bf16) {
-      // throughput mode: the conv output goes to HBM once, in the operand type, and is normalised in place (a wave owns a
-      // row: it reads all of it before it writes) -- the fp32 round trip below moves 3x the bytes (conv1 at 64 x 10 s:
-      // 2.1 GB written + 2.1 GB read + 1.05 GB written)
-      g.C = w.act[cur ^ 1]; g.out_f32 = 0; g.act = ACT_NONE;
-      if (int r = launch_gemm(gp, g, s)) return r;
-      if (int r = launch_layernorm(prec, w.act[cur ^ 1], 0, (int64_t)B * tout, co, Lw.gamma.as<float>(), Lw.beta.as<float>(),
-                                   1e-5f, 1, w.act[cur ^ 1], nullptr, s)) return r;
-    } else if (c.feat_extract_norm == SVT_NORM_LAYER) {
-      g.C = w.convF; g.out_f32 = 1; g.act = ACT_NONE;
-      if (int r = launch_gemm(gp, g, s)) return r;
-      if (int r = launch_layernorm(prec, w.convF, 1, (int64_t)B * tout, co, Lw.gamma.as<float>(), Lw.beta.as<float>(),
-                                   1e-5f, 1, w.act[cur ^ 1], nullptr, s)) return r;
-    } else {
-      g.C = w.act[cur ^ 1]; g.act = ACT_GELU;
-      if (int r = launch_gemm(gp, g, s)) return r;
-    }
-    cur ^= 1;
-    tin = tout;
-  }
-  const int C = c.conv_dim[c.num_conv_layers > 0 ? c.num_conv_layers - 1 : 0];
-  const int D = c.hidden_size, F = c.intermediate_size, H = c.num_heads, dh = D / H;
-  const int64_t rows = (int64_t)B * T;
-  const float eps = c.layer_norm_eps;
-
-  // ---- feature projection ----
-  const void* proj_in = w.act[cur];
-  if (c.feat_proj_layer_norm) {
-    if (int r = launch_layernorm(prec, w.act[cur], prec ? 0 : 1, rows, C, e->fp_g.as<float>(), e->fp_b.as<float>(), eps, 0,
-                                 pk_front ? nullptr : w.xln, nullptr, s, nullptr, nullptr, pk_front ? w.xln : nullptr, pk_front)) return r;
-    proj_in = w.xln;
-  }
-  {
-    GemmArgs g;
-    g.A = proj_in; g.W = e->proj_w.p; g.C = w.hF; g.bias = e->proj_b.as<float>();
-    g.M = (int)rows; g.N = D; g.K = C; g.a_rpb = (int)rows; g.a_rstride = C; g.ldw = C; g.ldc = D; g.out_f32 = 1;
-    g.a_pairs = pk_front ? 1 : 0;
-    if (int r = launch_gemm(gp, g, s)) return r;
-  }
-  // ---- positional conv embedding: pre = h + gelu(grouped_conv(h) + b) ----
-  {
-    const int kp = c.pos_conv_kernel, G = c.pos_conv_groups, cg = D / G;
-    const int Pf = e->pos_P;
-    const float* bn_sc = c.pos_conv_batch_norm ? e->pos_bn_sc.as<float>() : nullptr;
-    const float* bn_sh = c.pos_conv_batch_norm ? e->pos_bn_sh.as<float>() : nullptr;
-    if (c.pos_conv_depth > 1) {
-      // data2vec-audio: pos = stack of [grouped conv -> LayerNorm(no affine, eps 1e-5) -> GELU]; pre = h + pos
-      const float* cur = w.hF;
-      float* lnout = w.xF;  // fp32 scratch (rows x D): free until the encoder's first LayerNorm
-      for (int i = 0; i < c.pos_conv_depth; ++i) {
-        if (int r = launch_posconv_gather(prec, cur, B, (int)T, D, G, kp, (int)T + kp, w.posg, s)) return r;
-        GemmArgs g;
-        g.A = w.posg; g.W = e->pos_ws[i].p; g.C = w.preF; g.bias = e->pos_bs[i].as<float>();
-        g.M = (int)T; g.N = cg; g.K = kp * cg;
-        g.a_rpb = (int)T; g.a_rstride = cg;
-        g.ldw = g.K; g.ldc = D;
-        g.nz = B * G; g.nz2 = G;
-        g.a_z1 = (long)G * (T + kp) * cg; g.a_z2 = (long)(T + kp) * cg;
-        g.w_z1 = 0; g.w_z2 = (long)cg * g.K;
-        g.c_z1 = (long)T * D; g.c_z2 = cg; g.bias_z2 = cg;
-        g.act = ACT_NONE; g.out_f32 = 1;
-        if (int r = launch_gemm(gp, g, s)) return r;
-        if (int r = launch_layernorm(prec, w.preF, 1, rows, D, e->ones.as<float>(), e->zeros.as<float>(), 1e-5f, 1, nullptr,
-                                     lnout, s)) return r;
-        cur = lnout;
-      }
-      if (int r = launch_add_f32(w.hF, cur, w.preF, rows * (int64_t)D, s)) return r;
-    } else if (Pf && (int64_t)B * ((T + Pf - 1) / Pf) >= 128) {
-      const int Tq = (int)((T + Pf - 1) / Pf), Tp = Tq * Pf + kp;
-      if (int r = launch_posconv_gather(prec, w.hF, B, (int)T, D, G, kp, Tp, w.posg, s, bn_sc, bn_sh)) return r;
-      GemmArgs g;
-      g.A = w.posg; g.W = e->pos_wP.p; g.C = w.posy; g.bias = e->pos_bP.as<float>();
-      g.M = B * Tq; g.N = Pf * cg; g.K = (kp + Pf - 1) * cg;
-      g.a_rpb = Tq; g.a_bstride = (long)G * Tp * cg; g.a_rstride = (long)Pf * cg;
-      g.ldw = g.K; g.ldc = g.N;
-      g.nz = G; g.nz2 = G;
-      g.a_z2 = (long)Tp * cg; g.w_z2 = (long)g.N * g.K; g.c_z2 = (long)B * Tq * g.N; g.bias_z2 = g.N;
-      g.act = ACT_GELU; g.out_f32 = 0;
-      if (int r = launch_gemm(gp, g, s)) return r;
-      if (int r = launch_posconv_scatter_add(w.hF, w.posy, B, (int)T, D, G, Pf, Tq, w.preF, s, prec ? 0 : 1)) return r;
-    } else {
-    if (int r = launch_posconv_gather(prec, w.hF, B, (int)T, D, G, kp, (int)T + kp, w.posg, s, bn_sc, bn_sh)) return r;
-    GemmArgs g;
-    g.A = w.posg; g.W = e->pos_w.p; g.C = w.preF; g.bias = e->pos_b.as<float>(); g.resid = w.hF;
-    g.M = (int)T; g.N = cg; g.K = kp * cg;
-    g.a_rpb = (int)T; g.a_rstride = cg;
-    g.ldw = g.K; g.ldc = D;
-    g.nz = B * G; g.nz2 = G;
-    g.a_z1 = (long)G * (T + kp) * cg; g.a_z2 = (long)(T + kp) * cg;
-    g.w_z1 = 0; g.w_z2 = (long)cg * g.K;
-    g.c_z1 = (long)T * D; g.c_z2 = cg; g.bias_z2 = cg;
-    g.act = ACT_GELU; g.out_f32 = 1;
-    if (int r = launch_gemm(gp, g, s)) return r;
-    }
-  }
-  const float scale = 1.0f / std::sqrt((float)dh);
-  if (c.rel_pos_buckets)
-    if (int r = launch_relpos_table(e->rel_embed.as<float>(), H, (int)T, c.rel_pos_buckets, c.rel_pos_max_distance, w.relpb, s)) return r;
-  // split-operand modes with the fused attention: the QKV projection's epilogue writes the planes the attention reads
-  const bool qkv_planes = gp >= 2 && !c.rel_pos_buckets && flash_attention_x3_ok(dh) && w.ab.pl_qkv != nullptr;
-  unsigned short* const qkv_pl = qkv_planes ? (unsigned short*)w.ab.pl_qkv : nullptr;
-  // encoder layers on pair rows: the layer input (LayerNorm output), the attention output and the FFN intermediate are written as
-  // pair rows by their producers; the residual stream stays fp32 beside them (w.xF)
-  const bool pk_enc_ok = pk_mode != 0 && qkv_planes && c.num_layers > 0 && (D == 512 || D == 768 || D == 1024) && dh % 32 == 0 &&
-                         x3q_fits(w.xb, (int)rows, 3 * D, D, (int)rows, 0, D, e->layers[0].wqkv.p, 0, 3 * D) &&
-                         x3q_fits(w.attn_o, (int)rows, D, D, (int)rows, 0, D, e->layers[0].wo.p, 0, D) &&
-                         x3q_fits(w.xb, (int)rows, F, D, (int)rows, 0, D, e->layers[0].w1.p, 1, F) &&
-                         x3q_fits(w.ffn, (int)rows, D, F, (int)rows, 0, F, e->layers[0].w2.p, 0, D);
-  const int pk_enc = pk_enc_ok ? pk_mode : 0;
-  if (!prec && !pk_enc) w.xF = (float*)w.xb;   // fp32 storage without pair rows: the layer input IS the residual stream (one buffer)
-  int cur_layer = 0;
-  auto attention = [&](void) -> int {
-    const float* gate = nullptr;
-    if (c.rel_pos_buckets) {
-      // WavLM: the gate of the relative position bias is a function of the attention INPUT (w.xb, operand type)
-      const EncLayerW& Lg = e->layers[cur_layer];
-      if (int r = launch_relpos_gate(prec, w.xb, rows, (int)T, H, dh, Lg.g_wab.as<float>(), Lg.g_bab.as<float>(),
-                                     Lg.g_const.as<float>(), w.gate, s)) return r;
-      gate = w.gate;
-    }
-    ++cur_layer;
-    return attention_scores_path(prec, w.qkv, 3L * D, (const char*)w.qkv + (size_t)D * esize(prec),
-                                 (const char*)w.qkv + (size_t)2 * D * esize(prec), 3L * D, B, (int)T, H, dh, scale, w.ab,
-                                 qkv_planes, w.attn_o, D, s, gate, w.relpb, gp, pk_enc ? 1 : 0);
-  };
-  // planes: the product additionally / instead leaves as 16-bit (hi, lo) planes for the fused split attention (QKV projection)
-  auto gemm_rows = [&](const void* A, int K, const DevBuf& W, const DevBuf& bias, int N, void* Cout, int out_f32, int act,
-                       const float* resid, unsigned short* planes = nullptr, int c_pairs = 0) -> int {
-    GemmArgs g;
-    g.A = A; g.W = W.p; g.C = Cout; g.bias = bias.as<float>(); g.resid = resid;
-    g.M = (int)rows; g.N = N; g.K = K; g.a_rpb = (int)rows; g.a_rstride = K; g.ldw = K; g.ldc = N;
-    g.out_f32 = out_f32; g.act = act;
-    g.planes = planes; g.plane_stride = (long)rows * N;
-    g.a_pairs = pk_enc ? 1 : 0; g.c_pairs = c_pairs;
-    return launch_gemm(gp, g, s);
-  };
-
-  float* final_x = nullptr;
-  // The residual add lives in the LayerNorm kernel (LN(x + branch)), not in the GEMM epilogue: the GEMM epilogue
-  // is then store-only (fire-and-forget under the next tile's MFMAs in the persistent kernel).  tmp = w.hF is free
-  // after the positional conv.
-  float* tmp = w.hF;
-  // branch outputs (out-proj / FFN-2) are stored in the operand type (bf16 in throughput mode: half the store burst of
-  // the GEMM epilogue and half the read of the LayerNorm) and widened when added to the fp32 residual stream
-  const bool vecD = (D == 512 || D == 768 || D == 1024);
-  const int tmp_f32 = (prec && vecD) ? 0 : 1;
-  if (!c.stable_layer_norm && prec && layernorm_hilo_ok(D) && c.num_layers > 0) {
-    // throughput mode: the residual stream lives as a bf16 (hi, lo) pair -- hi IS the operand copy the next GEMM
-    // reads -- so a LayerNorm moves 10 bytes per element instead of 12 (see layernorm.hip, layernorm_hilo_kernel)
-    bf16_t* xh = (bf16_t*)w.xb;
-    bf16_t* xl = (bf16_t*)w.xlo;
-    if (int r = launch_layernorm_hilo(nullptr, nullptr, nullptr, w.preF, rows, D, e->enc_g.as<float>(), e->enc_b.as<float>(), eps,
-                                      xh, xl, nullptr, s)) return r;
-    // FFN-2 as a K-split small GEMM: when the one-utterance kernel would serve it with less than one workgroup per CU (gemm_skinny.hip)
-    bool ffn2_split = false;
-    if (g_ffn2_ksplit && w.ksplit && gp == 1 && F % 256 == 0 && F >= 2048 && g_ln_two_rows) {
-      GemmArgs g;
-      g.A = w.ffn; g.W = e->layers[0].w2.p; g.C = tmp; g.M = (int)rows; g.N = D; g.K = F; g.a_rpb = (int)rows; g.a_rstride = F; g.ldw = F; g.ldc = D;
-      ffn2_split = g_gemm_skinny && gemm_skinny_eligible(g) && (long)((rows + 31) / 32) * (D / 32) <= 256;
-    }
-    for (int l = 0; l < c.num_layers; ++l) {
-      const EncLayerW& Lw = e->layers[l];
-      const bool last = l + 1 == c.num_layers;
-      if (int r = gemm_rows(w.xb, D, Lw.wqkv, Lw.bqkv, 3 * D, w.qkv, 0, ACT_NONE, nullptr, qkv_pl)) return r;
-      if (int r = attention()) return r;
-      // (rounds 1-2 fused this projection with the residual add and the LayerNorm in one row-complete kernel, 44 us against 29 + 23; with
-      //  the projection on gemm_pps_kernel the pair costs 20.6 + 23.9 us and the fused kernel -- every workgroup streaming all of W,
-      //  0.16 of the matrix pipe -- is gone: C2 6 093-6 110 against 6 066-6 074 clips/s on one box)
-      if (int r = gemm_rows(w.attn_o, D, Lw.wo, Lw.bo, D, tmp, 0, ACT_NONE, nullptr)) return r;
-      if (int r = launch_layernorm_hilo((const bf16_t*)tmp, xh, xl, nullptr, rows, D, Lw.ln1g.as<float>(), Lw.ln1b.as<float>(), eps,
-                                        xh, xl, nullptr, s)) return r;
-      if (int r = gemm_rows(w.xb, D, Lw.w1, Lw.b1, F, w.ffn, 0, ACT_GELU, nullptr)) return r;
-      if (ffn2_split) {
-        // a few utterances: K = F split four ways over workgroups, raw fp32 partial tiles, summed (+ bias, rounded to the operand type
-        // like the un-split product's stored result) by the LayerNorm that reads them
-        GemmArgs g;
-        g.A = w.ffn; g.W = Lw.w2.p; g.C = w.ksplit; g.M = (int)rows; g.N = D; g.K = F; g.a_rpb = (int)rows; g.a_rstride = F; g.ldw = F; g.ldc = D;
-        g.out_f32 = 1; g.ksplit = 4; g.ksplit_stride = (long)rows * D;
-        if (int r = launch_gemm_skinny(g, s)) return r;
-        if (int r = launch_layernorm_hilo_parts(w.ksplit, 4, (long)rows * D, Lw.b2.as<float>(), xh, xl, rows, D, Lw.ln2g.as<float>(), Lw.ln2b.as<float>(),
-                                                eps, xh, xl, last ? w.xF : nullptr, s)) return r;
-        continue;
-      }
-      if (int r = gemm_rows(w.ffn, F, Lw.w2, Lw.b2, D, tmp, 0, ACT_NONE, nullptr)) return r;
-      if (int r = launch_layernorm_hilo((const bf16_t*)tmp, xh, xl, nullptr, rows, D, Lw.ln2g.as<float>(), Lw.ln2b.as<float>(), eps,
-                                        xh, xl, last ? w.xF : nullptr, s)) return r;
-    }
-    final_x = w.xF;
-  } else if (!c.stable_layer_norm && pk_enc) {
-    // split modes on pair rows.  fp16 pieces (kind 3): the layer input w.xb (pair rows) IS the residual stream -- LN(branch + (hi + lo))
-    // -> (hi', lo') in place, 12 bytes per element and pass instead of 16 with an fp32 copy beside it: hi + lo of two IEEE halves
-    // carries 22 of fp32's 24 mantissa bits.  bf16 pieces (kind 2) carry 16: there the residual stream stays fp32 (w.xF, updated in
-    // place) beside the pair rows the products read, as in round 3.  The products see exactly the same pieces either way; the last
-    // layer also leaves the fp32 result for the whole-batch output norm.
-    const bool pair_resid = pk_enc == 3;
-    float* const keepF = pair_resid ? nullptr : w.xF;
-    if (int r = launch_layernorm(prec, w.preF, 1, rows, D, e->enc_g.as<float>(), e->enc_b.as<float>(), eps, 0, nullptr, keepF, s, nullptr,
-                                 nullptr, w.xb, pk_enc)) return r;
-    auto ln_resid = [&](const float* g_, const float* b_, bool want_f32) -> int {
-      if (pair_resid)
-        return launch_layernorm(prec, tmp, 1, rows, D, g_, b_, eps, 0, nullptr, want_f32 ? w.xF : nullptr, s, nullptr, nullptr, w.xb,
-                                pk_enc, w.xb);
-      // every lane holds its part of the row in registers before anything is stored: add and yF may be the same buffer
-      return launch_layernorm(prec, tmp, 1, rows, D, g_, b_, eps, 0, nullptr, w.xF, s, w.xF, nullptr, w.xb, pk_enc, nullptr);
-    };
-    for (int l = 0; l < c.num_layers; ++l) {
-      const EncLayerW& Lw = e->layers[l];
-      const bool last = l + 1 == c.num_layers;
-      if (int r = gemm_rows(w.xb, D, Lw.wqkv, Lw.bqkv, 3 * D, w.qkv, 0, ACT_NONE, nullptr, qkv_pl)) return r;
-      if (int r = attention()) return r;
-      if (int r = gemm_rows(w.attn_o, D, Lw.wo, Lw.bo, D, tmp, 1, ACT_NONE, nullptr)) return r;
-      if (int r = ln_resid(Lw.ln1g.as<float>(), Lw.ln1b.as<float>(), false)) return r;
-      if (int r = gemm_rows(w.xb, D, Lw.w1, Lw.b1, F, w.ffn, 1, ACT_GELU, nullptr, nullptr, 1)) return r;
-      if (int r = gemm_rows(w.ffn, F, Lw.w2, Lw.b2, D, tmp, 1, ACT_NONE, nullptr)) return r;
-      if (int r = ln_resid(Lw.ln2g.as<float>(), Lw.ln2b.as<float>(), last)) return r;
-    }
-    final_x = w.xF;
-  } else if (!c.stable_layer_norm) {
-    if (int r = launch_layernorm(prec, w.preF, 1, rows, D, e->enc_g.as<float>(), e->enc_b.as<float>(), eps, 0, w.xb,
-                                 prec ? w.xF : nullptr, s)) return r;
-    for (int l = 0; l < c.num_layers; ++l) {
-      const EncLayerW& Lw = e->layers[l];
-      if (int r = gemm_rows(w.xb, D, Lw.wqkv, Lw.bqkv, 3 * D, w.qkv, 0, ACT_NONE, nullptr, qkv_pl)) return r;
-      if (int r = attention()) return r;
-      if (int r = gemm_rows(w.attn_o, D, Lw.wo, Lw.bo, D, tmp, tmp_f32, ACT_NONE, nullptr)) return r;
-      if (int r = launch_layernorm(prec, tmp, tmp_f32, rows, D, Lw.ln1g.as<float>(), Lw.ln1b.as<float>(), eps, 0, w.xb,
-                                   prec ? w.xF : nullptr, s, w.xF)) return r;
-      if (int r = gemm_rows(w.xb, D, Lw.w1, Lw.b1, F, w.ffn, 0, ACT_GELU, nullptr)) return r;
-      if (int r = gemm_rows(w.ffn, F, Lw.w2, Lw.b2, D, tmp, tmp_f32, ACT_NONE, nullptr)) return r;
-      if (int r = launch_layernorm(prec, tmp, tmp_f32, rows, D, Lw.ln2g.as<float>(), Lw.ln2b.as<float>(), eps, 0, w.xb,
-                                   prec ? w.xF : nullptr, s, w.xF)) return r;
-    }
-    final_x = w.xF;
-  } else {
-    float* h = w.preF;
-    const void* pending = nullptr;  // branch output not yet added to h
-    // branch outputs in the operand type in throughput mode (bf16: half the GEMM store burst and 2 of the 14 bytes per
-    // element the LayerNorm moves); the fp32 residual stream h is updated in place by the LayerNorm kernel (sumF)
-    auto ln_add = [&](const float* g_, const float* b_, const void* branch, void* y_op, float* y_f32) -> int {
-      if (pk_enc && y_op)   // pair rows for the products; h (fp32) += branch in place
-        return launch_layernorm(prec, h, 1, rows, D, g_, b_, eps, 0, nullptr, nullptr, s, (const float*)branch, branch ? h : nullptr, y_op, pk_enc);
-      if (!branch) return launch_layernorm(prec, h, 1, rows, D, g_, b_, eps, 0, y_op, y_f32, s, nullptr, nullptr);
-      if (!tmp_f32)  // x = bf16 branch, add = fp32 residual, sumF = residual updated in place
-        return launch_layernorm(prec, branch, 0, rows, D, g_, b_, eps, 0, y_op, y_f32, s, h, y_op ? h : nullptr);
-      return launch_layernorm(y_op ? prec : 0, h, 1, rows, D, g_, b_, eps, 0, y_op ? y_op : (void*)y_f32, nullptr, s,
-                              (const float*)branch, y_op ? h : nullptr);
-    };
-    for (int l = 0; l < c.num_layers; ++l) {
-      const EncLayerW& Lw = e->layers[l];
-      if (int r = ln_add(Lw.ln1g.as<float>(), Lw.ln1b.as<float>(), pending, w.xb, nullptr)) return r;
-      if (int r = gemm_rows(w.xb, D, Lw.wqkv, Lw.bqkv, 3 * D, w.qkv, 0, ACT_NONE, nullptr, qkv_pl)) return r;
-      if (int r = attention()) return r;
-      if (int r = gemm_rows(w.attn_o, D, Lw.wo, Lw.bo, D, tmp, tmp_f32, ACT_NONE, nullptr)) return r;
-      if (int r = ln_add(Lw.ln2g.as<float>(), Lw.ln2b.as<float>(), tmp, w.xb, nullptr)) return r;
-      if (int r = gemm_rows(w.xb, D, Lw.w1, Lw.b1, F, w.ffn, 0, ACT_GELU, nullptr, nullptr, pk_enc ? 1 : 0)) return r;
-      if (int r = gemm_rows(w.ffn, F, Lw.w2, Lw.b2, D, tmp, tmp_f32, ACT_NONE, nullptr)) return r;
-      pending = tmp;
-    }
-    // final LN(h + last FFN branch) -> fp32 (xF is unused in this family when prec == 0 it aliases xb: use qkv space)
-    float* fin = (float*)w.qkv;
-    if (int r = ln_add(e->enc_g.as<float>(), e->enc_b.as<float>(), pending, nullptr, fin)) return r;
-    final_x = fin;
-  }
-  // ---- wrapper's whole-batch output LayerNorm (+ frame head + decode when a head was given) ----
-  const int64_t n_out = rows * D;
-  const double n_out_stat = global_norm ? (double)e->reduce_global_clips * (double)(rows / B) * (double)D : 0.0;
-  rctx.mom = out_mom;
-  if (tail.head) {
-    static_assert(sizeof(svt_frame) == sizeof(FrameOut), "frame layout");
-    if (launch_head_fused(final_x, rows, D, tail.head->w.as<float>(), tail.head->wsum.as<float>(),
-                          tail.head->has_bias ? tail.head->b.as<float>() : nullptr, tail.head->out_f, w.dots,
-                          c.output_norm ? out_mom : nullptr, rows / groups, 1e-5f, tail.logits, (FrameOut*)tail.frames, tail.n_oct,
-                          tail.n_cls, s, n_out_stat, global_norm && c.output_norm ? +reduce_now : nullptr, &rctx,
-                          (char*)w.mom + w.mom_scr[3])) return SVT_ERR_HIP;
-    return SVT_OK;
-  }
-  if (c.output_norm) {
-    if (int r = launch_moments(final_x, n_out / groups, out_mom, (char*)w.mom + w.mom_scr[1], B, s, groups)) return r;
-    if (global_norm) { if (int r = reduce_now(&rctx)) return r; }
-    if (int r = launch_global_norm(final_x, feats, n_out / groups, out_mom, 1e-5f, s, groups, n_out_stat)) return r;
-  } else {
-    if (launch_copy_f32(final_x, feats, n_out, s)) return SVT_ERR_HIP;
-  }
-  return SVT_OK;
-}

@@ -182,11 +182,15 @@ int rca_forward_run(svt_rca* r, const float* audio, int T1, const float* video, 
     // out_proj is linear: alpha*Wo(a_s) + (1-alpha)*Wo(a_c) + bo = Wo(alpha*a_s + (1-alpha)*a_c) + bo
     if (int rc = launch_axpby(prec, att_s, att_c, r->alpha, 1.f - r->alpha, blend, rows * D, s)) return rc;
     if (int rc = gemm_rows(blend, D, L.wo.p, L.bo.as<float>(), D, pre1, 1, ACT_NONE, nullptr)) return rc;
-    if (int rc = launch_layernorm(prec, pre1, 1, rows, D, L.n1g.as<float>(), L.n1b.as<float>(), 1e-6f, 0, xT,
-                                  prec ? xF : nullptr, s, kvF)) return rc;
+    LnArgs n1;   // x = LN(kv + attention branch): operand copy for FFN-1 (+ the fp32 value where that copy is 16-bit)
+    n1.prec = prec; n1.x = pre1; n1.add = kvF; n1.rows = rows; n1.D = D; n1.gamma = L.n1g.as<float>(); n1.beta = L.n1b.as<float>(); n1.eps = 1e-6f;
+    n1.yT = xT; n1.yF = prec ? xF : nullptr;
+    if (int rc = launch_layernorm(n1, s)) return rc;
     if (int rc = gemm_rows(xT, D, L.w1.p, L.b1.as<float>(), F, ffn, 0, ACT_RELU, nullptr)) return rc;
     if (int rc = gemm_rows(ffn, F, L.w2.p, L.b2.as<float>(), D, pre2, 1, ACT_NONE, nullptr)) return rc;
-    if (int rc = launch_layernorm(0, pre2, 1, rows, D, L.n2g.as<float>(), L.n2b.as<float>(), 1e-6f, 0, outF, nullptr, s, xF)) return rc;
+    LnArgs n2;   // out = LN(x + FFN branch), fp32
+    n2.x = pre2; n2.add = xF; n2.rows = rows; n2.D = D; n2.gamma = L.n2g.as<float>(); n2.beta = L.n2b.as<float>(); n2.eps = 1e-6f; n2.yT = outF;
+    if (int rc = launch_layernorm(n2, s)) return rc;
     if (S) {
       const size_t bht = (size_t)B * H * T;
       if (int rc = launch_rca_attn_lse(prec, qkv, 3L * D, kp, 3L * D, B, T, H, dh, scale, S->lse, s)) return rc;

@@ -82,12 +82,7 @@ int bn_fold(const ParamMap& P, const std::string& pre, int C, std::vector<float>
   if (int r = need(P, pre + ".bias", {C}, &b)) return r;
   if (int r = need(P, pre + ".running_mean", {C}, &m)) return r;
   if (int r = need(P, pre + ".running_var", {C}, &var)) return r;
-  scale->resize(C); bias->resize(C);
-  for (int c = 0; c < C; ++c) {
-    const double sc = (double)g->v[c] / std::sqrt((double)var->v[c] + 1e-5);
-    (*scale)[c] = (float)sc;
-    (*bias)[c] = (float)((double)b->v[c] - (double)m->v[c] * sc);
-  }
+  batch_norm_fold(g->v.data(), b->v.data(), m->v.data(), var->v.data(), C, scale, bias);
   return SVT_OK;
 }
 // conv weight (Cout, Cin, k, k) -> [Cout][(ky*k + kx)*Cin + ci] with the BN scale folded
@@ -178,11 +173,6 @@ int upload_vec_rep(const ParamMap& P, const std::string& key, int C, int G, DevB
   std::vector<float> t;
   for (int j = 0; j < G; ++j) t.insert(t.end(), p->v.begin(), p->v.end());
   return upload_f32(*out, t.data(), t.size());
-}
-int upload_vec(const ParamMap& P, const std::string& key, int C, DevBuf* out) {
-  const Param* p = nullptr;
-  if (int r = need(P, key, {C}, &p)) return r;
-  return upload_f32(*out, p->v.data(), p->v.size());
 }
 }  // namespace
 

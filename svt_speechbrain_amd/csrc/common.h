@@ -392,14 +392,26 @@ int launch_head_fused(const float* x, int64_t rows, int K, const float* w, const
 size_t head_scratch_bytes(int64_t rows, int groups_max);
 
 // ---- row LayerNorm (layernorm.hip) ----
-// row LayerNorm over D: in fp32 or operand type; outputs: yT (operand type, may be null) and yF (fp32, may be null)
-// optional `add` (fp32, same shape) is summed into x before the statistics (residual add fused into the norm);
-// `sumF` (optional) receives x + add (the updated residual stream of the pre-LN encoder)
-int launch_layernorm(int prec, const void* x, int x_is_f32, int64_t rows, int D, const float* gamma,
-                     const float* beta, float eps, int gelu, void* yT, float* yF, hipStream_t s,
-                     const float* add = nullptr, float* sumF = nullptr,
-                     void* yP = nullptr, int pair_kind = 0,    // yP: the result as pair rows (split modes; kind 2 = bf16 / 3 = fp16 pieces)
-                     const void* addP = nullptr);              // addP: a second addend given as pair rows (may alias yP: in place)
+// row LayerNorm over D: y = LN(x [+ add] [+ addP]) * gamma + beta [-> GELU]; every output is optional
+struct LnArgs {
+  int prec = 0;               // operand type of yT, and of x when it is not fp32: 0 = fp32, 1 = 16-bit
+  const void* x = nullptr;    // rows x D
+  int x_is_f32 = 1;           // x is fp32 whatever prec says
+  int64_t rows = 0;
+  int D = 0;
+  const float* gamma = nullptr;
+  const float* beta = nullptr;
+  float eps = 1e-5f;
+  int gelu = 0;
+  void* yT = nullptr;         // result in the operand type
+  float* yF = nullptr;        // result in fp32
+  const float* add = nullptr; // fp32, same shape: summed into x before the statistics (residual add fused into the norm)
+  float* sumF = nullptr;      // receives x + add (the updated residual stream of the pre-LN encoder)
+  void* yP = nullptr;         // result as pair rows (split modes; needs fp32 x, prec 0, no yT, D in {512, 768, 1024})
+  int pair_kind = 0;          // of yP / addP: 2 = bf16 pieces, 3 = fp16 pieces
+  const void* addP = nullptr; // a second addend given as pair rows (may alias yP: in place)
+};
+int launch_layernorm(const LnArgs& a, hipStream_t s);
 // post-LN residual stream as a bf16 (hi, lo) pair (throughput mode, D in {512, 768, 1024})
 bool layernorm_hilo_ok(int D);
 // the same LayerNorm with the branch given as `nparts` fp32 partial products + bias (a K-split small GEMM: gemm_skinny.hip, ksplit)

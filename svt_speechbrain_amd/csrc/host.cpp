@@ -2,6 +2,7 @@
 #include "host.h"
 
 #include <algorithm>
+#include <cmath>
 
 namespace svt {
 
@@ -72,6 +73,67 @@ int validate_cfg(const svt_encoder_config& c) {
   if (c.rel_pos_buckets < 0 || c.rel_pos_buckets % 4 || (c.rel_pos_buckets > 0 && c.rel_pos_max_distance <= c.rel_pos_buckets / 4)) {
     set_error("rel_pos_buckets must be a multiple of 4 and rel_pos_max_distance > rel_pos_buckets / 4"); return SVT_ERR_INVALID; }
   return SVT_OK;
+}
+
+// ---- re-layouts and folds of the finalize step (host.h) ----
+
+std::vector<float> tap_major(const float* w, int Co, int Ci, int k) {
+  std::vector<float> wt((size_t)Co * k * Ci);
+  for (int o = 0; o < Co; ++o)
+    for (int ci = 0; ci < Ci; ++ci)
+      for (int j = 0; j < k; ++j) wt[((size_t)o * k + j) * Ci + ci] = w[((size_t)o * Ci + ci) * k + j];
+  return wt;
+}
+
+std::vector<float> tap_minor_slabs(const float* wt, int Co, int Ci, int k) {
+  std::vector<float> wp((size_t)Co * k * Ci);
+  const int nb = Ci / 64;
+  for (int o = 0; o < Co; ++o)
+    for (int cb = 0; cb < nb; ++cb)
+      for (int j = 0; j < k; ++j)
+        std::copy_n(&wt[((size_t)o * k + j) * Ci + (size_t)cb * 64], 64, &wp[((size_t)o * k * nb + (size_t)cb * k + j) * 64]);
+  return wp;
+}
+
+std::vector<float> weight_norm_fold(const float* g, const float* v, size_t n, int kp) {
+  std::vector<double> nrm(kp, 0.0);
+  for (size_t i = 0; i < n; ++i) nrm[i % kp] += (double)v[i] * (double)v[i];
+  for (int j = 0; j < kp; ++j) nrm[j] = std::sqrt(nrm[j]);
+  std::vector<float> w(n);
+  for (size_t i = 0; i < n; ++i) w[i] = (float)((double)g[i % kp] * (double)v[i] / nrm[i % kp]);
+  return w;
+}
+
+void batch_norm_fold(const float* weight, const float* bias, const float* mean, const float* var, int C, std::vector<float>* scale,
+                     std::vector<float>* shift) {
+  scale->resize(C); shift->resize(C);
+  for (int c = 0; c < C; ++c) {
+    const double sc = (double)weight[c] / std::sqrt((double)var[c] + 1e-5);
+    (*scale)[c] = (float)sc;
+    (*shift)[c] = (float)((double)bias[c] - (double)mean[c] * sc);
+  }
+}
+
+void gate_rowsum_fold(const float* w, const float* b, int dh, std::vector<float>* wab, std::vector<float>* bab) {
+  wab->assign((size_t)2 * dh, 0.f); bab->assign(2, 0.f);
+  for (int j = 0; j < 8; ++j) {
+    for (int d = 0; d < dh; ++d) (*wab)[(size_t)(j / 4) * dh + d] += w[(size_t)j * dh + d];
+    (*bab)[j / 4] += b[j];
+  }
+}
+
+void posconv_multiframe(const float* w, const float* bias, int G, int cg, int kp, int Pf, std::vector<float>* wP, std::vector<float>* bP) {
+  const size_t Np = (size_t)Pf * cg, Kp = (size_t)(kp + Pf - 1) * cg;
+  wP->assign((size_t)G * Np * Kp, 0.f); bP->resize((size_t)G * Np);
+  for (int g = 0; g < G; ++g)
+    for (int j = 0; j < Pf; ++j)
+      for (int co = 0; co < cg; ++co) {
+        const int o = g * cg + co;
+        (*bP)[(size_t)g * Np + (size_t)j * cg + co] = bias[o];
+        float* row = wP->data() + ((size_t)g * Np + (size_t)j * cg + co) * Kp;
+        for (int k = 0; k < kp; ++k)
+          for (int ci = 0; ci < cg; ++ci) row[(size_t)(k + j) * cg + ci] = w[((size_t)o * cg + ci) * kp + k];
+      }
 }
 
 }  // namespace svt

@@ -1,5 +1,6 @@
 // Host-only part of the library: routines that never touch the GPU -- the error string behind svt_last_error(), parameter intake by
-// key (svt_*_load_param), configuration validation (svt_encoder_create) and the frames -> notes scan (svt_frames_to_notes).  Plain
+// key (svt_*_load_param), configuration validation (svt_encoder_create), the weight re-layouts and folds of svt_*_finalize and the
+// frames -> notes scan (svt_frames_to_notes).  Plain
 // C++17 with no HIP header, so the same translation unit is compiled twice: by hipcc into libsvt_mi355*.so, and by g++ with
 // -fsanitize=address,undefined into the CPU test binary of `make san` (tests/test_host_sanitizers.py drives it with the reference's
 // frame2note fixture and hostile arguments).  Sanitizers run on the CPU build only.
@@ -26,6 +27,24 @@ int load_param_into(ParamMap& m, const char* key, const void* data, int dtype, c
 const Param* find(const ParamMap& m, const std::string& k);
 int need(const ParamMap& m, const std::string& k, std::vector<int64_t> shape, const Param** out);
 int validate_cfg(const svt_encoder_config& c);
+
+// ---- re-layouts and folds of the finalize step: pure index arithmetic on host floats (tests/test_host_sanitizers.py runs each) ----
+// conv weight (Co, Ci, k) -> (Co, k*Ci) tap-major: the implicit-GEMM row of output frame t is then the contiguous channels-last slice
+// x[t*s : t*s+k, :]
+std::vector<float> tap_major(const float* w, int Co, int Ci, int k);
+// a tap-major (Co, k*Ci) matrix with its K axis in TAP-MINOR slab order: slab g = tap g % k of channels [(g / k) * 64, + 64); Ci % 64 == 0
+std::vector<float> tap_minor_slabs(const float* wt, int Co, int Ci, int k);
+// weight-norm over dim 2 of v (.., kp), n elements: W[.., j] = g[j] v[.., j] / ||v[.., j]||_F, norms and quotient in fp64
+std::vector<float> weight_norm_fold(const float* g, const float* v, size_t n, int kp);
+// eval-mode BatchNorm (eps 1e-5, the torch.nn.BatchNorm*d default) -> y = scale x + shift per channel, folded in fp64
+void batch_norm_fold(const float* weight, const float* bias, const float* mean, const float* var, int C, std::vector<float>* scale,
+                     std::vector<float>* shift);
+// WavLM gate: gate = a (b const - 1) + 2, a / b = sigmoid of the sums of rows 0-3 / 4-7 of gru_rel_pos_linear (w: 8 x dh, b: 8):
+// the row sums, wab (2 x dh) and bab (2), added in fp32 in row order
+void gate_rowsum_fold(const float* w, const float* b, int dh, std::vector<float>* wab, std::vector<float>* bab);
+// multi-frame form of the grouped positional conv w (G*cg, cg, kp): Pf consecutive output frames per GEMM row.  wP is G x Pf*cg x
+// (kp+Pf-1)*cg -- row j*cg+co of a group holds filter co shifted by j taps, zero elsewhere -- and bP (G x Pf*cg) repeats the bias
+void posconv_multiframe(const float* w, const float* bias, int G, int cg, int kp, int Pf, std::vector<float>* wP, std::vector<float>* bP);
 
 #ifdef SVT_OPERAND_F16
 // the IEEE-half build serves the exact fp32 mode and the 16-bit throughput mode; the split-operand engines live in the bf16 build

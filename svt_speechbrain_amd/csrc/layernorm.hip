@@ -174,9 +174,14 @@ template <class F> void ln_width(int D, F&& f) {
 }
 }  // namespace
 int g_ln_two_rows = 1;   // svt_debug_set key 20: 0 = one row per wave in the (hi, lo) and 16-bit-row LayerNorms (A/B)
-int launch_layernorm(int prec, const void* x, int x_is_f32, int64_t rows, int D, const float* gamma,
-                     const float* beta, float eps, int gelu, void* yT, float* yF, hipStream_t s, const float* add,
-                     float* sumF, void* yP, int pair_kind, const void* addP) {
+int launch_layernorm(const LnArgs& a, hipStream_t s) {
+  const int prec = a.prec, x_is_f32 = a.x_is_f32, D = a.D, gelu = a.gelu, pair_kind = a.pair_kind;
+  const void *const x = a.x, *const addP = a.addP;
+  const int64_t rows = a.rows;
+  const float *const gamma = a.gamma, *const beta = a.beta, *const add = a.add;
+  const float eps = a.eps;
+  void *const yT = a.yT, *const yP = a.yP;
+  float *const yF = a.yF, *const sumF = a.sumF;
   if (addP && !yP) { set_error("layernorm: a pair-row addend needs the pair-row output form"); return -1; }
   const dim3 grid((unsigned)((rows + 3) / 4)), grid2((unsigned)((rows + 7) / 8)), block(256);
   const bool wide = D == 512 || D == 768 || D == 1024;

@@ -3,6 +3,9 @@
 //   host_san_test notes <frames.bin> <B> <T> <onset> <offset> <frame_size> [capacity]   -> one line per note: "b t_on t_off pitch lo hi"
 //                                                          (frames.bin: B * T records of {f32 p_on, f32 p_off, i32 octave, i32 class})
 //   host_san_test hostile                                   -> every refusal path of the four routines; prints "hostile ok"
+//   host_san_test fold <op> <out.bin> <dims...> <in.bin...>  -> a re-layout / fold of the finalize step on raw float32 files:
+//       tap_major | tap_minor Co Ci k w;  weight_norm n kp g v;  batch_norm C weight bias mean var -> scale, shift;
+//       gate dh w b -> wab, bab;  multiframe G cg kp Pf w bias -> wP, bP
 #include "../../svt_speechbrain_amd/csrc/host.h"
 
 #include <cstdio>
@@ -43,6 +46,55 @@ static int run_notes(int argc, char** argv) {
     for (long k = 0; k < n[b]; ++k)
       std::printf("%d %.17g %.17g %d %d %d\n", b, t_on[b * cap + k], t_off[b * cap + k], pitch[b * cap + k], lo[b * cap + k], hi[b * cap + k]);
   return 0;
+}
+
+static bool read_f32(const char* path, size_t n, std::vector<float>* v) {
+  v->resize(n);   // exact size: a read past the tensor lands in a red zone
+  FILE* f = std::fopen(path, "rb");
+  if (!f) return false;
+  const size_t got = std::fread(v->data(), sizeof(float), n, f);
+  const bool at_end = std::fgetc(f) == EOF;
+  std::fclose(f);
+  return got == n && at_end;
+}
+
+// fold <op> <out.bin> <dims...> <in.bin...>: one re-layout / fold of the finalize step on raw float32 files; two results are written
+// one after the other
+static int run_fold(int argc, char** argv) {
+  if (argc < 4) return 2;
+  const std::string op = argv[2];
+  bool dims_ok = true;   // every dimension is 1 .. 4096 and a tensor at most 2^28 elements: anything else (a sign, no number) is refused
+  auto dim = [&](int i) { const int v = i < argc ? std::atoi(argv[i]) : 0; if (v < 1 || v > 4096) dims_ok = false; return v; };
+  auto in = [&](int i, size_t n, std::vector<float>* v) { return dims_ok && n <= ((size_t)1 << 28) && i < argc && read_f32(argv[i], n, v); };
+  std::vector<float> a, b, c, d, out, out2;
+  if (op == "tap_major" || op == "tap_minor") {          // Co Ci k w
+    const int Co = dim(4), Ci = dim(5), k = dim(6);
+    if (!in(7, (size_t)Co * Ci * k, &a)) return 2;
+    out = tap_major(a.data(), Co, Ci, k);
+    if (op == "tap_minor") out = tap_minor_slabs(out.data(), Co, Ci, k);
+  } else if (op == "weight_norm") {                       // n kp g v
+    const int n = dim(4), kp = dim(5);
+    if (!in(6, (size_t)kp, &a) || !in(7, (size_t)n, &b)) return 2;
+    out = weight_norm_fold(a.data(), b.data(), (size_t)n, kp);
+  } else if (op == "batch_norm") {                        // C weight bias mean var
+    const int C = dim(4);
+    if (!in(5, C, &a) || !in(6, C, &b) || !in(7, C, &c) || !in(8, C, &d)) return 2;
+    batch_norm_fold(a.data(), b.data(), c.data(), d.data(), C, &out, &out2);
+  } else if (op == "gate") {                              // dh w b
+    const int dh = dim(4);
+    if (!in(5, (size_t)8 * dh, &a) || !in(6, 8, &b)) return 2;
+    gate_rowsum_fold(a.data(), b.data(), dh, &out, &out2);
+  } else if (op == "multiframe") {                        // G cg kp Pf w bias
+    const int G = dim(4), cg = dim(5), kp = dim(6), Pf = dim(7);
+    if (!in(8, (size_t)G * cg * cg * kp, &a) || !in(9, (size_t)G * cg, &b)) return 2;
+    posconv_multiframe(a.data(), b.data(), G, cg, kp, Pf, &out, &out2);
+  } else return 2;
+  FILE* f = std::fopen(argv[3], "wb");
+  if (!f) return 2;
+  bool ok = true;
+  for (const std::vector<float>* v : {&out, &out2})
+    if (!v->empty()) ok = ok && std::fwrite(v->data(), sizeof(float), v->size(), f) == v->size();
+  return std::fclose(f) == 0 && ok ? 0 : 2;
 }
 
 static svt_encoder_config good_cfg() {
@@ -129,6 +181,7 @@ static int run_hostile() {
 int main(int argc, char** argv) {
   if (argc >= 2 && !std::strcmp(argv[1], "notes")) return run_notes(argc, argv);
   if (argc >= 2 && !std::strcmp(argv[1], "hostile")) return run_hostile();
-  std::fprintf(stderr, "usage: host_san_test notes <frames.bin> B T onset offset frame_size [capacity] | hostile\n");
+  if (argc >= 2 && !std::strcmp(argv[1], "fold")) return run_fold(argc, argv);
+  std::fprintf(stderr, "usage: host_san_test notes <frames.bin> B T onset offset frame_size [capacity] | hostile | fold <op> <out.bin> dims... in.bin...\n");
   return 2;
 }
