@@ -338,6 +338,56 @@ typedef struct svt_debug_gemm_desc {
 } svt_debug_gemm_desc;
 int svt_debug_gemm_batched(int32_t precision, const svt_debug_gemm_desc* d, int device, void* stream);
 
+/* ---- test hook: one launch of a row LayerNorm launcher (csrc/layernorm.hip) on caller-supplied device buffers; tests/test_gpu_layernorm.py ----
+ * y = LN(t) gamma + beta [-> GELU] over the D columns of each of `rows` rows; the descriptor holds the union of the three launchers'
+ * arguments, and `form` says which one runs (fields of another form are ignored):
+ *   form 0  launch_layernorm: t = x [+ add] [+ addP].  prec 0 / 1 = fp32 / the build's 16-bit type for yT, and for x unless x_is_f32;
+ *           every output is optional: yT (type of prec), yF (fp32), sumF (fp32, receives t), yP (pair rows: every 32 consecutive elements
+ *           as 64 bytes of hi pieces then 64 bytes of lo pieces in the 128 bytes of the fp32 slab they replace; pair_kind 2 = bf16 pieces,
+ *           3 = IEEE-half pieces; needs fp32 x, prec 0, no yT, D in {512, 768, 1024}); add fp32; addP pair rows (needs yP; may alias it).
+ *   form 1  launch_layernorm_hilo: (yh, yl) = cut(LN(t)), 16-bit planes of the build's type, yF (optional) the fp32 result;
+ *           t = x32 (fp32; rh, rl NULL), or t = (rh + rl) [+ branch] with rh, rl, branch 16-bit (x32 NULL).  D in {512, 768, 1024}.
+ *   form 2  launch_layernorm_hilo_parts: t = (rh + rl) + rn16(parts[0] + ... + parts[nparts - 1] + pbias): `nparts` fp32 partial
+ *           products (rows, D), part_stride elements apart, pbias (D) fp32.  D in {512, 768, 1024}.
+ * gamma, beta (D) fp32.  In-place use as the callers have it is allowed: x == sumF, x == yT, add == yF, add == sumF, addP == yP,
+ * yh == rh with yl == rl.
+ * The hook is NARROWER than the launchers in one respect: it refuses (SVT_ERR_INVALID, nothing is launched) whatever they leave to their
+ * callers, so that no argument can send a kernel outside the buffers it was given -- rows < 1, D < 1, a NULL gamma / beta / x, prec 0
+ * with a 16-bit x, forms 1 / 2 with D outside {512, 768, 1024} or without yh / yl, form 1 without exactly one of {x32} and {rh, rl},
+ * nparts < 1 or parts closer than rows * D elements, and ANY non-NULL pointer that is not 16-byte aligned (128-byte for yP / addP).
+ * The unaligned fall-backs of launch_layernorm are therefore not reachable through it; the one-row (hi, lo) kernel is reached with
+ * svt_debug_set key 20 = 0.  A launcher's own refusal comes back as SVT_ERR_INVALID too.  struct_size = the size of the structure.
+ * svt_debug_set(40, 0) says which kernel the launch chose. */
+typedef struct svt_debug_layernorm_desc {
+  int32_t struct_size;
+  int32_t form;
+  int32_t prec, x_is_f32;
+  int64_t rows;
+  int32_t D, gelu;
+  float eps;
+  int32_t pair_kind;
+  const float* gamma;
+  const float* beta;
+  const void* x;
+  void* yT;
+  float* yF;
+  const float* add;
+  float* sumF;
+  void* yP;
+  const void* addP;
+  const void* branch;
+  const void* rh;
+  const void* rl;
+  const float* x32;
+  void* yh;
+  void* yl;
+  const float* parts;
+  const float* pbias;
+  int64_t part_stride;
+  int32_t nparts;
+} svt_debug_layernorm_desc;
+int svt_debug_layernorm(const svt_debug_layernorm_desc* d, int device, void* stream);
+
 /* ---- AV-HuBERT lip front-end: replaces SubModel / ResEncoder of N20EMv2/video_only/resnet.py:134-187 (the
  * `feature_extractor_video` of the AV-HuBERT model, hubert.py:344-346): 3-D stem + ResNet-18 trunk (PReLU) + Linear(512,
  * embed_dim), eval mode.  Parameter keys are SubModel.state_dict() keys ("resnet.frontend3D.0.weight", "resnet.trunk.layer1.0.
@@ -511,8 +561,14 @@ int svt_debug_rca_attn_bwd(int32_t precision, const void* qkv, const void* qc, c
  * gemm_kernel (128, or 256 for its 256 x 64 form; + 10000 for a split-operand instantiation), 3 = gemm_pp8_kernel (64 / 128 / 192 /
  * 256), 4 = gemm_pers_kernel, 5 = gemm_pps_kernel, 6 = gemm_p1w_kernel, 7 = gemm_x3s_kernel (256; 192 names its 192-column form),
  * 8 = gemm_x3p_kernel, 9 = gemm_x3q_kernel, 10 = gemm_p1x_kernel (tests/test_gpu_gemm_kernels.py and tests/test_gpu_gemm.py assert
- * the id of every case).
- * Returns 0 (keys 24, 31: the count; keys 38, 39: the id), SVT_ERR_INVALID for an unknown key or a value a key does not accept (21, 28, 30, 37 above). */
+ * the id of every case), 40 = query: returns which kernel the last row LayerNorm launch of this process chose (value ignored; 0 = none
+ * yet; set on the host by every branch of the three launchers of csrc/layernorm.hip) as 1000 * kernel + instantiation:
+ * 1000 + 10 * (16-bit x) + (16-bit yT) = layernorm_kernel<float, float> 1000, <float, 16-bit> 1001, <16-bit, 16-bit> 1011;
+ * 2000 + 100 * PK + 10 * (16-bit x) + (16-bit yT) = layernorm_f32_vec_kernel<VPT, float> 2000, <VPT, 16-bit> 2001, <VPT, 16-bit, 16-bit>
+ * 2011, <VPT, float, float, 2> 2200 (pair rows, bf16 pieces), <VPT, float, float, 3> 2300 (pair rows, IEEE-half pieces);
+ * 3000 = layernorm_op16_rows2_kernel; 4000 = layernorm_hilo_kernel; 5000 = layernorm_hilo2_kernel, 5001 = its PARTS instantiation;
+ * 6000 = layernorm_f32_to_hilo_kernel (tests/test_gpu_layernorm.py asserts the id of every case).
+ * Returns 0 (keys 24, 31: the count; keys 38, 39, 40: the id), SVT_ERR_INVALID for an unknown key or a value a key does not accept (21, 28, 30, 37 above). */
 int svt_debug_set(int key, int value);
 
 /* ---- measurement hook: HIP-event timing of the dominant kernel on the stream it runs on ----

@@ -70,6 +70,25 @@ class GemmDescC(C.Structure):
     ]
 
 
+class LayerNormDescC(C.Structure):
+    """svt_debug_layernorm_desc: one launch of a row LayerNorm launcher (svt_debug_layernorm); form 0 / 1 / 2, device pointers."""
+    _fields_ = [
+        ("struct_size", C.c_int32),
+        ("form", C.c_int32),
+        ("prec", C.c_int32), ("x_is_f32", C.c_int32),
+        ("rows", C.c_int64),
+        ("D", C.c_int32), ("gelu", C.c_int32),
+        ("eps", C.c_float),
+        ("pair_kind", C.c_int32),
+        ("gamma", C.c_void_p), ("beta", C.c_void_p),
+        ("x", C.c_void_p), ("yT", C.c_void_p), ("yF", C.c_void_p), ("add", C.c_void_p), ("sumF", C.c_void_p), ("yP", C.c_void_p), ("addP", C.c_void_p),
+        ("branch", C.c_void_p), ("rh", C.c_void_p), ("rl", C.c_void_p), ("x32", C.c_void_p), ("yh", C.c_void_p), ("yl", C.c_void_p),
+        ("parts", C.c_void_p), ("pbias", C.c_void_p),
+        ("part_stride", C.c_int64),
+        ("nparts", C.c_int32),
+    ]
+
+
 class FrameC(C.Structure):
     _fields_ = [("p_on", C.c_float), ("p_off", C.c_float), ("octave", C.c_int32), ("pitch_class", C.c_int32)]
 
@@ -121,6 +140,7 @@ SYMBOLS = {
     "svt_debug_gemm": (C.c_int, [C.c_int32, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64,
                                  C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int, _P]),
     "svt_debug_gemm_batched": (C.c_int, [C.c_int32, C.POINTER(GemmDescC), C.c_int, _P]),
+    "svt_debug_layernorm": (C.c_int, [C.POINTER(LayerNormDescC), C.c_int, _P]),
     "svt_debug_attention_scores": (C.c_int, [C.c_int32, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64,
                                              C.c_int64, C.c_float, _P, _P, C.c_int, _P]),
     "svt_debug_gemm_pairs": (C.c_int, [C.c_int32, _P, C.c_int64, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64,

@@ -378,6 +378,49 @@ int svt_debug_gemm_batched(int32_t precision, const svt_debug_gemm_desc* d, int 
   return rc ? SVT_ERR_INVALID : SVT_OK;
 }
 
+int svt_debug_layernorm(const svt_debug_layernorm_desc* d, int device, void* stream) {
+  auto refuse = [](const char* why) { set_error(std::string("svt_debug_layernorm: ") + why); return SVT_ERR_INVALID; };
+  auto aligned = [](unsigned mask, auto... p) { return !((... | (uintptr_t)p) & mask); };   // a null pointer passes
+  if (!d || d->struct_size != (int32_t)sizeof(svt_debug_layernorm_desc)) return refuse("struct_size");
+  if (d->form < 0 || d->form > 2) return refuse("form is 0, 1 or 2");
+  if (d->rows < 1 || d->D < 1) return refuse("rows and D must be positive");
+  if (!d->gamma || !d->beta) return refuse("null gamma / beta");
+  // what the launchers leave to their callers (the header says why the hook is narrower): decided here, before anything is launched
+  const bool hilo_width = d->D == 512 || d->D == 768 || d->D == 1024;
+  if (d->form == 0) {
+    if (!d->x) return refuse("null x");
+    if (!d->prec && !d->x_is_f32) return refuse("a 16-bit x needs prec 1");
+    if (!aligned(15, d->gamma, d->beta, d->x, d->yT, d->yF, d->add, d->sumF) || !aligned(127, d->yP, d->addP))
+      return refuse("every buffer 16-byte aligned, yP / addP 128-byte aligned");
+  } else {
+    if (!hilo_width) return refuse("the (hi, lo) forms need D in {512, 768, 1024}");
+    if (!d->yh || !d->yl) return refuse("null yh / yl");
+    if (!aligned(15, d->gamma, d->beta, d->branch, d->rh, d->rl, d->x32, d->yh, d->yl, d->yF, d->parts, d->pbias))
+      return refuse("every buffer 16-byte aligned");
+    if (d->form == 1 && !(d->x32 ? !d->rh && !d->rl : d->rh && d->rl)) return refuse("form 1 takes exactly one of x32 and (rh, rl)");
+    if (d->form == 2 && (!d->rh || !d->rl)) return refuse("form 2 needs rh and rl");
+    if (d->form == 2 && (d->nparts < 1 || (d->nparts > 1 && d->part_stride < d->rows * d->D))) return refuse("nparts >= 1, parts rows * D elements apart or more");
+  }
+  if (int r = check_device(device)) return r;
+  SVT_HIP(hipSetDevice(device));
+  hipStream_t s = (hipStream_t)stream;
+  int rc;
+  if (d->form == 0) {
+    LnArgs a;
+    a.prec = d->prec; a.x = d->x; a.x_is_f32 = d->x_is_f32; a.rows = d->rows; a.D = d->D; a.gamma = d->gamma; a.beta = d->beta;
+    a.eps = d->eps; a.gelu = d->gelu; a.yT = d->yT; a.yF = d->yF; a.add = d->add; a.sumF = d->sumF; a.yP = d->yP;
+    a.pair_kind = d->pair_kind; a.addP = d->addP;
+    rc = launch_layernorm(a, s);
+  } else if (d->form == 1) {
+    rc = launch_layernorm_hilo((const bf16_t*)d->branch, (const bf16_t*)d->rh, (const bf16_t*)d->rl, d->x32, d->rows, d->D, d->gamma,
+                               d->beta, d->eps, (bf16_t*)d->yh, (bf16_t*)d->yl, d->yF, s);
+  } else {
+    rc = launch_layernorm_hilo_parts(d->parts, d->nparts, (long)d->part_stride, d->pbias, (const bf16_t*)d->rh, (const bf16_t*)d->rl,
+                                     d->rows, d->D, d->gamma, d->beta, d->eps, (bf16_t*)d->yh, (bf16_t*)d->yl, d->yF, s);
+  }
+  return rc ? SVT_ERR_INVALID : SVT_OK;
+}
+
 int svt_debug_gemm_pairs(int32_t precision, const float* a, int64_t a_elems, const float* w, float* c, const float* bias, int32_t m,
                          int32_t n, int32_t k, int32_t a_rpb, int64_t a_bstride, int64_t a_rstride, int32_t act, int32_t out_kind,
                          int device, void* stream, int32_t time_iters, float* ms_out) {
@@ -560,6 +603,7 @@ int svt_debug_set(int key, int value) {
   else if (key == 37) { if (value < 8 || value > 256 || value % 8) { set_error("svt_debug_set(37): 8 .. 256, a multiple of 8"); return SVT_ERR_INVALID; } g_gemm_persist_wgs = value; }
   else if (key == 38) return g_flash_kernel_id;
   else if (key == 39) return g_gemm_kernel_id;
+  else if (key == 40) return g_ln_kernel_id;
   else { set_error("svt_debug_set: unknown key"); return SVT_ERR_INVALID; }
   return SVT_OK;
 }

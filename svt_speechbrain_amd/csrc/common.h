@@ -340,6 +340,7 @@ extern int g_gemm_persist_wgs;   // key 37: workgroups of a persistent GEMM laun
 extern int g_gemm_kernel_id;     // key 39 (query): 1000 * family + tile rows of the kernel the last product ran on (gemm_dispatch.hip)
 
 extern int g_ln_two_rows;  // (hi, lo) LayerNorm: half a wave per row, 16-byte accesses (1, default) or a wave per row (0)
+extern int g_ln_kernel_id;  // key 40 (query): which LayerNorm kernel and instantiation the last launch chose (layernorm.hip)
 extern int g_flash_wide;  // fused attention: 8-wave (256-query) workgroups for head_dim 64 (1, default) or 4-wave ones (0)
 extern int g_flash_kernel_id;  // fused attention: id of the kernel the last launch chose (attention_bf16.hip; svt_debug_set key 38)
 extern int g_ffn2_ksplit;   // svt_debug_set key 36 (api_encoder.hip): FFN-2 of a small batch as a K-split small GEMM + summing LayerNorm

@@ -174,6 +174,7 @@ template <class F> void ln_width(int D, F&& f) {
 }
 }  // namespace
 int g_ln_two_rows = 1;   // svt_debug_set key 20: 0 = one row per wave in the (hi, lo) and 16-bit-row LayerNorms (A/B)
+int g_ln_kernel_id = 0;  // svt_debug_set key 40 (query): 1000 * kernel + instantiation of the last launch (include/svt_mi355.h lists the ids)
 int launch_layernorm(const LnArgs& a, hipStream_t s) {
   const int prec = a.prec, x_is_f32 = a.x_is_f32, D = a.D, gelu = a.gelu, pair_kind = a.pair_kind;
   const void *const x = a.x, *const addP = a.addP;
@@ -188,6 +189,7 @@ int launch_layernorm(const LnArgs& a, hipStream_t s) {
   if (yP) {
     // split-operand modes: the result leaves as pair rows (and optionally as fp32: yF / sumF) -- fp32 input, D in {512, 768, 1024}
     if (prec || !x_is_f32 || yT || !wide || (pair_kind != 2 && pair_kind != 3) || !aligned(15, x, yF, add, sumF, gamma, beta) || !aligned(127, yP)) { set_error("layernorm: the pair-row output needs an fp32 input, D in {512, 768, 1024} and aligned buffers"); return -1; }
+    g_ln_kernel_id = pair_kind == 3 ? 2300 : 2200;
     ln_width(D, [&](auto vpt) {
       constexpr int VPT = decltype(vpt)::value;
       if (pair_kind == 3) hipLaunchKernelGGL((layernorm_f32_vec_kernel<VPT, float, float, 3>), grid, block, 0, s, (const float*)x, add, sumF, rows, gamma, beta, eps, gelu, (float*)nullptr, yF, yP, addP);
@@ -195,11 +197,13 @@ int launch_layernorm(const LnArgs& a, hipStream_t s) {
     });
   } else if (prec && !x_is_f32 && wide && yT && !yF && !add && !sumF && g_ln_two_rows && aligned(15, x, yT, gamma, beta)) {
     // 16-bit rows in, 16-bit rows out (in place for the conv stack of the layer-norm extractor): half a wave per row
+    g_ln_kernel_id = 3000;
     ln_width(D, [&](auto vpt) {
       hipLaunchKernelGGL((layernorm_op16_rows2_kernel<64 * decltype(vpt)::value>), grid2, block, 0, s, (const bf16_t*)x, rows, gamma, beta, eps, gelu, (bf16_t*)yT);
     });
   } else if (prec && !x_is_f32 && wide && aligned(7, x) && aligned(15, yT, yF, add, sumF)) {
     // bf16 branch output + fp32 residual (throughput mode)
+    g_ln_kernel_id = 2011;
     ln_width(D, [&](auto vpt) {
       hipLaunchKernelGGL((layernorm_f32_vec_kernel<decltype(vpt)::value, bf16_t, bf16_t>), grid, block, 0, s, (const bf16_t*)x, add, sumF, rows, gamma, beta, eps, gelu, (bf16_t*)yT, yF);
     });
@@ -207,16 +211,20 @@ int launch_layernorm(const LnArgs& a, hipStream_t s) {
     set_error("layernorm: the addend form needs an fp32 input (or bf16 with D in {512,768,1024})");
     return -1;
   } else if (x_is_f32 && wide && aligned(15, x, yT, yF, gamma, beta, add, sumF)) {
+    g_ln_kernel_id = prec ? 2001 : 2000;
     ln_width(D, [&](auto vpt) {
       constexpr int VPT = decltype(vpt)::value;
       if (prec) hipLaunchKernelGGL((layernorm_f32_vec_kernel<VPT, bf16_t>), grid, block, 0, s, (const float*)x, add, sumF, rows, gamma, beta, eps, gelu, (bf16_t*)yT, yF);
       else hipLaunchKernelGGL((layernorm_f32_vec_kernel<VPT, float>), grid, block, 0, s, (const float*)x, add, sumF, rows, gamma, beta, eps, gelu, (float*)yT, yF);
     });
   } else if (!prec) {
+    g_ln_kernel_id = 1000;
     hipLaunchKernelGGL((layernorm_kernel<float, float>), grid, block, 0, s, (const float*)x, add, sumF, rows, D, gamma, beta, eps, gelu, (float*)yT, yF);
   } else if (x_is_f32) {
+    g_ln_kernel_id = 1001;
     hipLaunchKernelGGL((layernorm_kernel<float, bf16_t>), grid, block, 0, s, (const float*)x, add, sumF, rows, D, gamma, beta, eps, gelu, (bf16_t*)yT, yF);
   } else {
+    g_ln_kernel_id = 1011;
     hipLaunchKernelGGL((layernorm_kernel<bf16_t, bf16_t>), grid, block, 0, s, (const bf16_t*)x, add, sumF, rows, D, gamma, beta, eps, gelu, (bf16_t*)yT, yF);
   }
   SVT_LAUNCH_CHECK();
@@ -390,6 +398,7 @@ int launch_layernorm_hilo_parts(const float* parts, int nparts, long part_stride
                                 int D, const float* gamma, const float* beta, float eps, bf16_t* yh, bf16_t* yl, float* yF, hipStream_t s) {
   if (!parts || nparts < 1 || !pbias || !(D == 512 || D == 768 || D == 1024) || (part_stride & 3) || !aligned(15, parts, pbias, rh, rl, yh, yl, yF, gamma, beta)) { set_error("layernorm (K-split branch): D in {512, 768, 1024} and 16-byte aligned buffers"); return -1; }
   const dim3 grid2((unsigned)((rows + 7) / 8)), block(256);
+  g_ln_kernel_id = 5001;
   ln_width(D, [&](auto vpt) {
     hipLaunchKernelGGL((layernorm_hilo2_kernel<64 * decltype(vpt)::value, true>), grid2, block, 0, s, nullptr, rh, rl, rows, gamma, beta, eps, yh, yl, yF, parts, nparts, part_stride, pbias);
   });
@@ -400,6 +409,7 @@ int launch_layernorm_hilo_parts(const float* parts, int nparts, long part_stride
 int launch_layernorm_hilo(const bf16_t* branch, const bf16_t* rh, const bf16_t* rl, const float* x32, int64_t rows, int D,
                           const float* gamma, const float* beta, float eps, bf16_t* yh, bf16_t* yl, float* yF, hipStream_t s) {
   const dim3 grid((unsigned)((rows + 3) / 4)), grid2((unsigned)((rows + 7) / 8)), block(256);
+  g_ln_kernel_id = x32 ? 6000 : g_ln_two_rows && aligned(15, branch, rh, rl, yh, yl, yF, gamma, beta) ? 5000 : 4000;
   ln_width(D, [&](auto vpt) {
     constexpr int VPT = decltype(vpt)::value;
     if (x32) hipLaunchKernelGGL((layernorm_f32_to_hilo_kernel<VPT>), grid, block, 0, s, x32, rows, gamma, beta, eps, yh, yl);
