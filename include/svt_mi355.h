@@ -282,6 +282,65 @@ int svt_resample(const float* in_dev, int32_t rows, int64_t n_in, int64_t ld_in,
                  int32_t P, int32_t W, int32_t S, float* out_dev, int64_t n_out, int64_t ld_out, int32_t downmix, int device,
                  void* stream);
 
+/* ---- wav files: replaces torchaudio.info / load / save and speechbrain.dataio.dataio.read_audio / write_audio for RIFF/WAVE files
+ * (MIR_ST500/prepare_benchmarks.py:58, N20EMv2/audio_visual/synthesis_noise.py, MIR_ST500/train_audio_ssl.py:373-390) ----
+ * The host parses and writes the header (no device call); the sample conversion runs on the GPU on the raw bytes of the file.
+ *
+ * svt_wav_parse walks the chunks of a file of file_bytes bytes of which head_host holds the first head_bytes (0 <= head_bytes <=
+ * file_bytes; nothing past head_bytes is read).  LIST / JUNK / bext / fact and any other chunk before or after `fmt ` is skipped, with the pad
+ * byte after an odd size.  Returns SVT_OK and fills *out once the header of the `data` chunk has been seen; SVT_WAV_NEED_MORE (positive)
+ * with *need_bytes > head_bytes, a prefix length that gets further, when the prefix ends before that (out is not written; need_bytes
+ * may be NULL otherwise); SVT_ERR_INVALID with a text that begins "svt_wav_parse" and out untouched for everything else.
+ * Accepted: WAVE_FORMAT_PCM (1) at 8 / 16 / 24 / 32 bits, WAVE_FORMAT_IEEE_FLOAT (3) at 32 / 64 bits, WAVE_FORMAT_EXTENSIBLE (0xFFFE) whose
+ * sub-format GUID is one of those two and whose valid bits equal the container size; 1..8 channels; block_align == channels * bits / 8.
+ * frames = data bytes / block_align (a trailing partial frame is dropped); a data size of 0 or 0xFFFFFFFF (streamed writers) or one that
+ * runs past file_bytes is taken as "to the end of the file".  Refused: RIFX, RF64, W64, A-law, mu-law, ADPCM and every other tag, `data`
+ * before `fmt `, zero channels or rate, a chunk or header cut by the end of the file.
+ *
+ * svt_wav_header writes the header of a file of `frames` frames into out_host (capacity bytes) and its length into *header_bytes: for
+ * SVT_PCM_S16 the canonical 44 bytes, for SVT_PCM_F32 tag 3 with an 18-byte `fmt ` (cbSize 0) and a `fact` chunk, 58 bytes (the RIFF
+ * specification's form for non-PCM data).  Other formats, channels outside 1..8, sample_rate < 1, frames < 0, a smaller capacity and
+ * data beyond 4 GiB - 1 - header: SVT_ERR_INVALID.  svt_wav_parse of its output returns its arguments. */
+typedef enum { SVT_PCM_U8 = 1, SVT_PCM_S16 = 2, SVT_PCM_S24 = 3, SVT_PCM_S32 = 4, SVT_PCM_F32 = 5, SVT_PCM_F64 = 6 } svt_pcm_format;
+#define SVT_WAV_NEED_MORE 1
+typedef struct svt_wav_info {
+  int32_t format;            /* svt_pcm_format */
+  int32_t channels;
+  int32_t sample_rate;
+  int32_t bits_per_sample;
+  int32_t block_align;       /* bytes per frame */
+  int64_t data_offset;       /* byte offset of the first frame in the file */
+  int64_t frames;
+} svt_wav_info;
+int svt_wav_parse(const void* head_host, int64_t head_bytes, int64_t file_bytes, svt_wav_info* out, int64_t* need_bytes);
+int svt_wav_header(int32_t format, int32_t channels, int32_t sample_rate, int64_t frames, void* out_host, int64_t capacity,
+                   int64_t* header_bytes);
+
+/* svt_pcm_decode: `frames` interleaved little-endian frames of `channels` samples at src_dev, at ANY byte alignment (an offset into a
+ * 24-bit stereo file is a multiple of 6), to planar fp32: row c of out_dev, at pitch ld_out >= frames, holds channel c; with downmix
+ * != 0 (2 channels only) the one row 0.5f * (l + r), the `.mean(dim=0)` of the preparation scripts: one rounding for the sum and an
+ * exact halving.  Every value is the fp32 nearest (ties to even) to the exact one: U8 (b - 128) / 128, S16 x / 2^15, S24 x / 2^23 (all
+ * three exact), S32 x / 2^31 (the one rounding of the int -> float conversion, then an exact scale: INT32_MAX gives 1.0), F32 the bits
+ * unchanged (NaN payloads and -0.0 included), F64 rounded once to fp32.  These are torchaudio's normalize=True conventions; no bit
+ * parity with sox is claimed for S32 / F64.
+ * svt_pcm_encode: the way back for the two formats the reference writes.  Row c of in_dev (pitch ld_in >= frames, 4-byte aligned) is
+ * channel c; dst_dev, at any byte alignment, receives `frames` interleaved frames.  F32: the bits unchanged (torchaudio.save of a float32
+ * tensor).  S16: q = clamp(rint(x * 32768), -32768, 32767) with ties to even, NaN -> 0, +-inf clamped; the scale is exact in fp32
+ * (soundfile's PCM_16).  No parity with sox's rounding is claimed.
+ * Both: one launch on `stream`, no synchronisation, no allocation, no workspace, no atomics; two calls give the same bytes.  Nothing
+ * outside [src_dev, src_dev + frames * block_align) is read, nothing outside the `frames` elements of each row (decode) or the frames *
+ * block_align bytes at dst_dev (encode) is written; the gaps of ld_out stay untouched.  A workgroup of 256 threads takes
+ * SVT_PCM_FRAMES_PER_WORKGROUP consecutive frames at a time and the grid holds at most SVT_PCM_MAX_WORKGROUPS of them; longer inputs
+ * take further trips of the grid-stride loop.
+ * SVT_ERR_INVALID (nothing is written): a null pointer, out_dev / in_dev not 4-byte aligned, channels outside 1..8, frames < 1, ld <
+ * frames, downmix with channels != 2, for decode a format that is none of the six, for encode one other than S16 / F32. */
+#define SVT_PCM_FRAMES_PER_WORKGROUP 4096
+#define SVT_PCM_MAX_WORKGROUPS 1024
+int svt_pcm_decode(const void* src_dev, int32_t format, int32_t channels, int64_t frames, float* out_dev, int64_t ld_out, int32_t downmix,
+                   int device, void* stream);
+int svt_pcm_encode(const float* in_dev, int64_t ld_in, int32_t channels, int64_t frames, int32_t format, void* dst_dev, int device,
+                   void* stream);
+
 /* ======================================================================================================================
  * DIAGNOSTIC SURFACE: svt_debug_* and svt_prof_*.  These entry points exist for the unit tests of single kernels, the micro-benchmarks
  * under tools/ and the bench's per-launch timing.  They are the ONE exception to the conventions of the product entry points above:

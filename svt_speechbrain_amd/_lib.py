@@ -89,6 +89,12 @@ class LayerNormDescC(C.Structure):
     ]
 
 
+class WavInfoC(C.Structure):
+    """svt_wav_info: what svt_wav_parse reads from a RIFF/WAVE header; format is a svt_pcm_format (U8 = 1 .. F64 = 6)."""
+    _fields_ = [("format", C.c_int32), ("channels", C.c_int32), ("sample_rate", C.c_int32), ("bits_per_sample", C.c_int32),
+                ("block_align", C.c_int32), ("data_offset", C.c_int64), ("frames", C.c_int64)]
+
+
 class FrameC(C.Structure):
     _fields_ = [("p_on", C.c_float), ("p_off", C.c_float), ("octave", C.c_int32), ("pitch_class", C.c_int32)]
 
@@ -137,6 +143,10 @@ SYMBOLS = {
     "svt_resample_output_samples": (C.c_int64, [C.c_int64, C.c_int32, C.c_int32]),
     "svt_resample": (C.c_int, [_P, C.c_int32, C.c_int64, C.c_int64, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int64, C.c_int64,
                                C.c_int32, C.c_int, _P]),
+    "svt_wav_parse": (C.c_int, [_P, C.c_int64, C.c_int64, C.POINTER(WavInfoC), _I64P]),
+    "svt_wav_header": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int64, _P, C.c_int64, _I64P]),
+    "svt_pcm_decode": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int64, _P, C.c_int64, C.c_int32, C.c_int, _P]),
+    "svt_pcm_encode": (C.c_int, [_P, C.c_int64, C.c_int32, C.c_int64, C.c_int32, _P, C.c_int, _P]),
     "svt_debug_gemm": (C.c_int, [C.c_int32, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64,
                                  C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int, _P]),
     "svt_debug_gemm_batched": (C.c_int, [C.c_int32, C.POINTER(GemmDescC), C.c_int, _P]),

@@ -260,6 +260,33 @@ int svt_resample(const float* in, int32_t rows, int64_t n_in, int64_t ld_in, con
   return SVT_OK;
 }
 
+// ---- PCM <-> fp32 on the bytes of a wav file (pcm.hip); the header's parser and writer are host.cpp's ----
+int svt_pcm_decode(const void* src, int32_t format, int32_t channels, int64_t frames, float* out, int64_t ld_out, int32_t downmix,
+                   int device, void* stream) {
+  if (format < SVT_PCM_U8 || format > SVT_PCM_F64) { set_error("svt_pcm_decode: unknown format"); return SVT_ERR_INVALID; }
+  if (channels < 1 || channels > 8) { set_error("svt_pcm_decode: channels must be in 1..8"); return SVT_ERR_INVALID; }
+  if (frames < 1) { set_error("svt_pcm_decode: frames < 1"); return SVT_ERR_INVALID; }
+  if (ld_out < frames) { set_error("svt_pcm_decode: ld_out < frames"); return SVT_ERR_INVALID; }
+  if (downmix && channels != 2) { set_error("svt_pcm_decode: downmix takes 2 channels"); return SVT_ERR_INVALID; }
+  if (!src || !out) { set_error("svt_pcm_decode: null argument"); return SVT_ERR_INVALID; }
+  if ((uintptr_t)out & 3) { set_error("svt_pcm_decode: out_dev must be 4-byte aligned"); return SVT_ERR_INVALID; }
+  if (int r = check_device(device)) return r;
+  if (launch_pcm_decode(src, format, channels, frames, out, ld_out, downmix != 0, (hipStream_t)stream)) return SVT_ERR_HIP;
+  return SVT_OK;
+}
+
+int svt_pcm_encode(const float* in, int64_t ld_in, int32_t channels, int64_t frames, int32_t format, void* dst, int device, void* stream) {
+  if (format != SVT_PCM_S16 && format != SVT_PCM_F32) { set_error("svt_pcm_encode: only SVT_PCM_S16 and SVT_PCM_F32 are written"); return SVT_ERR_INVALID; }
+  if (channels < 1 || channels > 8) { set_error("svt_pcm_encode: channels must be in 1..8"); return SVT_ERR_INVALID; }
+  if (frames < 1) { set_error("svt_pcm_encode: frames < 1"); return SVT_ERR_INVALID; }
+  if (ld_in < frames) { set_error("svt_pcm_encode: ld_in < frames"); return SVT_ERR_INVALID; }
+  if (!in || !dst) { set_error("svt_pcm_encode: null argument"); return SVT_ERR_INVALID; }
+  if ((uintptr_t)in & 3) { set_error("svt_pcm_encode: in_dev must be 4-byte aligned"); return SVT_ERR_INVALID; }
+  if (int r = check_device(device)) return r;
+  if (launch_pcm_encode(in, ld_in, channels, frames, format, dst, (hipStream_t)stream)) return SVT_ERR_HIP;
+  return SVT_OK;
+}
+
 // ---- Fbank add-ons ----
 int svt_deltas(const float* x, int64_t ldx, int32_t batch, int32_t t, int32_t c, int32_t window_length, float* out, int64_t ldo,
                int device, void* stream) {

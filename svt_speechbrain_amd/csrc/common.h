@@ -528,6 +528,10 @@ int launch_noise_mix(const float* clean, const float* noise, int64_t n, const do
 int resample_units_per_tile(int P, int W, int S, bool downmix);
 int launch_resample(const float* in, int rows_out, int64_t n_in, int64_t ld_in, const float* w, const int32_t* first, int P, int W, int S,
                     float* out, int64_t n_out, int64_t ld_out, bool downmix, hipStream_t s);
+// PCM <-> fp32 on the bytes of a wav file (pcm.hip): interleaved little-endian frames at any byte address <-> planar fp32 rows (4-byte
+// aligned, pitch ld >= frames); format = svt_pcm_format (encode: S16 or F32); downmix: 2 channels -> the one row 0.5 * (l + r).  One launch
+int launch_pcm_decode(const void* src, int format, int channels, int64_t frames, float* out, int64_t ld, bool downmix, hipStream_t s);
+int launch_pcm_encode(const float* in, int64_t ld, int channels, int64_t frames, int format, void* dst, hipStream_t s);
 // lip front-end (video.hip)
 int launch_video_pad(int prec, const float* v, int B, int T, int H, int W, int Hp, int Wp, void* out, hipStream_t s);
 // the recipe's uint8 -> float32 pixel map, ((u - sub0) / div0 - mean) / std in float64 (video.hip, svt_video_forward_u8)

@@ -3,6 +3,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstring>
 
 namespace svt {
 
@@ -140,9 +141,121 @@ void posconv_multiframe(const float* w, const float* bias, int G, int cg, int kp
 
 using namespace svt;
 
+// ---- RIFF/WAVE headers (svt_wav_parse, svt_wav_header): little-endian fields read and written byte by byte, so neither the host's byte
+// order nor the alignment of the caller's buffer matters ----
+namespace {
+inline uint32_t rd16(const unsigned char* p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8); }
+inline uint32_t rd32(const unsigned char* p) { return rd16(p) | (rd16(p + 2) << 16); }
+inline void wr16(unsigned char* p, uint32_t v) { p[0] = (unsigned char)(v & 0xff); p[1] = (unsigned char)((v >> 8) & 0xff); }
+inline void wr32(unsigned char* p, uint32_t v) { wr16(p, v & 0xffff); wr16(p + 2, v >> 16); }
+inline bool tag_is(const unsigned char* p, const char* t) { return p[0] == (unsigned char)t[0] && p[1] == (unsigned char)t[1] && p[2] == (unsigned char)t[2] && p[3] == (unsigned char)t[3]; }
+int wav_refuse(const char* why) { set_error(std::string("svt_wav_parse: ") + why); return SVT_ERR_INVALID; }
+// bytes 2..15 of KSDATAFORMAT_SUBTYPE_PCM / _IEEE_FLOAT (bytes 0..1 are the format tag)
+const unsigned char kSubFormatTail[14] = {0x00, 0x00, 0x00, 0x00, 0x10, 0x00, 0x80, 0x00, 0x00, 0xAA, 0x00, 0x38, 0x9B, 0x71};
+
+// 0 or the svt_pcm_format of a format tag at a sample size
+int pcm_format_of(uint32_t tag, uint32_t bits) {
+  if (tag == 1) return bits == 8 ? SVT_PCM_U8 : bits == 16 ? SVT_PCM_S16 : bits == 24 ? SVT_PCM_S24 : bits == 32 ? SVT_PCM_S32 : 0;
+  if (tag == 3) return bits == 32 ? SVT_PCM_F32 : bits == 64 ? SVT_PCM_F64 : 0;
+  return 0;
+}
+}  // namespace
+
 extern "C" {
 
 const char* svt_last_error(void) { return svt::g_err.c_str(); }
+
+int svt_wav_parse(const void* head_host, int64_t head_bytes, int64_t file_bytes, svt_wav_info* out, int64_t* need_bytes) {
+  const unsigned char* h = (const unsigned char*)head_host;
+  if (!out || head_bytes < 0 || file_bytes < head_bytes || (!h && head_bytes > 0)) return wav_refuse("bad argument");
+  // the prefix ends before byte `upto`: ask for it if the file has it, otherwise the file is cut short
+#define SVT_WAV_WANT(upto, what)                                                            \
+  do {                                                                                      \
+    if ((upto) > file_bytes) return wav_refuse(what);                                       \
+    if ((upto) > head_bytes) {                                                              \
+      if (!need_bytes) return wav_refuse("need_bytes is null and the prefix is too short"); \
+      *need_bytes = (upto);                                                                 \
+      return SVT_WAV_NEED_MORE;                                                             \
+    }                                                                                       \
+  } while (0)
+  SVT_WAV_WANT(12, "the file is shorter than a RIFF header");
+  if (tag_is(h, "RIFX")) return wav_refuse("RIFX (big-endian) files are not supported");
+  if (tag_is(h, "RF64") || tag_is(h, "BW64")) return wav_refuse("RF64 files are not supported");
+  if (tag_is(h, "riff")) return wav_refuse("W64 files are not supported");
+  if (!tag_is(h, "RIFF") || !tag_is(h + 8, "WAVE")) return wav_refuse("not a RIFF/WAVE file");
+  svt_wav_info w = {};
+  bool have_fmt = false;
+  int64_t pos = 12;
+  for (;;) {
+    SVT_WAV_WANT(pos + 8, "the file ends before its data chunk");
+    const unsigned char* c = h + pos;
+    const int64_t size = (int64_t)rd32(c + 4);
+    if (tag_is(c, "data")) {
+      if (!have_fmt) return wav_refuse("data chunk before fmt chunk");
+      w.data_offset = pos + 8;
+      const int64_t avail = file_bytes - w.data_offset;
+      const int64_t bytes = (size == 0 || size == 0xFFFFFFFFll || size > avail) ? avail : size;
+      w.frames = bytes / w.block_align;
+      *out = w;
+      return SVT_OK;
+    }
+    if (tag_is(c, "fmt ")) {
+      if (size < 16) return wav_refuse("fmt chunk shorter than 16 bytes");
+      if (pos + 8 + size > file_bytes) return wav_refuse("the file ends inside its fmt chunk");
+      SVT_WAV_WANT(pos + 8 + (size < 40 ? size : 40), "the file ends inside its fmt chunk");
+      const unsigned char* f = c + 8;
+      uint32_t tag = rd16(f);
+      const uint32_t channels = rd16(f + 2), rate = rd32(f + 4), align = rd16(f + 12), bits = rd16(f + 14);
+      if (tag == 0xFFFE) {
+        if (size < 40 || rd16(f + 16) < 22) return wav_refuse("WAVE_FORMAT_EXTENSIBLE with a short fmt chunk");
+        if (memcmp(f + 26, kSubFormatTail, sizeof(kSubFormatTail)) != 0) return wav_refuse("unknown sub-format GUID");
+        if (rd16(f + 18) != bits) return wav_refuse("valid bits differ from the container size");
+        tag = rd16(f + 24);
+        if (tag != 1 && tag != 3) return wav_refuse("unsupported sub-format (PCM and IEEE float only)");
+      }
+      if (tag == 6 || tag == 7) return wav_refuse("A-law / mu-law files are not supported");
+      if (tag == 2 || tag == 0x11) return wav_refuse("ADPCM files are not supported");
+      if (tag != 1 && tag != 3) return wav_refuse("unsupported format tag (PCM and IEEE float only)");
+      const int fmt = pcm_format_of(tag, bits);
+      if (!fmt) return wav_refuse("unsupported sample size");
+      if (channels < 1 || channels > 8) return wav_refuse("channels must be in 1..8");
+      if (rate < 1 || rate > 0x7FFFFFFFu) return wav_refuse("bad sample rate");
+      if (align != channels * bits / 8) return wav_refuse("block_align is not channels * bits / 8");
+      w.format = fmt; w.channels = (int32_t)channels; w.sample_rate = (int32_t)rate; w.bits_per_sample = (int32_t)bits;
+      w.block_align = (int32_t)align;
+      have_fmt = true;
+    }
+    pos += 8 + size + (size & 1);
+    if (pos > file_bytes) return wav_refuse("the file ends inside a chunk");
+  }
+#undef SVT_WAV_WANT
+}
+
+int svt_wav_header(int32_t format, int32_t channels, int32_t sample_rate, int64_t frames, void* out_host, int64_t capacity,
+                   int64_t* header_bytes) {
+  if (!out_host || !header_bytes) { set_error("svt_wav_header: null argument"); return SVT_ERR_INVALID; }
+  if (format != SVT_PCM_S16 && format != SVT_PCM_F32) { set_error("svt_wav_header: only SVT_PCM_S16 and SVT_PCM_F32 are written"); return SVT_ERR_INVALID; }
+  if (channels < 1 || channels > 8 || sample_rate < 1 || frames < 0) { set_error("svt_wav_header: bad channels, rate or frames"); return SVT_ERR_INVALID; }
+  const bool flt = format == SVT_PCM_F32;
+  const int64_t hb = flt ? 58 : 44, align = (int64_t)channels * (flt ? 4 : 2);
+  if (capacity < hb) { set_error("svt_wav_header: capacity below the header's size"); return SVT_ERR_INVALID; }
+  if (frames > (0xFFFFFFFFll - hb) / align) { set_error("svt_wav_header: more than 4 GiB - 1 - header of data"); return SVT_ERR_INVALID; }
+  const int64_t data = frames * align;
+  unsigned char* p = (unsigned char*)out_host;
+  memcpy(p, "RIFF", 4); wr32(p + 4, (uint32_t)(hb - 8 + data)); memcpy(p + 8, "WAVEfmt ", 8);
+  wr32(p + 16, flt ? 18 : 16);
+  wr16(p + 20, flt ? 3 : 1); wr16(p + 22, (uint32_t)channels); wr32(p + 24, (uint32_t)sample_rate);
+  wr32(p + 28, (uint32_t)((int64_t)sample_rate * align)); wr16(p + 32, (uint32_t)align); wr16(p + 34, flt ? 32 : 16);
+  unsigned char* q = p + 36;
+  if (flt) {
+    wr16(q, 0);   // cbSize
+    memcpy(q + 2, "fact", 4); wr32(q + 6, 4); wr32(q + 10, (uint32_t)frames);
+    q += 14;
+  }
+  memcpy(q, "data", 4); wr32(q + 4, (uint32_t)data);
+  *header_bytes = hb;
+  return SVT_OK;
+}
 
 // frame2note (reference MIR_ST500/utils.py:82-149) over a batch of decoded frame sequences, on the HOST (no device call).
 // Same scan as the reference's loop: float32 comparisons against the thresholds, onset = above threshold AND equal to the

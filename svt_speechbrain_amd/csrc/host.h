@@ -1,6 +1,7 @@
 // Host-only part of the library: routines that never touch the GPU -- the error string behind svt_last_error(), parameter intake by
 // key (svt_*_load_param), configuration validation (svt_encoder_create), the weight re-layouts and folds of svt_*_finalize and the
-// frames -> notes scan (svt_frames_to_notes).  Plain
+// frames -> notes scan (svt_frames_to_notes), and the RIFF/WAVE header parser and writer (svt_wav_parse, svt_wav_header; `make san_wav`
+// builds those two with tests/cabi/wav_san_driver.cpp).  Plain
 // C++17 with no HIP header, so the same translation unit is compiled twice: by hipcc into libsvt_mi355*.so, and by g++ with
 // -fsanitize=address,undefined into the CPU test binary of `make san` (tests/test_host_sanitizers.py drives it with the reference's
 // frame2note fixture and hostile arguments).  Sanitizers run on the CPU build only.

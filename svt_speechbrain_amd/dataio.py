@@ -6,6 +6,7 @@ right-zero-padded batch with relative lengths.  Host code, as in the reference.
   ``utter_num = round(duration / dur_thrd)`` rule (Python banker's rounding, last utterance takes the remainder).
 * ``slice_audio`` / ``slice_annotation`` are the two dynamic-item pipelines of ``MIR_ST500/train_audio_ssl.py:381-421``
   (``round()`` of ``(utter_id-1) * rate * dur_threshold``; the last utterance runs to the end).
+* ``read_utterance`` is ``slice_audio`` of a wav FILE: it reads and decodes the utterance's frames only (``audio_io``, on the GPU).
 * ``batch_pad_right`` / ``PaddedBatch`` follow ``speechbrain/utils/data_utils.py:361-424`` and
   ``speechbrain/dataio/batch.py:101-137``: pad dim 0 to the longest item, relative length = len / max_len.
 """
@@ -66,6 +67,17 @@ def slice_audio(sig: torch.Tensor, utter_id, utter_num, sample_rate: int = 16000
     assert len(sig.shape) == 1
     lo, hi = _bounds(int(utter_id), int(utter_num), sample_rate, dur_threshold)
     return sig[lo:] if hi is None else sig[lo:hi]
+
+
+def read_utterance(path, utter_id, utter_num, sample_rate: int = 16000, dur_threshold: float = 5, device=None) -> torch.Tensor:
+    """``audio_pipeline`` (train_audio_ssl.py:373-390) without decoding the whole song: the utterance's bounds are those of
+    ``slice_audio`` and only that range of the mono wav file at ``path`` is read, uploaded and decoded (``audio_io.read_audio`` with
+    ``start`` / ``stop``).  Bit for bit ``slice_audio(read_audio(path), utter_id, utter_num, ...)``, on the GPU."""
+    from .audio_io import read_audio
+    lo, hi = _bounds(int(utter_id), int(utter_num), sample_rate, dur_threshold)
+    sig = read_audio({"file": path, "start": lo} if hi is None else {"file": path, "start": lo, "stop": hi}, device=device)
+    assert len(sig.shape) == 1
+    return sig
 
 
 def slice_annotation(anno: torch.Tensor, utter_id, utter_num, frame_rate: float = 49.8, dur_threshold: float = 5) -> torch.Tensor:

@@ -16,7 +16,8 @@ torchaudio's and is Kaldi's ``LinearResample``: a Hann-windowed sinc of ``lowpas
 * ``SpeedPerturb``: the reference's class over this ``Resample`` (the recipes' commented-out ``augmentation:`` block,
   ``train_audio_ssl.yaml:91-93``); it makes the same ``torch.rand`` / ``torch.randint`` draws in the same order.
 
-Reading audio files stays with the caller.  Waveforms must be on the GPU; there is no CPU fallback.
+Wav files are read and written by ``audio_io`` (``load`` puts the decoded waveform on the GPU, where these classes want it).  Waveforms
+must be on the GPU; there is no CPU fallback.
 """
 from __future__ import annotations
 

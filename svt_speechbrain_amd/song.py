@@ -13,7 +13,8 @@
   ``train_video_ssl.py:537-546``), batch-1 AV-HuBERT forwards, ``feats[0]`` concatenated and saved as
   ``<folder>/noise_data/video_feats.pt`` (``song_video_features`` / ``save_song_video_features``);
 * the noisy inputs of the audio-visual recipe (``N20EMv2/audio_visual/synthesis_noise.py``): ``NoiseSweep`` mixes a song with a noise
-  track at the recipe's five SNRs on the GPU and transcribes every mixture.
+  track at the recipe's five SNRs on the GPU and transcribes every mixture; with ``write_wavs`` it also leaves the noisy wavs;
+* ``SongTranscriber.transcribe_file``: the same from a wav file (``audio_io.load``: the PCM conversion runs on the GPU).
 """
 from __future__ import annotations
 
@@ -23,6 +24,7 @@ from typing import List, Optional, Tuple
 import torch
 
 from .decode import decode_frames, frame2note, frames2note, frames2note_batch, frames_to_info
+from . import audio_io
 from .noise import SNRS_DB, mix_at_snrs
 from .resample import resample_to_mono
 
@@ -124,6 +126,15 @@ class SongTranscriber:
             return notes, torch.cat(feats_all, dim=0)
         return notes
 
+    def transcribe_file(self, path, return_feats: bool = False, device=None):
+        """A wav file -> what ``transcribe`` returns: ``audio_io.load`` (raw PCM uploaded and decoded on the GPU), then
+        ``transcribe(song, sample_rate=fs)`` -- the preparation scripts' Resample and channel mean -- when the file is not mono at
+        ``self.sample_rate``, and ``transcribe(song)`` when it is."""
+        song, fs = audio_io.load(path, device=device)
+        if fs != self.sample_rate or song.shape[0] != 1:
+            return self.transcribe(song, return_feats=return_feats, sample_rate=fs)
+        return self.transcribe(song[0], return_feats=return_feats)
+
 
 def feature_path(song_folder: str, add_noise: bool = False, noise_type: Optional[str] = None,
                  snr_db: Optional[int] = None) -> str:
@@ -156,12 +167,16 @@ class NoiseSweep:
         self.transcriber, self.snrs_db = transcriber, tuple(snrs_db)
 
     @torch.no_grad()
-    def run(self, clean: torch.Tensor, noise_track: torch.Tensor, song_folder: Optional[str] = None, noise_type: Optional[str] = None):
+    def run(self, clean: torch.Tensor, noise_track: torch.Tensor, song_folder: Optional[str] = None, noise_type: Optional[str] = None,
+            write_wavs: bool = False):
         """clean, noise_track: 1-D waveforms of one length on the GPU.  Returns ``{snr_db: (notes, feats)}``; with ``song_folder`` each
         SNR's features are also written where ``train_rca_av.py:402-408`` looks for them (``feature_path(song_folder, True, noise_type,
-        snr_db)``)."""
+        snr_db)``).  ``write_wavs``: each mixture is also written, as a float32 wav at the transcriber's sample rate, to
+        ``noisy_wav_path(song_folder, noise_type, snr_db)`` -- the files ``synthesis_noise.py:141, 184, 310, 472`` leave behind."""
         if song_folder is not None and noise_type is None:
             raise ValueError("noise_type names the folder the features are written to")
+        if write_wavs and song_folder is None:
+            raise ValueError("write_wavs needs the song_folder the wavs are written to")
         n = clean.shape[-1]
         # rows on 16-byte boundaries, like the clean song of a fresh allocation
         rows = torch.empty((len(self.snrs_db), (n + 3) // 4 * 4), dtype=torch.float32, device=clean.device)
@@ -169,6 +184,10 @@ class NoiseSweep:
         out = {}
         for s, snr in enumerate(self.snrs_db):
             notes, feats = self.transcriber.transcribe(mix[s], return_feats=True)
+            if write_wavs:
+                path = noisy_wav_path(song_folder, noise_type, snr)
+                os.makedirs(os.path.dirname(path), exist_ok=True)
+                audio_io.save(path, mix[s].unsqueeze(0), self.transcriber.sample_rate)
             if song_folder is not None:
                 save_song_features(feats, song_folder, add_noise=True, noise_type=noise_type, snr_db=snr)
             out[snr] = (notes, feats)
