@@ -282,6 +282,39 @@ int svt_resample(const float* in_dev, int32_t rows, int64_t n_in, int64_t ld_in,
                  int32_t P, int32_t W, int32_t S, float* out_dev, int64_t n_out, int64_t ld_out, int32_t downmix, int device,
                  void* stream);
 
+/* ---- frequency and chunk dropping of a waveform batch: replaces the DropFreq and DropChunk steps of
+ * speechbrain.lobes.augment.TimeDomainSpecAugment (speechbrain/processing/speech_augmentation.py:876-1140: a conv1d with a 101-tap
+ * band-reject filter between a transpose, a clone and a squeeze, then a Python loop over the batch with one slice assignment per
+ * dropped chunk), the `augmentation:` block of the five training yamls ----
+ * For every r < rows and t < n, with the host-built filter of `taps` fp32 coefficients and row r's max_chunks pairs {start, end}
+ * (chunks_dev: rows x max_chunks x 2 int64):
+ *     out[r][t] = 0.0f                                                   if start <= t < end for any chunk of row r
+ *               = sum_{k < taps} filter[k] * x[r][t + k - taps / 2]      otherwise,      x taken as 0 outside [0, n)
+ * The sum is a cross-correlation, as torch.nn.functional.conv1d computes it (the reference's compound filter is not symmetric: its
+ * Blackman window is the periodic one).  A row's zero padding starts at the row's n samples, not at a clip's valid length: what the
+ * reference does to a padded batch.  A dropped element is WRITTEN as zero, not multiplied by it: whatever the filter produced there,
+ * NaN included, does not survive.  A chunk with end > n is cut at n (and start < 0 at 0), one with start >= end is empty, chunks may
+ * overlap; a row with fewer chunks than max_chunks fills up with empty ones.  filter_dev == NULL with taps == 0: no filtering, the
+ * elements outside the chunks are copied unchanged (DropChunk alone); chunks_dev == NULL with max_chunks == 0: no chunks (DropFreq alone).
+ * Each output is ONE fp32 chain of fused multiply-adds over the taps in ascending order, started at 0: two calls give the same bits,
+ * and a delta filter (1 at the centre tap) returns finite input exactly.  One launch on `stream` for any number of rows; no
+ * synchronisation, no allocation, no workspace.  in_dev: rows x n, row pitch ld_in >= n; out_dev: rows x n, row pitch ld_out >= n;
+ * nothing is read outside a row's n samples and nothing is written at out_dev[r * ld_out + n .. (r + 1) * ld_out).  in_dev, filter_dev
+ * and out_dev need 4-byte alignment only, chunks_dev 8-byte; indices into the rows are 64-bit.
+ * SVT_ERR_INVALID (nothing is written): rows < 1 or n < 1; taps even or outside 1..SVT_DROP_MAX_TAPS; filter_dev non-null with taps ==
+ * 0 or null with taps != 0, and the same for chunks_dev and max_chunks; max_chunks < 0; ld_in < n or ld_out < n; in_dev or out_dev
+ * null; a misaligned pointer; the rows x n extents of in_dev and out_dev (row pitches included) overlapping: the filter reads taps / 2
+ * samples either side of an output, so in-place operation would be wrong.
+ * A workgroup of 256 threads takes SVT_DROP_TILE_OUTPUTS consecutive outputs of a row at a time (four per lane) and stages their
+ * SVT_DROP_TILE_OUTPUTS + taps - 1 input samples in LDS; a tile that lies wholly inside one chunk is zeroed without reading its input.
+ * Up to SVT_DROP_MAX_WORKGROUPS (row, tile) pairs each has a workgroup of its own; beyond that the grid is cut to the pairs divided by
+ * the trips they need, and every workgroup takes that many. */
+#define SVT_DROP_MAX_TAPS 255
+#define SVT_DROP_TILE_OUTPUTS 1024
+#define SVT_DROP_MAX_WORKGROUPS 8192
+int svt_drop_freq_chunk(const float* in_dev, int32_t rows, int64_t n, int64_t ld_in, const float* filter_dev, int32_t taps,
+                        const int64_t* chunks_dev, int32_t max_chunks, float* out_dev, int64_t ld_out, int device, void* stream);
+
 /* ---- wav files: replaces torchaudio.info / load / save and speechbrain.dataio.dataio.read_audio / write_audio for RIFF/WAVE files
  * (MIR_ST500/prepare_benchmarks.py:58, N20EMv2/audio_visual/synthesis_noise.py, MIR_ST500/train_audio_ssl.py:373-390) ----
  * The host parses and writes the header (no device call); the sample conversion runs on the GPU on the raw bytes of the file.

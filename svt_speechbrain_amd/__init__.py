@@ -21,6 +21,8 @@ from .noise import (SNRS_DB, compute_amplitude, mix_at_snrs, assemble_noise_trac
                     babble_keep, babble_split, noise_pools, natural_pools, babble_pools)
 from . import resample  # noqa: F401
 from .resample import Resample, SpeedPerturb, resample_table, resample_to_mono  # noqa: F401
+from . import augment  # noqa: F401
+from .augment import notch_filter, drop_filter, DropFreq, DropChunk, TimeDomainSpecAugment  # noqa: F401
 from . import audio_io  # noqa: F401
 from .audio_io import info, load, save, read_audio, write_audio  # noqa: F401
 from .dataio import read_utterance  # noqa: F401
@@ -35,4 +37,5 @@ __all__ = ["EncoderConfig", "PRESETS", "config_from_source", "HuggingFaceWav2Vec
            "SNRS_DB", "compute_amplitude", "mix_at_snrs", "assemble_noise_track", "split_natural_files", "natural_keep", "babble_keep",
            "babble_split", "noise_pools", "natural_pools", "babble_pools", "noisy_wav_path", "NoiseSweep",
            "Resample", "SpeedPerturb", "resample_table", "resample_to_mono",
+           "notch_filter", "drop_filter", "DropFreq", "DropChunk", "TimeDomainSpecAugment",
            "audio_io", "info", "load", "save", "read_audio", "write_audio", "read_utterance"]

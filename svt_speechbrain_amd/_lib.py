@@ -143,6 +143,7 @@ SYMBOLS = {
     "svt_resample_output_samples": (C.c_int64, [C.c_int64, C.c_int32, C.c_int32]),
     "svt_resample": (C.c_int, [_P, C.c_int32, C.c_int64, C.c_int64, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int64, C.c_int64,
                                C.c_int32, C.c_int, _P]),
+    "svt_drop_freq_chunk": (C.c_int, [_P, C.c_int32, C.c_int64, C.c_int64, _P, C.c_int32, _P, C.c_int32, _P, C.c_int64, C.c_int, _P]),
     "svt_wav_parse": (C.c_int, [_P, C.c_int64, C.c_int64, C.POINTER(WavInfoC), _I64P]),
     "svt_wav_header": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int64, _P, C.c_int64, _I64P]),
     "svt_pcm_decode": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int64, _P, C.c_int64, C.c_int32, C.c_int, _P]),

@@ -260,6 +260,29 @@ int svt_resample(const float* in, int32_t rows, int64_t n_in, int64_t ld_in, con
   return SVT_OK;
 }
 
+// ---- frequency and chunk dropping of a waveform batch (drop_freq_chunk.hip) ----
+int svt_drop_freq_chunk(const float* in, int32_t rows, int64_t n, int64_t ld_in, const float* filter, int32_t taps, const int64_t* chunks,
+                        int32_t max_chunks, float* out, int64_t ld_out, int device, void* stream) {
+  if (rows < 1 || n < 1) { set_error("svt_drop_freq_chunk: empty input"); return SVT_ERR_INVALID; }
+  if ((filter != nullptr) != (taps != 0)) { set_error("svt_drop_freq_chunk: filter_dev and taps go together (NULL / 0: no filtering)"); return SVT_ERR_INVALID; }
+  if (taps && (taps < 1 || taps > SVT_DROP_MAX_TAPS || !(taps & 1))) { set_error("svt_drop_freq_chunk: taps must be odd and in 1..SVT_DROP_MAX_TAPS"); return SVT_ERR_INVALID; }
+  if (max_chunks < 0) { set_error("svt_drop_freq_chunk: max_chunks < 0"); return SVT_ERR_INVALID; }
+  if ((chunks != nullptr) != (max_chunks != 0)) { set_error("svt_drop_freq_chunk: chunks_dev and max_chunks go together (NULL / 0: no chunks)"); return SVT_ERR_INVALID; }
+  if (ld_in < n) { set_error("svt_drop_freq_chunk: ld_in < n"); return SVT_ERR_INVALID; }
+  if (ld_out < n) { set_error("svt_drop_freq_chunk: ld_out < n"); return SVT_ERR_INVALID; }
+  if (!in || !out) { set_error("svt_drop_freq_chunk: null argument"); return SVT_ERR_INVALID; }
+  if (((uintptr_t)in | (uintptr_t)filter | (uintptr_t)out) & 3) { set_error("svt_drop_freq_chunk: in_dev, filter_dev and out_dev must be 4-byte aligned"); return SVT_ERR_INVALID; }
+  if ((uintptr_t)chunks & 7) { set_error("svt_drop_freq_chunk: chunks_dev must be 8-byte aligned"); return SVT_ERR_INVALID; }
+  const int64_t most = (INT64_MAX / 8 - n) / rows;                  // the byte extents below stay inside 63 bits
+  if (ld_in > most || ld_out > most) { set_error("svt_drop_freq_chunk: a row pitch too large to address"); return SVT_ERR_INVALID; }
+  const uintptr_t in_lo = (uintptr_t)in, in_hi = in_lo + 4 * (uintptr_t)((rows - 1) * ld_in + n);
+  const uintptr_t out_lo = (uintptr_t)out, out_hi = out_lo + 4 * (uintptr_t)((rows - 1) * ld_out + n);
+  if (in_lo < out_hi && out_lo < in_hi) { set_error("svt_drop_freq_chunk: in_dev and out_dev overlap (the filter's halo makes in-place operation wrong)"); return SVT_ERR_INVALID; }
+  if (int r = check_device(device)) return r;
+  if (launch_drop_freq_chunk(in, rows, n, ld_in, filter, taps, chunks, max_chunks, out, ld_out, (hipStream_t)stream)) return SVT_ERR_HIP;
+  return SVT_OK;
+}
+
 // ---- PCM <-> fp32 on the bytes of a wav file (pcm.hip); the header's parser and writer are host.cpp's ----
 int svt_pcm_decode(const void* src, int32_t format, int32_t channels, int64_t frames, float* out, int64_t ld_out, int32_t downmix,
                    int device, void* stream) {

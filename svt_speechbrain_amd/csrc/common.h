@@ -528,6 +528,11 @@ int launch_noise_mix(const float* clean, const float* noise, int64_t n, const do
 int resample_units_per_tile(int P, int W, int S, bool downmix);
 int launch_resample(const float* in, int rows_out, int64_t n_in, int64_t ld_in, const float* w, const int32_t* first, int P, int W, int S,
                     float* out, int64_t n_out, int64_t ld_out, bool downmix, hipStream_t s);
+// frequency and chunk dropping (drop_freq_chunk.hip): out[r][t] = 0 inside a chunk [start, end) of row r, else sum_k filter[k] *
+// in[r][t + k - taps / 2] with zeros outside [0, n); filter null / taps 0: a copy; chunks (rows x max_chunks x 2 int64) null /
+// max_chunks 0: none.  One launch
+int launch_drop_freq_chunk(const float* in, int rows, int64_t n, int64_t ld_in, const float* filter, int taps, const int64_t* chunks,
+                           int max_chunks, float* out, int64_t ld_out, hipStream_t s);
 // PCM <-> fp32 on the bytes of a wav file (pcm.hip): interleaved little-endian frames at any byte address <-> planar fp32 rows (4-byte
 // aligned, pitch ld >= frames); format = svt_pcm_format (encode: S16 or F32); downmix: 2 channels -> the one row 0.5 * (l + r).  One launch
 int launch_pcm_decode(const void* src, int format, int channels, int64_t frames, float* out, int64_t ld, bool downmix, hipStream_t s);
