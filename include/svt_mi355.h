@@ -480,6 +480,60 @@ typedef struct svt_debug_layernorm_desc {
 } svt_debug_layernorm_desc;
 int svt_debug_layernorm(const svt_debug_layernorm_desc* d, int device, void* stream);
 
+/* ---- test hook: one launch of ONE launcher of the waveform front end (csrc/stats.hip, csrc/conv0.hip, csrc/conv0_mfma.hip) on
+ * caller-supplied device buffers; tests/test_gpu_conv0.py ----
+ * The descriptor holds the union of the seven launchers' arguments; `form` says which one runs (fields of another form are ignored):
+ *   form 0  launch_moments: mom[2 g] = sum, mom[2 g + 1] = sum of squares of x[g n .. (g + 1) n), g < groups (fp64, written, not
+ *           accumulated); scratch sized for groups_max groups.
+ *   form 1  launch_conv0_window_moments: wm[65 b ..] = the 10 tap sums and 55 tap products (j <= j2, products rounded to fp32) over the T1
+ *           windows of stride `stride` of clip b of wav (B, L).
+ *   form 2  launch_conv0_group_coef: coef (B, C, 11) fp32 from wm (B, 65), the waveform moments wav_mom (2 per norm group of cpg clips,
+ *           over n_wav samples; NULL = the waveform is not normalised), w0 (C, 10), b0 (C) or NULL, gamma, beta (C); eps_wav, eps.
+ *   form 3  launch_conv0_group_apply: out (B, T1, C) = gelu(sum_j coef[b, c, j] wav[b, t stride + j] + coef[b, c, 10]); prec 0 = fp32
+ *           rows, 1 = the build's 16-bit rows; pair_kind 2 / 3 (prec 0, C % 32 == 0) = pair rows of bf16 / IEEE-half pieces.
+ *   form 4  launch_conv0_layer: out = gelu(LN_C(conv(w0, b0) of the normalised waveform) gamma + beta); prec / pair_kind as form 3.
+ *   form 5  launch_conv0_mfma_group: form 3 on the matrix pipe, C = 512; pair_kind 0 = 16-bit rows, 2 / 3 = pair rows (prec is ignored).
+ *   form 6  launch_conv0_mfma_layer: form 4 on the matrix pipe, C = 512; pair_kind as form 5.
+ * Buffers (elements): x groups * n floats; mom 2 * groups doubles; wav B * L floats; wm 65 * B doubles; wav_mom 2 * (B / cpg) doubles;
+ * coef B * C * 11 floats; w0 10 * C, b0 / gamma / beta C floats; out B * T1 * C elements of its type (4 bytes each for pair rows).
+ * The hook allocates the launchers' scratch itself (tickets and per-workgroup partials for forms 0 and 1, the table workspace for forms
+ * 5 and 6), zeroes ONLY the tickets and fills the rest with 0xFF bytes, launches `repeat` times (values below 1 count as 1) on the same
+ * scratch without zeroing it again -- a ticket that is not put back to 0 shows in the second launch -- synchronises the stream and, for
+ * forms 0 and 1 with tickets_out != NULL (a HOST pointer), copies the final value of the groups_max (form 0) / B (form 1) tickets there.
+ * The hook is NARROWER than the launchers: it refuses (SVT_ERR_INVALID, nothing is launched) every argument that could send a kernel
+ * outside these buffers -- k != 10 or stride outside 1 .. 5 (in every form); groups < 1, groups > groups_max, n < 1, groups > 1 with
+ * n % 4 != 0 (form 0); B < 1, T1 < 1, L < (T1 - 1) * stride + 10 (forms 1 - 6); C < 1 or C > 512 (forms 2 - 6), C % 8 != 0 (forms 3 - 6: form 2's kernel
+ * takes any C); C != 512 (forms 5, 6); cpg < 1 or B % cpg != 0 (forms 2, 4, 6); wav_mom with n_wav < 1; prec outside {0, 1}, pair_kind outside {0, 2, 3}, pair rows
+ * without C % 32 == 0 and prec == 0 (forms 3, 4); a NULL pointer where the form needs one (b0 and wav_mom may be NULL); ANY non-NULL
+ * pointer that is not 16-byte aligned (128-byte for a pair-row out and for every out of forms 5 and 6).  Forms 5 and 6 validate their
+ * geometry here and do not consult svt_debug_set key 22.  struct_size = the size of the structure.  svt_debug_set(41, 0) says which
+ * kernel the launch chose. */
+typedef struct svt_debug_conv0_desc {
+  int32_t struct_size;
+  int32_t form;
+  int32_t B, C;
+  int64_t L, T1;
+  int32_t k, stride;
+  int32_t prec, pair_kind;
+  int32_t cpg, groups;
+  int32_t groups_max, repeat;
+  int64_t n, n_wav;
+  float eps_wav, eps;
+  const float* x;
+  const float* wav;
+  const double* wav_mom;
+  const float* w0;
+  const float* b0;
+  const float* gamma;
+  const float* beta;
+  double* mom;
+  double* wm;
+  float* coef;
+  void* out;
+  uint32_t* tickets_out;
+} svt_debug_conv0_desc;
+int svt_debug_conv0(const svt_debug_conv0_desc* d, int device, void* stream);
+
 /* ---- AV-HuBERT lip front-end: replaces SubModel / ResEncoder of N20EMv2/video_only/resnet.py:134-187 (the
  * `feature_extractor_video` of the AV-HuBERT model, hubert.py:344-346): 3-D stem + ResNet-18 trunk (PReLU) + Linear(512,
  * embed_dim), eval mode.  Parameter keys are SubModel.state_dict() keys ("resnet.frontend3D.0.weight", "resnet.trunk.layer1.0.
@@ -659,8 +713,14 @@ int svt_debug_rca_attn_bwd(int32_t precision, const void* qkv, const void* qc, c
  * 2000 + 100 * PK + 10 * (16-bit x) + (16-bit yT) = layernorm_f32_vec_kernel<VPT, float> 2000, <VPT, 16-bit> 2001, <VPT, 16-bit, 16-bit>
  * 2011, <VPT, float, float, 2> 2200 (pair rows, bf16 pieces), <VPT, float, float, 3> 2300 (pair rows, IEEE-half pieces);
  * 3000 = layernorm_op16_rows2_kernel; 4000 = layernorm_hilo_kernel; 5000 = layernorm_hilo2_kernel, 5001 = its PARTS instantiation;
- * 6000 = layernorm_f32_to_hilo_kernel (tests/test_gpu_layernorm.py asserts the id of every case).
- * Returns 0 (keys 24, 31: the count; keys 38, 39, 40: the id), SVT_ERR_INVALID for an unknown key or a value a key does not accept (21, 28, 30, 37 above). */
+ * 6000 = layernorm_f32_to_hilo_kernel (tests/test_gpu_layernorm.py asserts the id of every case), 41 = query: returns which kernel of
+ * the waveform front end the last launch of this process chose (value ignored; 0 = none yet; set on the host by every branch of the seven
+ * launchers of csrc/stats.hip, csrc/conv0.hip and csrc/conv0_mfma.hip) as 100 * kernel + 10 * PK + (16-bit rows out):
+ * 100 = moments_kernel; 200 = conv0_window_moments_kernel; 300 = conv0_group_coef_kernel; conv0_group_apply_kernel<float> 400,
+ * <16-bit> 401, <float, 2> 420, <float, 3> 430; conv0_layer_kernel<float> 500, <16-bit> 501, <float, 2> 520, <float, 3> 530;
+ * conv0_mfma_kernel<0, 0> 601 (with conv0_coef_exp_kernel and conv0_table_kernel<0> in front of it), <0, 2> 620, <0, 3> 630;
+ * conv0_mfma_kernel<1, 0> 701 (with conv0_table_kernel<0>), <1, 2> 720, <1, 3> 730 (tests/test_gpu_conv0.py asserts the id of every case).
+ * Returns 0 (keys 24, 31: the count; keys 38, 39, 40, 41: the id), SVT_ERR_INVALID for an unknown key or a value a key does not accept (21, 28, 30, 37 above). */
 int svt_debug_set(int key, int value);
 
 /* ---- measurement hook: HIP-event timing of the dominant kernel on the stream it runs on ----

@@ -89,6 +89,26 @@ class LayerNormDescC(C.Structure):
     ]
 
 
+class Conv0DescC(C.Structure):
+    """svt_debug_conv0_desc: one launch of a launcher of the waveform front end (svt_debug_conv0); form 0 .. 6, device pointers
+    (tickets_out: a host pointer)."""
+    _fields_ = [
+        ("struct_size", C.c_int32),
+        ("form", C.c_int32),
+        ("B", C.c_int32), ("C", C.c_int32),
+        ("L", C.c_int64), ("T1", C.c_int64),
+        ("k", C.c_int32), ("stride", C.c_int32),
+        ("prec", C.c_int32), ("pair_kind", C.c_int32),
+        ("cpg", C.c_int32), ("groups", C.c_int32),
+        ("groups_max", C.c_int32), ("repeat", C.c_int32),
+        ("n", C.c_int64), ("n_wav", C.c_int64),
+        ("eps_wav", C.c_float), ("eps", C.c_float),
+        ("x", C.c_void_p), ("wav", C.c_void_p), ("wav_mom", C.c_void_p), ("w0", C.c_void_p), ("b0", C.c_void_p), ("gamma", C.c_void_p),
+        ("beta", C.c_void_p), ("mom", C.c_void_p), ("wm", C.c_void_p), ("coef", C.c_void_p), ("out", C.c_void_p),
+        ("tickets_out", C.c_void_p),
+    ]
+
+
 class WavInfoC(C.Structure):
     """svt_wav_info: what svt_wav_parse reads from a RIFF/WAVE header; format is a svt_pcm_format (U8 = 1 .. F64 = 6)."""
     _fields_ = [("format", C.c_int32), ("channels", C.c_int32), ("sample_rate", C.c_int32), ("bits_per_sample", C.c_int32),
@@ -152,6 +172,7 @@ SYMBOLS = {
                                  C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int, _P]),
     "svt_debug_gemm_batched": (C.c_int, [C.c_int32, C.POINTER(GemmDescC), C.c_int, _P]),
     "svt_debug_layernorm": (C.c_int, [C.POINTER(LayerNormDescC), C.c_int, _P]),
+    "svt_debug_conv0": (C.c_int, [C.POINTER(Conv0DescC), C.c_int, _P]),
     "svt_debug_attention_scores": (C.c_int, [C.c_int32, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64,
                                              C.c_int64, C.c_float, _P, _P, C.c_int, _P]),
     "svt_debug_gemm_pairs": (C.c_int, [C.c_int32, _P, C.c_int64, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64,

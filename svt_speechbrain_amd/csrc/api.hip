@@ -421,6 +421,84 @@ int svt_debug_layernorm(const svt_debug_layernorm_desc* d, int device, void* str
   return rc ? SVT_ERR_INVALID : SVT_OK;
 }
 
+int svt_debug_conv0(const svt_debug_conv0_desc* d, int device, void* stream) {
+  auto refuse = [](const char* why) { set_error(std::string("svt_debug_conv0: ") + why); return SVT_ERR_INVALID; };
+  auto aligned = [](unsigned mask, auto... p) { return !((... | (uintptr_t)p) & mask); };   // a null pointer passes
+  if (!d || d->struct_size != (int32_t)sizeof(svt_debug_conv0_desc)) return refuse("struct_size");
+  const int form = d->form;
+  if (form < 0 || form > 6) return refuse("form is 0 .. 6");
+  // what the launchers leave to their callers (the header says why the hook is narrower): decided here, before anything is launched
+  if (d->k != 10 || d->stride < 1 || d->stride > 5) return refuse("k must be 10 and stride 1 .. 5");
+  if (!aligned(15, d->x, d->wav, d->wav_mom, d->w0, d->b0, d->gamma, d->beta, d->mom, d->wm, d->coef, d->out))
+    return refuse("every buffer 16-byte aligned");
+  const bool pairs = d->pair_kind != 0, mfma = form >= 5;
+  if (form == 0) {
+    if (d->groups < 1 || d->groups > d->groups_max) return refuse("1 <= groups <= groups_max");
+    if (d->n < 1 || (d->groups > 1 && d->n % 4)) return refuse("n >= 1, a multiple of 4 with more than one group");
+    if (!d->x || !d->mom) return refuse("null x / mom");
+  } else {
+    if (d->B < 1 || d->T1 < 1) return refuse("B and T1 must be positive");
+    if (d->L < 10 || (d->L - 10) / d->stride < d->T1 - 1) return refuse("L < (T1 - 1) * stride + 10");
+    if (form == 2 ? !d->wm : !d->wav) return refuse(form == 2 ? "null wm" : "null wav");
+  }
+  if (form == 1 && !d->wm) return refuse("null wm");
+  if (form >= 2) {
+    if (d->C < 1 || d->C > 512 || (form > 2 && d->C % 8)) return refuse("C in 1 .. 512, a multiple of 8 for the forms that write rows");
+    if (mfma && d->C != 512) return refuse("the matrix-pipe forms need C = 512");
+    if (d->pair_kind != 0 && d->pair_kind != 2 && d->pair_kind != 3) return refuse("pair_kind is 0, 2 or 3");
+  }
+  if (form == 2 || form == 4 || form == 6) {
+    if (d->cpg < 1 || d->B % d->cpg) return refuse("cpg >= 1 and a divisor of B");
+    if (d->wav_mom && d->n_wav < 1) return refuse("wav_mom needs n_wav >= 1");
+    if (!d->w0 || !d->gamma || !d->beta) return refuse("null w0 / gamma / beta");
+  }
+  if (form == 2 && !d->coef) return refuse("null coef");
+  if (form >= 3) {
+    if (!d->out) return refuse("null out");
+    if ((form == 3 || form == 5) && !d->coef) return refuse("null coef");
+    if (!mfma && (d->prec < 0 || d->prec > 1)) return refuse("prec is 0 or 1");
+    if (!mfma && pairs && (d->prec || d->C % 32)) return refuse("pair rows need prec 0 and C % 32 == 0");
+    if ((pairs || mfma) && !aligned(127, d->out)) return refuse("a pair-row out and every out of forms 5 and 6 128-byte aligned");
+  }
+  if (int r = check_device(device)) return r;
+  SVT_HIP(hipSetDevice(device));
+  hipStream_t s = (hipStream_t)stream;
+  // scratch: tickets (zeroed once) in front of the partials for forms 0 and 1, the table workspace for forms 5 and 6; the rest 0xFF
+  const int n_tickets = form == 0 ? d->groups_max : form == 1 ? d->B : 0;
+  const size_t bytes = form == 0 ? moments_scratch_bytes(d->groups_max) : form == 1 ? conv0_window_moments_scratch_bytes(d->B, d->T1)
+                     : mfma ? conv0_mfma_table_bytes(d->B) : 0;
+  void* scratch = nullptr;
+  int rc = SVT_OK;
+  if (bytes) {
+    rc = dev_alloc(&scratch, bytes);
+    if (!rc && (hipMemsetAsync(scratch, 0xFF, bytes, s) != hipSuccess ||
+                (n_tickets && hipMemsetAsync(scratch, 0, moments_ticket_bytes(n_tickets), s) != hipSuccess))) {
+      set_error("svt_debug_conv0: hipMemsetAsync"); rc = SVT_ERR_HIP;
+    }
+  }
+  for (int it = 0; !rc && it < (d->repeat > 1 ? d->repeat : 1); ++it) {
+    int lr;
+    if (form == 0) lr = launch_moments(d->x, d->n, d->mom, scratch, d->groups_max, s, d->groups);
+    else if (form == 1) lr = launch_conv0_window_moments(d->wav, d->B, d->L, d->k, d->stride, d->T1, d->wm, scratch, s);
+    else if (form == 2) lr = launch_conv0_group_coef(d->wav_mom, d->n_wav, d->wm, d->B, d->T1, d->C, d->k, d->w0, d->b0, d->gamma, d->beta,
+                                                     d->eps_wav, d->eps, d->coef, s, d->cpg);
+    else if (form == 3) lr = launch_conv0_group_apply(d->prec, d->wav, d->B, d->L, d->k, d->stride, d->T1, d->C, d->coef, d->out, s, d->pair_kind);
+    else if (form == 4) lr = launch_conv0_layer(d->prec, d->wav, d->B, d->L, d->k, d->stride, d->T1, d->C, d->wav_mom, d->n_wav, d->eps_wav, d->w0,
+                                                d->b0, d->gamma, d->beta, d->eps, d->out, s, d->cpg, d->pair_kind);
+    else if (form == 5) lr = launch_conv0_mfma_group(d->wav, d->B, d->L, d->stride, d->T1, d->coef, scratch, d->out, s, d->pair_kind);
+    else lr = launch_conv0_mfma_layer(d->wav, d->B, d->L, d->stride, d->T1, d->wav_mom, d->n_wav, d->eps_wav, d->w0, d->b0, d->gamma, d->beta,
+                                      d->eps, scratch, d->out, s, d->cpg, d->pair_kind);
+    if (lr) rc = SVT_ERR_INVALID;
+  }
+  if (hipStreamSynchronize(s) != hipSuccess && !rc) { set_error("svt_debug_conv0: hipStreamSynchronize"); rc = SVT_ERR_HIP; }
+  if (!rc && n_tickets && d->tickets_out &&
+      hipMemcpy(d->tickets_out, scratch, (size_t)n_tickets * 4, hipMemcpyDeviceToHost) != hipSuccess) {
+    set_error("svt_debug_conv0: hipMemcpy"); rc = SVT_ERR_HIP;
+  }
+  if (scratch) dev_free(scratch);
+  return rc;
+}
+
 int svt_debug_gemm_pairs(int32_t precision, const float* a, int64_t a_elems, const float* w, float* c, const float* bias, int32_t m,
                          int32_t n, int32_t k, int32_t a_rpb, int64_t a_bstride, int64_t a_rstride, int32_t act, int32_t out_kind,
                          int device, void* stream, int32_t time_iters, float* ms_out) {
@@ -604,6 +682,7 @@ int svt_debug_set(int key, int value) {
   else if (key == 38) return g_flash_kernel_id;
   else if (key == 39) return g_gemm_kernel_id;
   else if (key == 40) return g_ln_kernel_id;
+  else if (key == 41) return g_c0_kernel_id;
   else { set_error("svt_debug_set: unknown key"); return SVT_ERR_INVALID; }
   return SVT_OK;
 }

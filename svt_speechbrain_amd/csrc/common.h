@@ -367,6 +367,8 @@ void prof_end(hipStream_t s, double flops, double bytes, int kind = 1);
 
 // ---- sums over the workgroups of a launch (stats.hip): the whole-batch moments, conv layer 0's window moments, the fused frame head ----
 int set_ticket_fenced(int on);   // svt_debug_set key 32 (stats.hip, last_workgroup)
+extern int g_c0_kernel_id;       // key 41 (query): which front-end kernel and instantiation the last launch chose (stats.hip, conv0.hip, conv0_mfma.hip)
+size_t moments_ticket_bytes(int groups);   // the tickets in front of the partials of launch_moments' / launch_conv0_window_moments' scratch
 // moments[0] = sum(x), moments[1] = sum(x^2) over n fp32 values (fp64 accumulation, workgroup partials added in a fixed order: the
 // result is reproducible bit for bit); scratch = moments_scratch_bytes(groups_max) bytes whose first 4 * groups_max bytes are ZERO
 int launch_moments(const float* x, int64_t n, double* moments, void* scratch, int groups_max, hipStream_t s, int groups = 1);  // groups > 1: n elements and 2 doubles per group

@@ -83,6 +83,7 @@ int launch_conv0_group_apply(int prec, const float* wav, int B, int64_t L, int k
   else
     hipLaunchKernelGGL((conv0_group_apply_kernel<float>), grid, dim3(256), 0, s, wav, L, stride, T1, C, coef,
                        (float*)out);
+  g_c0_kernel_id = 400 + (pair_kind ? 10 * pair_kind : prec ? 1 : 0);
   SVT_LAUNCH_CHECK();
   return 0;
 }
@@ -196,7 +197,7 @@ __global__ __launch_bounds__(256) void conv0_layer_kernel(const float* wav, int6
 int launch_conv0_layer(int prec, const float* wav, int B, int64_t L, int k, int stride, int64_t T1, int C,
                        const double* wav_moments, int64_t n_wav, float eps_wav, const float* w0, const float* b0,
                        const float* gamma, const float* beta, float eps, void* out, hipStream_t s, int cpg, int pair_kind) {
-  if (k != K0 || C > 512 || C % 8) { set_error("conv0: unsupported geometry"); return -1; }
+  if (k != K0 || stride > 5 || C > 512 || C % 8) { set_error("conv0: unsupported geometry"); return -1; }   // (the LDS strip holds stride <= 5)
   dim3 grid((unsigned)((T1 + 63) / 64), B);
   if (pair_kind) {
     if (prec || C % 32 || ((uintptr_t)out & 127) || (pair_kind != 2 && pair_kind != 3)) { set_error("conv0: pair-row output needs fp32 storage and C % 32 == 0"); return -1; }
@@ -210,6 +211,7 @@ int launch_conv0_layer(int prec, const float* wav, int B, int64_t L, int k, int 
   else
     hipLaunchKernelGGL((conv0_layer_kernel<float>), grid, dim3(256), 0, s, wav, L, stride, T1, C, wav_moments, n_wav,
                        eps_wav, w0, b0, gamma, beta, eps, (float*)out, cpg);
+  g_c0_kernel_id = 500 + (pair_kind ? 10 * pair_kind : prec ? 1 : 0);
   SVT_LAUNCH_CHECK();
   return 0;
 }

@@ -281,6 +281,7 @@ int launch_conv0_mfma_group(const float* wav, int B, int64_t L, int stride, int6
   if (((uintptr_t)table_ws & 15) || ((uintptr_t)out & 127)) { set_error("conv0_mfma: alignment"); return -1; }
   dim3 grid((unsigned)((T1 + 255) / 256), B);
   int* exps = (int*)((char*)table_ws + (size_t)B * TBL16 * 16);
+  g_c0_kernel_id = pair_kind == 3 ? 630 : pair_kind == 2 ? 620 : 601;
   hipLaunchKernelGGL(conv0_coef_exp_kernel, dim3(B), dim3(256), 0, s, coef, exps);
   SVT_C0_DISPATCH(pair_kind,
     hipLaunchKernelGGL((conv0_table_kernel<PK_>), dim3(TBL16 / 256, B), dim3(256), 0, s, coef, (long)C0 * (K0 + 1), K0 + 1, (const float*)nullptr,
@@ -297,6 +298,7 @@ int launch_conv0_mfma_layer(const float* wav, int B, int64_t L, int stride, int6
                             void* out, hipStream_t s, int cpg, int pair_kind) {
   if (((uintptr_t)table_ws & 15) || ((uintptr_t)out & 127) || ((uintptr_t)gamma & 15) || ((uintptr_t)beta & 15)) { set_error("conv0_mfma: alignment"); return -1; }
   dim3 grid((unsigned)((T1 + 255) / 256), B);
+  g_c0_kernel_id = pair_kind == 3 ? 730 : pair_kind == 2 ? 720 : 701;
   SVT_C0_DISPATCH(pair_kind,
     hipLaunchKernelGGL((conv0_table_kernel<PK_>), dim3(TBL16 / 256, 1), dim3(256), 0, s, w0, 0L, K0, b0, table_ws, (const int*)nullptr);
     hipLaunchKernelGGL((conv0_mfma_kernel<1, PK_>), grid, dim3(256), 0, s, wav, L, stride, T1, (const void*)table_ws, 0L, wav_moments, n_wav,

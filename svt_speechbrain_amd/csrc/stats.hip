@@ -120,7 +120,8 @@ __global__ void global_norm_kernel(const float* x, float* y, int64_t n, const do
 static int moments_grid(int64_t n, int groups) {
   return groups > 1 ? grid_for(n / 4 + 1, 256, 512 / (groups < 64 ? groups : 64) + 1) : grid_for(n / 4 + 1, 256, 512);
 }
-static size_t moments_ticket_bytes(int groups) { return ((size_t)groups * 4 + 255) & ~(size_t)255; }
+int g_c0_kernel_id = 0;  // svt_debug_set key 41 (query): 100 * kernel + 10 * PK + (16-bit rows) of the last front-end launch (include/svt_mi355.h lists the ids)
+size_t moments_ticket_bytes(int groups) { return ((size_t)groups * 4 + 255) & ~(size_t)255; }
 size_t moments_scratch_bytes(int groups_max) {
   // groups < 64: groups * (512 / groups + 1) <= 512 + groups workgroups; otherwise 9 per group
   const size_t wgs = (size_t)(groups_max < 64 ? 512 + groups_max : 576) + 9 * (size_t)groups_max;
@@ -134,6 +135,7 @@ int launch_moments(const float* x, int64_t n, double* moments, void* scratch, in
   if (moments_ticket_bytes(groups_max) + (size_t)gx * groups * 2 * sizeof(double) > moments_scratch_bytes(groups_max)) { set_error("moments: scratch too small"); return -1; }
   unsigned* ticket = (unsigned*)scratch;
   double* part = (double*)((char*)scratch + moments_ticket_bytes(groups_max));
+  g_c0_kernel_id = 100;
   hipLaunchKernelGGL(moments_kernel, dim3(gx, groups), dim3(256), 0, s, x, n, moments, part, ticket);
   SVT_LAUNCH_CHECK();
   return 0;
@@ -260,6 +262,7 @@ int launch_conv0_window_moments(const float* wav, int B, int64_t L, int k, int s
   dim3 grid((unsigned)((T1 + per_block - 1) / per_block), B);
   unsigned* ticket = (unsigned*)scratch;
   double* part = (double*)((char*)scratch + moments_ticket_bytes(B));
+  g_c0_kernel_id = 200;
   hipLaunchKernelGGL(conv0_window_moments_kernel, grid, dim3(256), 0, s, wav, L, stride, T1, wm, part, ticket);
   SVT_LAUNCH_CHECK();
   return 0;
@@ -270,6 +273,7 @@ int launch_conv0_group_coef(const double* wav_moments, int64_t n_wav, const doub
                             float eps_wav, float eps_gn, float* coef, hipStream_t s, int cpg) {
   if (k != K0) { set_error("conv layer 0 kernel size must be 10"); return -1; }
   dim3 grid((C + 63) / 64, B);
+  g_c0_kernel_id = 300;
   hipLaunchKernelGGL(conv0_group_coef_kernel, grid, dim3(64), 0, s, wav_moments, n_wav, wm, T1, C, w0, b0, gamma, beta,
                      eps_wav, eps_gn, coef, cpg);
   SVT_LAUNCH_CHECK();
