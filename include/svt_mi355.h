@@ -568,6 +568,20 @@ typedef struct svt_video_transform { double sub0, div0, mean, std; int32_t crop_
 int svt_video_forward_u8(svt_video* v, const uint8_t* roi_dev, int32_t batch, int32_t t, int32_t h_in, int32_t w_in,
                          const svt_video_transform* tf, float* out_dev, int64_t out_ld, int32_t zero_left, void* workspace_dev,
                          size_t workspace_bytes, void* stream);
+/* ---- the TRAINING recipe's input side, fused: replaces transform_train of N20EMv2/video_only/train_video_ssl.py:448-452 --
+ * Normalize(0, 255) -> RandomCrop((88, 88)) -> HorizontalFlip(0.5) -> Normalize(0.421, 0.165), utils.py:87-129 -- and PaddedBatch's zero
+ * padding of a ragged batch.  As svt_video_forward_u8, but clip b of roi_dev (B, T, h_in, w_in) carries its own crop offsets, flip and
+ * length: crop pixel (y, x) of frame t < n_frames is the pixel map of roi[b, t, y + dy, dx + (flip ? crop_w - 1 - x : x)]; frames
+ * t >= n_frames are exact float zeros (what the reference pads the TRANSFORMED tensor with), whatever bytes roi_dev holds there -- they
+ * are never read.  The random draws are the caller's (svt_speechbrain_amd.video.TrainTransform reproduces the reference's order).
+ * clips_host: `batch` entries on the HOST, free for reuse when the call returns; they travel to the padding kernel inside its arguments,
+ * 64 clips per launch (no device allocation, copy or memset: capturable).  Checked before anything is launched, SVT_ERR_INVALID with the
+ * clip and the field named otherwise: 0 <= dy <= h_in - crop_h, 0 <= dx <= w_in - crop_w, flip 0 or 1, 1 <= n_frames <= t.
+ * Workspace: svt_video_workspace_bytes(v, batch, t, crop_h, crop_w).  out_ld / zero_left as above. */
+typedef struct svt_video_clip { int32_t dy, dx, flip, n_frames; } svt_video_clip;
+int svt_video_forward_u8_clips(svt_video* v, const uint8_t* roi_dev, int32_t batch, int32_t t, int32_t h_in, int32_t w_in,
+                               const svt_video_transform* tf, const svt_video_clip* clips_host, float* out_dev, int64_t out_ld,
+                               int32_t zero_left, void* workspace_dev, size_t workspace_bytes, void* stream);
 
 /* ---- Fbank add-ons: replace speechbrain.processing.features.Deltas (features.py:788-850; replicate padding, kernel
  * -n..n, denominator n(n+1)(2n+1)/3) and ContextWindow (:853-940; out[..., c*ctx + j], zero padding).  x rows have pitch ldx
@@ -719,8 +733,13 @@ int svt_debug_rca_attn_bwd(int32_t precision, const void* qkv, const void* qc, c
  * 100 = moments_kernel; 200 = conv0_window_moments_kernel; 300 = conv0_group_coef_kernel; conv0_group_apply_kernel<float> 400,
  * <16-bit> 401, <float, 2> 420, <float, 3> 430; conv0_layer_kernel<float> 500, <16-bit> 501, <float, 2> 520, <float, 3> 530;
  * conv0_mfma_kernel<0, 0> 601 (with conv0_coef_exp_kernel and conv0_table_kernel<0> in front of it), <0, 2> 620, <0, 3> 630;
- * conv0_mfma_kernel<1, 0> 701 (with conv0_table_kernel<0>), <1, 2> 720, <1, 3> 730 (tests/test_gpu_conv0.py asserts the id of every case).
- * Returns 0 (keys 24, 31: the count; keys 38, 39, 40, 41: the id), SVT_ERR_INVALID for an unknown key or a value a key does not accept (21, 28, 30, 37 above). */
+ * conv0_mfma_kernel<1, 0> 701 (with conv0_table_kernel<0>), <1, 2> 720, <1, 3> 730 (tests/test_gpu_conv0.py asserts the id of every case),
+ * 42 = query: returns which padding kernel the last lip front-end call of this process launched (value ignored; 0 = none yet; set on the
+ * host by every branch of the three launchers of csrc/video.hip) as 100 * family + form: family 1 = video_pad*_kernel (float input),
+ * 2 = video_pad*_u8_kernel (svt_video_forward_u8), 3 = video_pad*_u8_clips_kernel (svt_video_forward_u8_clips); form 0 = the generic
+ * kernel writing fp32, 1 = the generic kernel writing 16-bit, 2 = the 8-pixels-per-16-byte-store kernel of the 16-bit modes
+ * (tests/test_gpu_video_train.py asserts the id of every case).
+ * Returns 0 (keys 24, 31: the count; keys 38, 39, 40, 41, 42: the id), SVT_ERR_INVALID for an unknown key or a value a key does not accept (21, 28, 30, 37 above). */
 int svt_debug_set(int key, int value);
 
 /* ---- measurement hook: HIP-event timing of the dominant kernel on the stream it runs on ----

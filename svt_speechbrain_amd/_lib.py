@@ -53,6 +53,11 @@ class VideoTransformC(C.Structure):
     _fields_ = [("sub0", C.c_double), ("div0", C.c_double), ("mean", C.c_double), ("std", C.c_double), ("crop_h", C.c_int32), ("crop_w", C.c_int32)]
 
 
+class VideoClipC(C.Structure):
+    """svt_video_clip: one clip of svt_video_forward_u8_clips -- crop offsets, horizontal flip (0 / 1) and its number of real frames."""
+    _fields_ = [("dy", C.c_int32), ("dx", C.c_int32), ("flip", C.c_int32), ("n_frames", C.c_int32)]
+
+
 class GemmDescC(C.Structure):
     """svt_debug_gemm_desc: one batched launch of the dense product (svt_debug_gemm_batched); strides in elements."""
     _fields_ = [
@@ -189,6 +194,8 @@ SYMBOLS = {
                                        C.c_void_p, C.c_size_t, C.c_void_p]),
     "svt_video_forward_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(VideoTransformC),
                                        C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "svt_video_forward_u8_clips": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(VideoTransformC),
+                                             C.POINTER(VideoClipC), C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]),
     "svt_deltas": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_int, C.c_void_p]),
     "svt_context_window": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int, C.c_void_p]),
     "svt_bce_loss": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32,

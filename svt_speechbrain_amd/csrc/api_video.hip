@@ -307,12 +307,14 @@ int svt_video_keep_workspace(svt_video* v, int keep) {
   return SVT_OK;
 }
 
-// One body for the three entry points: `video_dev` fp32 (B,1,T,h,w) already normalised, or `roi_dev` uint8 (B,T,h_in,w_in) with the
-// recipe's transform `tf` and crop offsets (dy, dx) fused into the padding pass; out rows with pitch out_ld, `zero_left` columns to the
-// left of every row zeroed by a kernel of the library (zero_cols_kernel: no torch kernel, no memset node -- capturable)
+// One body for the four entry points: `video_dev` fp32 (B,1,T,h,w) already normalised, or `roi_dev` uint8 (B,T,h_in,w_in) with the
+// recipe's transform `tf` and crop offsets (dy, dx) fused into the padding pass -- with `clips` (a host array of `batch` entries, already
+// validated) every clip's own offsets, flip and length instead of (dy, dx); only the padding launch differs; out rows with pitch out_ld,
+// `zero_left` columns to the left of every row zeroed by a kernel of the library (zero_cols_kernel: no torch kernel, no memset node --
+// capturable)
 static int video_forward_impl(svt_video* v, const float* video_dev, const unsigned char* roi_dev, int h_in, int w_in, int dy, int dx,
-                              const VideoTransform* tf, int32_t batch, int32_t t, int32_t h, int32_t w, float* out_dev, int64_t out_ld,
-                              int32_t zero_left, void* workspace_dev, size_t workspace_bytes, void* stream) {
+                              const VideoTransform* tf, const VideoClip* clips, int32_t batch, int32_t t, int32_t h, int32_t w, float* out_dev,
+                              int64_t out_ld, int32_t zero_left, void* workspace_dev, size_t workspace_bytes, void* stream) {
   if (!v || (!video_dev && !roi_dev) || !out_dev || !workspace_dev) { set_error("svt_video_forward: null argument"); return SVT_ERR_INVALID; }
   if (!v->finalized) { set_error("svt_video_forward: call svt_video_finalize first"); return SVT_ERR_STATE; }
   if (batch < 1 || t < 1 || h < 8 || w < 8) { set_error("svt_video_forward: bad geometry"); return SVT_ERR_INVALID; }
@@ -327,7 +329,9 @@ static int video_forward_impl(svt_video* v, const float* video_dev, const unsign
   const int prec = v->prec;
   const size_t es = esize(prec);
   const long F = (long)batch * t;
-  if (roi_dev) {
+  if (roi_dev && clips) {
+    if (launch_video_pad_u8_clips(prec, roi_dev, batch, t, h_in, w_in, h, w, g.Hp0, g.Wp0, *tf, clips, ws.vp, s)) return SVT_ERR_HIP;
+  } else if (roi_dev) {
     if (launch_video_pad_u8(prec, roi_dev, batch, t, h_in, w_in, dy, dx, h, w, g.Hp0, g.Wp0, *tf, ws.vp, s)) return SVT_ERR_HIP;
   } else if (launch_video_pad(prec, video_dev, batch, t, h, w, g.Hp0, g.Wp0, ws.vp, s)) return SVT_ERR_HIP;
   if (zero_left > 0)
@@ -468,11 +472,11 @@ static int video_forward_impl(svt_video* v, const float* video_dev, const unsign
 
 int svt_video_forward(svt_video* v, const float* video_dev, int32_t batch, int32_t t, int32_t h, int32_t w, float* out_dev,
                       void* workspace_dev, size_t workspace_bytes, void* stream) {
-  return video_forward_impl(v, video_dev, nullptr, 0, 0, 0, 0, nullptr, batch, t, h, w, out_dev, v ? v->E : 0, 0, workspace_dev, workspace_bytes, stream);
+  return video_forward_impl(v, video_dev, nullptr, 0, 0, 0, 0, nullptr, nullptr, batch, t, h, w, out_dev, v ? v->E : 0, 0, workspace_dev, workspace_bytes, stream);
 }
 int svt_video_forward_ex(svt_video* v, const float* video_dev, int32_t batch, int32_t t, int32_t h, int32_t w, float* out_dev, int64_t out_ld,
                          int32_t zero_left, void* workspace_dev, size_t workspace_bytes, void* stream) {
-  return video_forward_impl(v, video_dev, nullptr, 0, 0, 0, 0, nullptr, batch, t, h, w, out_dev, out_ld, zero_left, workspace_dev, workspace_bytes, stream);
+  return video_forward_impl(v, video_dev, nullptr, 0, 0, 0, 0, nullptr, nullptr, batch, t, h, w, out_dev, out_ld, zero_left, workspace_dev, workspace_bytes, stream);
 }
 int svt_video_forward_u8(svt_video* v, const uint8_t* roi_dev, int32_t batch, int32_t t, int32_t h_in, int32_t w_in,
                          const svt_video_transform* tf, float* out_dev, int64_t out_ld, int32_t zero_left, void* workspace_dev,
@@ -484,8 +488,36 @@ int svt_video_forward_u8(svt_video* v, const uint8_t* roi_dev, int32_t batch, in
   // CenterCrop (N20EMv2/video_only/utils.py:79-83): delta = int(round(w - tw) / 2.) -- truncation of a non-negative half
   const int dx = (w_in - tf->crop_w) / 2, dy = (h_in - tf->crop_h) / 2;
   const VideoTransform vt{tf->sub0, tf->div0, tf->mean, tf->std};
-  return video_forward_impl(v, nullptr, roi_dev, h_in, w_in, dy, dx, &vt, batch, t, tf->crop_h, tf->crop_w, out_dev, out_ld, zero_left, workspace_dev,
+  return video_forward_impl(v, nullptr, roi_dev, h_in, w_in, dy, dx, &vt, nullptr, batch, t, tf->crop_h, tf->crop_w, out_dev, out_ld, zero_left, workspace_dev,
                             workspace_bytes, stream);
+}
+int svt_video_forward_u8_clips(svt_video* v, const uint8_t* roi_dev, int32_t batch, int32_t t, int32_t h_in, int32_t w_in,
+                               const svt_video_transform* tf, const svt_video_clip* clips_host, float* out_dev, int64_t out_ld,
+                               int32_t zero_left, void* workspace_dev, size_t workspace_bytes, void* stream) {
+  static_assert(sizeof(svt_video_clip) == sizeof(VideoClip), "svt_video_clip and svt::VideoClip are the same four int32");
+  if (!tf || !roi_dev || !clips_host) { set_error("svt_video_forward_u8_clips: null argument"); return SVT_ERR_INVALID; }
+  if (batch < 1 || t < 1) { set_error("svt_video_forward_u8_clips: bad geometry"); return SVT_ERR_INVALID; }
+  if (tf->crop_h < 8 || tf->crop_w < 8 || tf->crop_h > h_in || tf->crop_w > w_in) {
+    set_error("svt_video_forward_u8_clips: the crop must lie inside the ROI"); return SVT_ERR_INVALID; }
+  if (tf->div0 == 0.0 || tf->std == 0.0) { set_error("svt_video_forward_u8_clips: zero divisor in the transform"); return SVT_ERR_INVALID; }
+  // every clip before any launch: an offset outside the ROI would read outside the caller's buffer
+  for (int32_t b = 0; b < batch; ++b) {
+    const svt_video_clip& c = clips_host[b];
+    const char* field = nullptr;
+    int32_t val = 0, lo = 0, hi = 0;
+    if (c.dy < 0 || c.dy > h_in - tf->crop_h) { field = "dy"; val = c.dy; hi = h_in - tf->crop_h; }
+    else if (c.dx < 0 || c.dx > w_in - tf->crop_w) { field = "dx"; val = c.dx; hi = w_in - tf->crop_w; }
+    else if (c.flip != 0 && c.flip != 1) { field = "flip"; val = c.flip; hi = 1; }
+    else if (c.n_frames < 1 || c.n_frames > t) { field = "n_frames"; val = c.n_frames; lo = 1; hi = t; }
+    if (field) {
+      set_error("svt_video_forward_u8_clips: clip " + std::to_string(b) + ": " + field + " = " + std::to_string(val) + " is outside " +
+                std::to_string(lo) + " .. " + std::to_string(hi));
+      return SVT_ERR_INVALID;
+    }
+  }
+  const VideoTransform vt{tf->sub0, tf->div0, tf->mean, tf->std};
+  return video_forward_impl(v, nullptr, roi_dev, h_in, w_in, 0, 0, &vt, reinterpret_cast<const VideoClip*>(clips_host), batch, t, tf->crop_h,
+                            tf->crop_w, out_dev, out_ld, zero_left, workspace_dev, workspace_bytes, stream);
 }
 
 }  // extern "C"

@@ -545,6 +545,14 @@ int launch_video_pad(int prec, const float* v, int B, int T, int H, int W, int H
 struct VideoTransform { double sub0, div0, mean, std; };
 int launch_video_pad_u8(int prec, const unsigned char* v, int B, int T, int Hin, int Win, int dy, int dx, int H, int W, int Hp, int Wp,
                         const VideoTransform& tf, void* out, hipStream_t s);
+// the training recipe's padding pass (svt_video_forward_u8_clips): every clip with its own crop offsets, horizontal flip and length.  The
+// kernels take their clips BY VALUE, kVideoClipsPerLaunch at a time (a larger batch is several launches over clip ranges): `clips` is a
+// host array the caller may reuse as soon as the call returns, and nothing is allocated, copied or memset on the device
+struct VideoClip { int dy, dx, flip, n_frames; };
+constexpr int kVideoClipsPerLaunch = 64;
+int launch_video_pad_u8_clips(int prec, const unsigned char* v, int B, int T, int Hin, int Win, int H, int W, int Hp, int Wp,
+                              const VideoTransform& tf, const VideoClip* clips, void* out, hipStream_t s);
+extern int g_vpad_kernel_id;   // key 42 (query): which padding kernel the last lip front-end call launched (video.hip; include/svt_mi355.h lists the ids)
 int launch_conv3d_front(int prec, const void* vp, const void* w, const float* bias, const float* slope, long F, int T, int Hp,
                         int Wp, int H0, int W0, void* out, hipStream_t s);
 int launch_maxpool_3x3s2(int prec, const void* in, long F, int H0, int W0, int C, int H1, int W1, void* out, hipStream_t s);

@@ -129,6 +129,67 @@ __global__ __launch_bounds__(256) void video_pad8_u8_kernel(const unsigned char*
   }
 }
 
+// ---- the TRAINING recipe's input side: transform_train of N20EMv2/video_only/train_video_ssl.py:448-452 -- Normalize(0, 255) ->
+// RandomCrop((88, 88)) -> HorizontalFlip(0.5) -> Normalize(0.421, 0.165) -- and PaddedBatch's float zeros behind a short clip, in the
+// same one pass.  Clip b carries {dy, dx, flip, n_frames} (drawn on the host in the reference's order, video.py TrainTransform):
+//   out[b, t + 2, y + 3, x + 4] = lut[roi[b, t, y + dy_b, dx_b + (flip_b ? W - 1 - x : x)]]   for t < n_frames_b, +0.0 everywhere else
+// (the halo AND the whole frames past a clip's length: the reference pads the TRANSFORMED tensor with 0.0, and byte 0 would be -2.552).
+// A workgroup stays inside one padded plane: blockIdx.z = clip of this launch, blockIdx.y = padded time index, so the clip's four integers
+// are scalar loads from the kernel arguments and "is this plane all zeros" is wave-uniform (such a plane builds no table and reads no
+// byte).  The table of clips travels in the kernel arguments: no device allocation, copy or memset node, the call stays capturable.
+struct VideoClipTable { VideoClip c[kVideoClipsPerLaunch]; };
+// b0: first clip of this launch (clip blockIdx.z of the table is clip b0 + blockIdx.z of the batch)
+template <typename T>
+__global__ __launch_bounds__(256) void video_pad_u8_clips_kernel(const unsigned char* v, int b0, int Tt, int Hin, int Win, int H, int W, int Hp,
+                                                                int Wp, VideoTransform tf, VideoClipTable tab, T* out) {
+  __shared__ float lut[256];
+  const VideoClip c = tab.c[blockIdx.z];
+  const long b = (long)b0 + blockIdx.z;
+  const int tp = blockIdx.y, t = tp - 2;
+  const bool live = t >= 0 && t < c.n_frames;   // same for the whole workgroup
+  if (live) build_u8_table(lut, tf);
+  const long plane = (long)Hp * Wp;
+  T* o = out + (b * (Tt + 4) + tp) * plane;
+  const unsigned char* frame = v + ((b * Tt + (live ? t : 0)) * Hin + c.dy) * (long)Win + c.dx;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < plane; i += (long)gridDim.x * blockDim.x) {
+    const int xp = (int)(i % Wp), yp = (int)(i / Wp);
+    const int x = xp - 4, y = yp - 3;
+    float val = 0.f;
+    if (live && x >= 0 && x < W && y >= 0 && y < H) val = lut[frame[(long)y * Win + (c.flip ? W - 1 - x : x)]];
+    o[i] = from_f32<T>(val);
+  }
+}
+// 16-bit modes, Wp % 8 == 0: 8 output pixels (one 16-byte store) per thread
+__global__ __launch_bounds__(256) void video_pad8_u8_clips_kernel(const unsigned char* v, int b0, int Tt, int Hin, int Win, int H, int W, int Hp,
+                                                                 int Wp, VideoTransform tf, VideoClipTable tab, bf16_t* out) {
+  __shared__ float lut[256];
+  const VideoClip c = tab.c[blockIdx.z];
+  const long b = (long)b0 + blockIdx.z;
+  const int tp = blockIdx.y, t = tp - 2;
+  const bool live = t >= 0 && t < c.n_frames;
+  if (live) build_u8_table(lut, tf);
+  const int Wg = Wp >> 3;
+  const long groups = (long)Hp * Wg;
+  bf16_t* op = out + (b * (Tt + 4) + tp) * groups * 8;
+  const unsigned char* frame = v + ((b * Tt + (live ? t : 0)) * Hin + c.dy) * (long)Win + c.dx;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < groups; i += (long)gridDim.x * blockDim.x) {
+    const int g = (int)(i % Wg), yp = (int)(i / Wg);
+    const int x0 = g * 8 - 4, y = yp - 3;
+    bf16x8 o;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) o[j] = (bf16_t)0.f;
+    if (live && y >= 0 && y < H) {
+      const unsigned char* row = frame + (long)y * Win;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const int x = x0 + j;
+        if (x >= 0 && x < W) o[j] = (bf16_t)lut[row[c.flip ? W - 1 - x : x]];
+      }
+    }
+    *(bf16x8*)(op + i * 8) = o;
+  }
+}
+
 // exact-fp32 stem (parity mode): one thread per (pixel, channel); w is [35*8][64] (k-major), BN scale folded
 __global__ __launch_bounds__(256) void conv3d_front_f32_kernel(const float* vp, const float* w, const float* bias,
                                                                const float* slope, int Tt, int Hp, int Wp, int H0, int W0,
@@ -478,12 +539,24 @@ unsigned grid_of(long n) {
 
 }  // namespace
 
+// svt_debug_set key 42 (query): 100 * family + form of the padding kernel the last lip front-end call launched, set on the host by every
+// branch of the three launchers below.  family 1 = video_pad*_kernel (float input), 2 = video_pad*_u8_kernel (uint8 ROI, one crop),
+// 3 = video_pad*_u8_clips_kernel (uint8 ROI, per-clip crop / flip / length); form 0 = generic fp32, 1 = generic 16-bit, 2 = 8 pixels
+// per 16-byte store (16-bit)
+int g_vpad_kernel_id = 0;
+
 int launch_video_pad(int prec, const float* v, int B, int T, int H, int W, int Hp, int Wp, void* out, hipStream_t s) {
   const long n = (long)B * (T + 4) * Hp * Wp;
-  if (prec && W % 4 == 0 && Wp % 8 == 0 && ((size_t)v & 15) == 0)
+  if (prec && W % 4 == 0 && Wp % 8 == 0 && ((size_t)v & 15) == 0) {
+    g_vpad_kernel_id = 102;
     hipLaunchKernelGGL(video_pad8_kernel, dim3(grid_of(n / 8)), dim3(256), 0, s, v, B, T, H, W, Hp, Wp, (bf16_t*)out);
-  else if (prec) hipLaunchKernelGGL(video_pad_kernel<bf16_t>, dim3(grid_of(n)), dim3(256), 0, s, v, B, T, H, W, Hp, Wp, (bf16_t*)out);
-  else hipLaunchKernelGGL(video_pad_kernel<float>, dim3(grid_of(n)), dim3(256), 0, s, v, B, T, H, W, Hp, Wp, (float*)out);
+  } else if (prec) {
+    g_vpad_kernel_id = 101;
+    hipLaunchKernelGGL(video_pad_kernel<bf16_t>, dim3(grid_of(n)), dim3(256), 0, s, v, B, T, H, W, Hp, Wp, (bf16_t*)out);
+  } else {
+    g_vpad_kernel_id = 100;
+    hipLaunchKernelGGL(video_pad_kernel<float>, dim3(grid_of(n)), dim3(256), 0, s, v, B, T, H, W, Hp, Wp, (float*)out);
+  }
   SVT_LAUNCH_CHECK();
   return 0;
 }
@@ -491,11 +564,45 @@ int launch_video_pad(int prec, const float* v, int B, int T, int H, int W, int H
 int launch_video_pad_u8(int prec, const unsigned char* v, int B, int T, int Hin, int Win, int dy, int dx, int H, int W, int Hp, int Wp,
                         const VideoTransform& tf, void* out, hipStream_t s) {
   const long n = (long)B * (T + 4) * Hp * Wp;
-  if (prec && Wp % 8 == 0)
+  if (prec && Wp % 8 == 0) {
+    g_vpad_kernel_id = 202;
     hipLaunchKernelGGL(video_pad8_u8_kernel, dim3(grid_of(n / 8)), dim3(256), 0, s, v, B, T, Hin, Win, dy, dx, H, W, Hp, Wp, tf, (bf16_t*)out);
-  else if (prec) hipLaunchKernelGGL(video_pad_u8_kernel<bf16_t>, dim3(grid_of(n)), dim3(256), 0, s, v, B, T, Hin, Win, dy, dx, H, W, Hp, Wp, tf, (bf16_t*)out);
-  else hipLaunchKernelGGL(video_pad_u8_kernel<float>, dim3(grid_of(n)), dim3(256), 0, s, v, B, T, Hin, Win, dy, dx, H, W, Hp, Wp, tf, (float*)out);
+  } else if (prec) {
+    g_vpad_kernel_id = 201;
+    hipLaunchKernelGGL(video_pad_u8_kernel<bf16_t>, dim3(grid_of(n)), dim3(256), 0, s, v, B, T, Hin, Win, dy, dx, H, W, Hp, Wp, tf, (bf16_t*)out);
+  } else {
+    g_vpad_kernel_id = 200;
+    hipLaunchKernelGGL(video_pad_u8_kernel<float>, dim3(grid_of(n)), dim3(256), 0, s, v, B, T, Hin, Win, dy, dx, H, W, Hp, Wp, tf, (float*)out);
+  }
   SVT_LAUNCH_CHECK();
+  return 0;
+}
+
+// the same dispatch as launch_video_pad_u8; grid = (workgroups per padded plane, T + 4 planes, clips of this launch), clips in ranges of
+// kVideoClipsPerLaunch with the range's table copied into the kernel arguments (the launch copies them: `clips` is free on return).
+// A workgroup pays for its 256-entry table (two float64 divisions per thread and a barrier) before its first pixel, so a plane is cut
+// into as few workgroups as still fill the chip: about 2 048 of them (8 per CU) per launch, one per plane from 2 048 planes on.  Measured
+// at 8 x 254 planes of 94 x 96 (profiles/video_train_input.txt): one workgroup per plane 23.8 us, one per 256 or 512 groups of 8 pixels
+// (5 or 3 per plane) 26.2-26.5 us, video_pad8_u8_kernel on the same box 24.5 us
+int launch_video_pad_u8_clips(int prec, const unsigned char* v, int B, int T, int Hin, int Win, int H, int W, int Hp, int Wp,
+                              const VideoTransform& tf, const VideoClip* clips, void* out, hipStream_t s) {
+  if (T + 4 > 65535) { set_error("video front-end: more than 65531 frames per clip in one per-clip padding launch"); return -1; }
+  const bool wide = prec && Wp % 8 == 0;
+  const long per_plane = wide ? (long)Hp * (Wp >> 3) : (long)Hp * Wp;
+  g_vpad_kernel_id = wide ? 302 : (prec ? 301 : 300);
+  for (int b0 = 0; b0 < B; b0 += kVideoClipsPerLaunch) {
+    const int nb = B - b0 < kVideoClipsPerLaunch ? B - b0 : kVideoClipsPerLaunch;
+    VideoClipTable tab = {};
+    for (int i = 0; i < nb; ++i) tab.c[i] = clips[b0 + i];
+    const long planes = (long)(T + 4) * nb, most = (per_plane + 255) / 256;
+    long gx = 2048 / planes;
+    gx = gx < 1 ? 1 : (gx > most ? most : gx);
+    const dim3 grid((unsigned)gx, (unsigned)(T + 4), (unsigned)nb);
+    if (wide) hipLaunchKernelGGL(video_pad8_u8_clips_kernel, grid, dim3(256), 0, s, v, b0, T, Hin, Win, H, W, Hp, Wp, tf, tab, (bf16_t*)out);
+    else if (prec) hipLaunchKernelGGL(video_pad_u8_clips_kernel<bf16_t>, grid, dim3(256), 0, s, v, b0, T, Hin, Win, H, W, Hp, Wp, tf, tab, (bf16_t*)out);
+    else hipLaunchKernelGGL(video_pad_u8_clips_kernel<float>, grid, dim3(256), 0, s, v, b0, T, Hin, Win, H, W, Hp, Wp, tf, tab, (float*)out);
+    SVT_LAUNCH_CHECK();
+  }
   return 0;
 }
 

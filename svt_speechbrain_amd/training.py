@@ -9,6 +9,9 @@ Nothing is computed by torch and there is no CPU fallback.  The encoder's backwa
 
 ``FusionTrainer`` is the audio-visual recipe's step (``N20EMv2/audio_visual/train_rca_av.py:174-185``): ``FusionRCA`` + the head on
 precomputed, frozen audio and video features, with the RCA layers' backward of ``csrc/train_rca.hip``.
+
+``VideoProbe`` is the video recipe's linear-probe step (``N20EMv2/video_only/train_video_ssl.py``): ``LinearProbe`` behind the frozen
+AV-HuBERT encoder on raw uint8 lip ROIs, with the recipe's ``transform_train`` drawn on the host and applied in the padding kernel.
 """
 from __future__ import annotations
 
@@ -359,6 +362,49 @@ class LinearProbe:
         self.last_grad_norm = torch.empty((), dtype=torch.float32, device=dev)
         self.optimizer.step(max_norm=self.max_grad_norm, total_norm=self.last_grad_norm)
         return loss.detach().cpu()
+
+
+class VideoProbe(LinearProbe):
+    """``AMT.fit_batch`` of the video recipe with the AV-HuBERT encoder frozen (``N20EMv2/video_only/train_video_ssl.py:27-49``: the
+    ``linear_prob_epochs`` stage, or ``freeze_encoder: True``): ``modules`` is the recipe's mapping, ``encoder``
+    (``FairseqAVHubertPretrain``) + ``head``.  A step draws the batch's ``transform_train`` parameters on the host in the reference's
+    order (``TrainTransform.plan``), runs the frozen encoder on the RAW uint8 lip ROIs -- crop, flip, pixel map and the zero padding of
+    the ragged batch inside the front-end's padding kernel -- and then ``LinearProbe.fit_features``.  ``last_clips`` keeps the draws of
+    the last step.  The offset term carries no positive weight (the recipe's ``offset_positive_weight: 1.0``)."""
+
+    def __init__(self, modules, transform=None, **hparams):
+        super().__init__(modules, **hparams)
+        from .video import TrainTransform
+        self.transform = transform if transform is not None else TrainTransform()
+        self.last_clips = []
+
+    def fit_batch(self, rois, lens: Optional[torch.Tensor], anno: torch.Tensor, anno_lens: Optional[torch.Tensor] = None,
+                  transform=None) -> torch.Tensor:
+        """One training step from lip ROIs: ``rois`` a list of ``(T_i, H, W)`` uint8 clips (padded here; ``lens`` None takes
+        ``T_i / max T``, the relative lengths ``PaddedBatch`` would give) or an already padded ``(B, T, H, W)`` uint8 tensor with the
+        relative ``lens`` (clip ``b`` has ``round(lens[b] * T)`` real frames; None: all ``T``).  ``lens`` also masks the objective, as
+        ``video_lens`` does in ``compute_objectives``."""
+        from .video import pad_roi_batch
+        tf = transform if transform is not None else self.transform
+        if isinstance(rois, (list, tuple)):
+            roi, n_frames = pad_roi_batch(list(rois))
+            if lens is None:
+                lens = torch.tensor([n / roi.shape[1] for n in n_frames], dtype=torch.float32)
+        else:
+            roi = rois
+            if roi.dtype != torch.uint8 or roi.dim() != 4:
+                raise ValueError(f"expected a list of (T, H, W) uint8 clips or a padded (B, T, H, W) uint8 tensor, got {tuple(roi.shape)} {roi.dtype}")
+            T = roi.shape[1]
+            if lens is None:
+                n_frames = [T] * roi.shape[0]
+            else:
+                n_frames = [int(round(float(l) * T)) for l in torch.as_tensor(lens).reshape(-1).tolist()]
+        if not roi.is_cuda:
+            raise _lib.SvtError("VideoProbe needs its lip ROIs on the GPU; there is no CPU fallback")
+        self.last_clips = tf.plan(n_frames, roi.shape[-2], roi.shape[-1])
+        with torch.no_grad():
+            feats = self.amt._get("encoder")({"video": roi, "audio": None, "transform": tf, "clips": self.last_clips})
+        return self.fit_features(feats, lens, anno, anno_lens)
 
 
 # the 24 fusion tensors in the order of svt_rca_refresh_params / svt_rca_backward (include/svt_mi355.h)

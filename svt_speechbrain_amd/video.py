@@ -12,7 +12,8 @@ from __future__ import annotations
 
 import ctypes as C
 import os
-from typing import Optional
+import random
+from typing import NamedTuple, Optional
 
 import torch
 from torch import nn
@@ -46,6 +47,83 @@ class EvalTransform:
         f = (f - self.sub0) / self.div0
         f = f[..., dy:dy + self.crop_h, dx:dx + self.crop_w]
         return ((f - self.mean) / self.std).astype(np.float32)
+
+    def plan(self, lengths, h: int, w: int):
+        """The ``svt_video_clip`` list of a ragged evaluation batch of ``h`` x ``w`` ROIs: the centre offsets, no flip, clip ``b`` with
+        ``lengths[b]`` real frames (``SubModel.forward_into(roi, clips=...)``)."""
+        dy, dx = self.offsets(h, w)
+        return [VideoClip(dy, dx, 0, int(n)) for n in lengths]
+
+
+class VideoClip(NamedTuple):
+    """``svt_video_clip`` (``include/svt_mi355.h``): what the padding kernel needs to know about one clip of a batch."""
+    dy: int
+    dx: int
+    flip: int
+    n_frames: int
+
+
+class TrainTransform(EvalTransform):
+    """``transform_train`` of the video recipes (``N20EMv2/video_only/train_video_ssl.py:448-452``, classes of ``utils.py:87-129``):
+    ``Normalize(0.0, 255.0)`` -> ``RandomCrop((88, 88))`` -> ``HorizontalFlip(0.5)`` -> ``Normalize(0.421, 0.165)``, then
+    ``.astype(np.float32)`` (:474-476).  The random numbers are drawn on the host, from ``rng`` (default: the ``random`` module, as the
+    reference; a ``random.Random`` is accepted) and in the reference's order -- ``randint(0, w - tw)``, then ``randint(0, h - th)``, then
+    ``random() < flip_ratio``; all three are consumed even when the ROI equals the crop -- so after ``random.seed(s)`` a single-process
+    run draws what the reference draws.  ``plan`` turns a batch's draws into the per-clip table of ``svt_video_forward_u8_clips``, where
+    crop, flip and the pixel map run inside the padding kernel on the raw uint8 ROI; ``__call__`` is the host restatement."""
+
+    def __init__(self, crop=(88, 88), flip_ratio: float = 0.5, image_mean: float = 0.421, image_std: float = 0.165, scale_sub: float = 0.0,
+                 scale_div: float = 255.0, rng=None):
+        super().__init__(crop, image_mean, image_std, scale_sub, scale_div)
+        self.flip_ratio = float(flip_ratio)
+        self.rng = rng if rng is not None else random
+
+    def draw(self, h: int, w: int):
+        """One clip's ``(dy, dx, flip)`` for an ``h`` x ``w`` ROI; consumes three numbers of ``rng``, the WIDTH offset first."""
+        if h < self.crop_h or w < self.crop_w:
+            raise ValueError(f"RandomCrop({self.crop_h}, {self.crop_w}) of a {h} x {w} frame")
+        dx = self.rng.randint(0, w - self.crop_w)           # utils.py:103-104
+        dy = self.rng.randint(0, h - self.crop_h)
+        flip = self.rng.random() < self.flip_ratio          # utils.py:126
+        return dy, dx, bool(flip)
+
+    def __call__(self, frames, draw=None):
+        import numpy as np
+        f = np.asarray(frames)
+        dy, dx, flip = self.draw(f.shape[-2], f.shape[-1]) if draw is None else draw
+        if not (0 <= dy <= f.shape[-2] - self.crop_h and 0 <= dx <= f.shape[-1] - self.crop_w):
+            raise ValueError(f"crop offsets ({dy}, {dx}) outside a {f.shape[-2]} x {f.shape[-1]} frame")
+        f = (f - self.sub0) / self.div0
+        f = f[..., dy:dy + self.crop_h, dx:dx + self.crop_w]
+        if flip:
+            f = f[..., ::-1]
+        return ((f - self.mean) / self.std).astype(np.float32)
+
+    def plan(self, lengths, h: int, w: int):
+        """The ``svt_video_clip`` list of a training batch: one draw per clip, in batch order."""
+        out = []
+        for n in lengths:
+            dy, dx, flip = self.draw(h, w)
+            out.append(VideoClip(dy, dx, int(flip), int(n)))
+        return out
+
+
+def pad_roi_batch(clips):
+    """A list of ``(T_i, H, W)`` uint8 lip ROIs -> ``((B, max T_i, H, W) uint8, [T_i])`` on the clips' device.  The bytes behind a short
+    clip are left uninitialised: the padding kernel never reads them (it writes the float zeros the reference pads with)."""
+    if not clips:
+        raise ValueError("pad_roi_batch: no clips")
+    h, w = clips[0].shape[-2], clips[0].shape[-1]
+    for c in clips:
+        if c.dtype != torch.uint8 or c.dim() != 3 or c.shape[0] < 1:
+            raise ValueError(f"pad_roi_batch: expected (T, H, W) uint8 clips, got {tuple(c.shape)} {c.dtype}")
+        if c.shape[-2] != h or c.shape[-1] != w:
+            raise ValueError(f"pad_roi_batch: ROIs of {h} x {w} and {c.shape[-2]} x {c.shape[-1]} in one batch")
+    lengths = [int(c.shape[0]) for c in clips]
+    out = torch.empty((len(clips), max(lengths), h, w), dtype=torch.uint8, device=clips[0].device)
+    for b, c in enumerate(clips):
+        out[b, :lengths[b]] = c
+    return out, lengths
 
 
 class SubModel(ReplicaAware, nn.Module):
@@ -117,12 +195,17 @@ class SubModel(ReplicaAware, nn.Module):
     def forward(self, x: torch.Tensor, transform: "Optional[EvalTransform]" = None) -> torch.Tensor:
         return self.forward_into(x, None, transform).transpose(1, 2)  # (B, embed_dim, T), the reference's layout
 
-    def forward_into(self, x: torch.Tensor, fused: Optional[torch.Tensor] = None, transform: "Optional[EvalTransform]" = None) -> torch.Tensor:
+    def forward_into(self, x: torch.Tensor, fused: Optional[torch.Tensor] = None, transform: "Optional[EvalTransform]" = None,
+                     clips=None) -> torch.Tensor:
         """The front-end on ``x`` -- a ``(B, 1, T, H, W)`` float tensor already normalised (what the reference's ``SubModel`` takes), or the
         raw ``(B, T, H, W)`` / ``(B, 1, T, H, W)`` / ``(B, T, H, W, 1)`` **uint8** lip ROI, in which case ``transform`` (default: the recipes'
         ``transform_eval``) is applied inside the padding kernel.  Returns ``(B, T, embed_dim)``; with ``fused`` -- an uninitialised
         ``(B, T, 2 * embed_dim)`` fp32 buffer -- the result is written into its right half and the left half is zeroed by the same C-ABI
-        call (AV-HuBERT's ``cat([zeros, video], -1)``, ``hubert.py:700-712``), and ``fused`` is returned."""
+        call (AV-HuBERT's ``cat([zeros, video], -1)``, ``hubert.py:700-712``), and ``fused`` is returned.
+
+        ``clips`` (uint8 input only): one ``VideoClip(dy, dx, flip, n_frames)`` per clip of the batch -- ``TrainTransform.plan`` /
+        ``EvalTransform.plan`` -- instead of the one centre crop: every clip is cropped at its own offsets, mirrored when ``flip``, and
+        its frames from ``n_frames`` on are the float zeros the reference pads a ragged batch with (``svt_video_forward_u8_clips``)."""
         if not x.is_cuda:
             raise _lib.SvtError("the lip front-end needs its input on the GPU; there is no CPU fallback")
         u8 = x.dtype == torch.uint8
@@ -134,6 +217,8 @@ class SubModel(ReplicaAware, nn.Module):
             raise ValueError(f"expected a (B, 1, T, H, W) float lip ROI or a (B, T, H, W) uint8 one, got {tuple(x.shape)} {x.dtype}")
         if transform is not None and not u8:
             raise ValueError("transform applies to the raw uint8 ROI; a float tensor is taken as already normalised")
+        if clips is not None and not u8:
+            raise ValueError("clips apply to the raw uint8 ROI; a float tensor is taken as already cropped, flipped and padded")
         B, T = (x.shape[0], x.shape[1]) if u8 else (x.shape[0], x.shape[2])
         Hin, Win = x.shape[-2], x.shape[-1]
         tf = (transform or EvalTransform()) if u8 else None
@@ -153,7 +238,14 @@ class SubModel(ReplicaAware, nn.Module):
         else:
             out = torch.empty((B, T, E), dtype=torch.float32, device=v.device)
             out_ptr, ld, zl = out.data_ptr(), E, 0
-        if u8:
+        if u8 and clips is not None:
+            if len(clips) != B:
+                raise ValueError(f"{len(clips)} clips for a batch of {B}")
+            tc = _lib.VideoTransformC(tf.sub0, tf.div0, tf.mean, tf.std, tf.crop_h, tf.crop_w)
+            cc = (_lib.VideoClipC * B)(*[_lib.VideoClipC(int(c[0]), int(c[1]), int(c[2]), int(c[3])) for c in clips])
+            _lib.check(lib.svt_video_forward_u8_clips(slot.handle, _lib.ptr(v), B, T, Hin, Win, C.byref(tc), cc, C.c_void_p(out_ptr), ld, zl,
+                                                      _lib.ptr(ws), ws.numel(), _lib.stream_ptr(v.device)), "svt_video_forward_u8_clips", lib)
+        elif u8:
             tc = _lib.VideoTransformC(tf.sub0, tf.div0, tf.mean, tf.std, tf.crop_h, tf.crop_w)
             _lib.check(lib.svt_video_forward_u8(slot.handle, _lib.ptr(v), B, T, Hin, Win, C.byref(tc), C.c_void_p(out_ptr), ld, zl,
                                                 _lib.ptr(ws), ws.numel(), _lib.stream_ptr(v.device)), "svt_video_forward_u8", lib)
@@ -293,7 +385,8 @@ class FairseqAVHubertPretrain(ReplicaAware, nn.Module):
             raise ValueError('expected {"video": (B,1,T,H,W) tensor, "audio": None}')
         if wav.get("audio") is not None:
             raise NotImplementedError("the recipes feed AV-HuBERT the video modality only (audio=None)")
-        video = wav["video"]            # (B, 1, T, H, W) float, normalised -- or the raw uint8 ROI (transform_eval runs in the kernel)
+        video = wav["video"]            # (B, 1, T, H, W) float, normalised -- or the raw uint8 ROI (transform_eval runs in the kernel;
+        #                                 with wav["clips"] every clip's own crop, flip and length: the training recipe's batch)
         fe = self.model.feature_extractor_video
         E = fe.embed_dim
         u8 = video.dtype == torch.uint8
@@ -301,7 +394,8 @@ class FairseqAVHubertPretrain(ReplicaAware, nn.Module):
         T = video.shape[1] if (u8 and not (video.dim() == 5 and video.shape[1] == 1)) else video.shape[2]
         # cat([zeros (absent audio), video], -1) (hubert.py:700-712) written in place by the front-end's own call: its projection stores
         # rows with pitch 2E into the right half, one 2-D memset node zeroes the left half -- no torch fill / strided copy
-        feats = fe.forward_into(video, torch.empty((B, T, 2 * E), dtype=torch.float32, device=video.device), wav.get("transform"))
+        feats = fe.forward_into(video, torch.empty((B, T, 2 * E), dtype=torch.float32, device=video.device), wav.get("transform"),
+                               wav.get("clips"))
         lib = _lib.load(LIB_VARIANT.get(self.precision))
         slot = self._sync(feats.device)
         need = lib.svt_encoder_workspace_bytes(slot.handle, B, T)
