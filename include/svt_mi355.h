@@ -125,8 +125,19 @@ void svt_encoder_destroy(svt_encoder* e);
  * (clips_per_norm_group = 0).  fn = NULL restores the per-shard norms, which is what the reference's DataParallel / DDP runs do. */
 typedef int (*svt_norm_reduce_fn)(double* sums_dev, int32_t n_doubles, void* stream, void* user);
 int svt_encoder_set_norm_reduce(svt_encoder* enc, svt_norm_reduce_fn fn, void* user, int64_t global_clips);
+/* SpecAugment inside the encoder (HF _mask_hidden_states; the wrapper's apply_spec_augment=True).  While masks are set, every
+ * forward of this encoder (svt_encoder_forward, _ex and _forward_head) runs svt_spec_augment's one launch on the fp32 output of the
+ * feature projection, in front of the positional conv, with the parameter "masked_spec_embed" as the embedding.  time_mask_dev:
+ * batch * frames bytes or NULL; feature_mask_dev: batch * hidden_size bytes (4-byte aligned) or NULL; device buffers owned by the
+ * caller, read in stream order by every forward until they are replaced or cleared.  batch / frames: the geometry the masks were made
+ * for -- a forward with another batch or frame count fails with SVT_ERR_INVALID before it launches anything.  (NULL, NULL) clears the
+ * masks (batch and frames are then ignored): the forward is the plain one, with no launch added and no kernel changed.
+ * SVT_ERR_KEY: a time mask on an encoder that never received "masked_spec_embed" (shape (hidden_size,)). */
+int svt_encoder_set_spec_augment(svt_encoder* enc, const uint8_t* time_mask_dev, const uint8_t* feature_mask_dev, int32_t batch,
+                                 int32_t frames);
 /* copy one parameter by its HF state-dict key (without the wrapper's "model." prefix); both weight-norm
  * spellings of the positional conv are accepted (…conv.weight_g/_v and …parametrizations.weight.original0/1).
+ * "masked_spec_embed" (hidden_size) is optional: kept in fp32 for svt_encoder_set_spec_augment.
  * replaces: Module.load_state_dict (speechbrain/utils/checkpoints.py:69-95, train_audio_ssl.py:232-234) */
 int svt_encoder_load_param(svt_encoder* e, const char* key, const void* data_host, int dtype,
                            const int64_t* shape, int ndim);
@@ -314,6 +325,24 @@ int svt_resample(const float* in_dev, int32_t rows, int64_t n_in, int64_t ld_in,
 #define SVT_DROP_MAX_WORKGROUPS 8192
 int svt_drop_freq_chunk(const float* in_dev, int32_t rows, int64_t n, int64_t ld_in, const float* filter_dev, int32_t taps,
                         const int64_t* chunks_dev, int32_t max_chunks, float* out_dev, int64_t ld_out, int device, void* stream);
+
+/* ---- SpecAugment masks on the output of the feature projection: replaces the two index_puts of HF's _mask_hidden_states
+ * (transformers modeling_wav2vec2.py; reached through `apply_spec_augment=True` of MIR_ST500/huggingface_interface.py:97,126-127) ----
+ * In place on h_dev, fp32 (B, T, D) with row pitch ld (elements) between frames:
+ *     h[b][t][c] = 0.0f          if feature_mask[b][c] != 0
+ *                = embed[c]      else if time_mask[b][t] != 0
+ *                = unchanged     otherwise
+ * which is HF's order: the time-masked frames take the learned masked_spec_embed, then the feature-masked columns are zeroed in
+ * every frame of the clip.  time_mask_dev: B*T bytes or NULL; feature_mask_dev: B*D bytes or NULL (both NULL: nothing is launched);
+ * embed_dev: D floats, needed with a time mask.  Masked elements are WRITTEN, not multiplied: a NaN there does not survive; every
+ * other element keeps its bits.  One launch on `stream`, no synchronisation, no allocation, no workspace: a frame with nothing to do
+ * is neither read nor written, a time-masked frame is written without being read, and of the other frames of a clip with masked
+ * columns only the 16-byte pieces that hold one are touched -- the cost follows the masked rows, not B*T*D.  Accesses are 16 bytes
+ * per lane: h_dev and embed_dev 16-byte aligned, feature_mask_dev 4-byte, D and ld multiples of 4, ld >= D.
+ * SVT_ERR_INVALID (nothing is written): B, T or D < 1, D % 4 != 0, ld % 4 != 0, ld < D, h_dev NULL, a time mask without embed_dev,
+ * a misaligned pointer. */
+int svt_spec_augment(float* h_dev, int32_t B, int32_t T, int32_t D, int64_t ld, const uint8_t* time_mask_dev,
+                     const uint8_t* feature_mask_dev, const float* embed_dev, int device, void* stream);
 
 /* ---- wav files: replaces torchaudio.info / load / save and speechbrain.dataio.dataio.read_audio / write_audio for RIFF/WAVE files
  * (MIR_ST500/prepare_benchmarks.py:58, N20EMv2/audio_visual/synthesis_noise.py, MIR_ST500/train_audio_ssl.py:373-390) ----

@@ -41,11 +41,12 @@ class ReplicaAware:
 
 class DeviceSlot:
     """One C object on one device: its handle, what was uploaded into it, and its workspace."""
-    __slots__ = ("key", "handle", "sig", "gen", "ws")
+    __slots__ = ("key", "handle", "sig", "gen", "ws", "masks")
 
     def __init__(self, key):
         self.key = key
         self.handle = None
+        self.masks = None  # encoder: the device tensors svt_encoder_set_spec_augment currently points at (kept alive here), or None
         self.sig = None   # signature of the uploaded parameters (tuple of (data_ptr, version)), or None
         self.gen = -1     # generation of the owner's parameters at upload time
         self.ws: Optional[torch.Tensor] = None
@@ -82,6 +83,7 @@ class DeviceObjects:
                 pass
             s.handle = None
         s.ws = None
+        s.masks = None
 
     def close(self) -> None:
         for s in list(self._slots.values()):

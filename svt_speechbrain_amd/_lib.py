@@ -169,6 +169,8 @@ SYMBOLS = {
     "svt_resample": (C.c_int, [_P, C.c_int32, C.c_int64, C.c_int64, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int64, C.c_int64,
                                C.c_int32, C.c_int, _P]),
     "svt_drop_freq_chunk": (C.c_int, [_P, C.c_int32, C.c_int64, C.c_int64, _P, C.c_int32, _P, C.c_int32, _P, C.c_int64, C.c_int, _P]),
+    "svt_spec_augment": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int64, _P, _P, _P, C.c_int, _P]),
+    "svt_encoder_set_spec_augment": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32]),
     "svt_wav_parse": (C.c_int, [_P, C.c_int64, C.c_int64, C.POINTER(WavInfoC), _I64P]),
     "svt_wav_header": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int64, _P, C.c_int64, _I64P]),
     "svt_pcm_decode": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int64, _P, C.c_int64, C.c_int32, C.c_int, _P]),

@@ -39,6 +39,14 @@ class EncoderConfig:
     # HuBERT ``conv_pos_batch_norm`` (HF modeling_hubert.py HubertPositionalConvEmbedding): BatchNorm1d in front of a plain
     # positional conv instead of the weight-normed conv
     conv_pos_batch_norm: bool = False
+    # SpecAugment (HF _mask_hidden_states; read only with apply_spec_augment=True in training mode): HF's config defaults.  The masks
+    # travel to the device as data, so the C struct has no such fields
+    mask_time_prob: float = 0.05
+    mask_time_length: int = 10
+    mask_time_min_masks: int = 2
+    mask_feature_prob: float = 0.0
+    mask_feature_length: int = 10
+    mask_feature_min_masks: int = 0
 
     @property
     def head_dim(self) -> int:

@@ -3,7 +3,7 @@
 // synchronisation inside a forward call.
 //   finalize: finalize_conv_stack -> finalize_projection -> finalize_pos_conv(_stack) -> encoder LayerNorm -> finalize_layer
 //   forward:  plan_encoder -> carve_encoder -> input_statistics -> choose_pair_rows -> conv_layer0 -> conv_stack -> feature_projection
-//             -> positional_conv -> encoder_layers (post_ln_layers / pre_ln_layers) -> forward_tail
+//             [-> spec_augment] -> positional_conv -> encoder_layers (post_ln_layers / pre_ln_layers) -> forward_tail
 #include "../../include/svt_mi355.h"
 #include "api.h"
 #include "common.h"
@@ -48,6 +48,12 @@ struct svt_encoder {
   svt_norm_reduce_fn reduce_fn = nullptr;
   void* reduce_user = nullptr;
   int64_t reduce_global_clips = 0;
+  // optional SpecAugment masks (svt_encoder_set_spec_augment): caller-owned device bytes, the geometry they were made for, and the
+  // parameter "masked_spec_embed" (fp32; empty when the checkpoint had none)
+  const uint8_t* sa_time = nullptr;
+  const uint8_t* sa_feat = nullptr;
+  int sa_B = 0, sa_T = 0;
+  DevBuf spec_embed;
 };
 
 // every mode but plain fp32 (16-bit storage, or fp32 storage with split-operand products): conv layer 0 on the matrix pipe, the
@@ -282,6 +288,20 @@ int svt_encoder_set_norm_reduce(svt_encoder* e, svt_norm_reduce_fn fn, void* use
   return SVT_OK;
 }
 
+int svt_encoder_set_spec_augment(svt_encoder* e, const uint8_t* time_mask, const uint8_t* feature_mask, int32_t batch, int32_t frames) {
+  if (!e) { set_error("svt_encoder_set_spec_augment: null encoder"); return SVT_ERR_INVALID; }
+  if (!time_mask && !feature_mask) { e->sa_time = e->sa_feat = nullptr; e->sa_B = e->sa_T = 0; return SVT_OK; }
+  if (batch < 1 || frames < 1) { set_error("svt_encoder_set_spec_augment: batch and frames are the geometry the masks were made for"); return SVT_ERR_INVALID; }
+  if ((uintptr_t)feature_mask & 3) { set_error("svt_encoder_set_spec_augment: feature_mask_dev must be 4-byte aligned"); return SVT_ERR_INVALID; }
+  if (e->cfg.hidden_size % 4) { set_error("svt_encoder_set_spec_augment: hidden_size must be a multiple of 4"); return SVT_ERR_INVALID; }
+  if (time_mask && !find(e->params, "masked_spec_embed")) {
+    set_error("svt_encoder_set_spec_augment: a time mask needs the parameter masked_spec_embed, which this encoder never received");
+    return SVT_ERR_KEY;
+  }
+  e->sa_time = time_mask; e->sa_feat = feature_mask; e->sa_B = batch; e->sa_T = frames;
+  return SVT_OK;
+}
+
 int svt_encoder_load_param(svt_encoder* e, const char* key, const void* data_host, int dtype, const int64_t* shape,
                            int ndim) {
   if (!e) { set_error("null encoder"); return SVT_ERR_INVALID; }
@@ -308,6 +328,9 @@ int svt_encoder_finalize(svt_encoder* e) {
   if (int r = c.pos_conv_depth > 1 ? finalize_pos_conv_stack(e) : finalize_pos_conv(e)) return r;
   if (int r = upload_vec(e->params, "encoder.layer_norm.weight", c.hidden_size, &e->enc_g)) return r;
   if (int r = upload_vec(e->params, "encoder.layer_norm.bias", c.hidden_size, &e->enc_b)) return r;
+  if (find(e->params, "masked_spec_embed")) {   // optional: only svt_encoder_set_spec_augment reads it
+    if (int r = upload_vec(e->params, "masked_spec_embed", c.hidden_size, &e->spec_embed)) return r;
+  } else e->spec_embed.release();
   if ((int)e->layers.size() != c.num_layers) { e->layers.clear(); e->layers.resize(c.num_layers); }
   for (int l = 0; l < c.num_layers; ++l)
     if (int r = finalize_layer(e, l)) return r;
@@ -722,6 +745,12 @@ int feature_projection(const EncRun& x, int cur) {
   return launch_gemm(x.p.gp, g, x.s);
 }
 
+// SpecAugment (svt_encoder_set_spec_augment), in place on w.hF between the projection and the positional conv: one launch
+int spec_augment(const EncRun& x) {
+  const svt_encoder* e = x.e;
+  return launch_spec_augment(x.w.hF, x.p.B, (int)x.p.T, x.p.D, x.p.D, e->sa_time, e->sa_feat, e->spec_embed.as<float>(), x.s) ? SVT_ERR_HIP : SVT_OK;
+}
+
 // the grouped conv over the gathered input w.posg as one batched product per (clip, group): kp*cg -> cg columns of C (fp32, row stride D)
 GemmArgs posconv_gemm(const EncRun& x, const DevBuf& W, const DevBuf& bias) {
   const int T = (int)x.p.T, D = x.p.D, G = x.c.pos_conv_groups, cg = D / G, kp = x.c.pos_conv_kernel;
@@ -1021,6 +1050,13 @@ int encoder_forward_impl(svt_encoder* e, const float* wav, int32_t B, int64_t L,
   EncPlan plan;
   if (!plan_encoder(e, B, L, &plan)) { set_error("encoder_forward: waveform shorter than the receptive field"); return SVT_ERR_INVALID; }
   EncRun x{e, e->cfg, plan, carve_encoder(e, plan, workspace), (hipStream_t)stream};
+  const bool masks = e->sa_time || e->sa_feat;
+  if (masks && (e->sa_B != B || e->sa_T != plan.T)) {
+    set_error("encoder_forward: the SpecAugment masks were set for (" + std::to_string(e->sa_B) + ", " + std::to_string(e->sa_T) + ") clips x frames, this call has (" +
+              std::to_string(B) + ", " + std::to_string(plan.T) + ")");
+    return SVT_ERR_INVALID;
+  }
+  if (e->sa_time && !e->spec_embed.p) { set_error("encoder_forward: a time mask is set but masked_spec_embed was not loaded before finalize"); return SVT_ERR_STATE; }
   if (x.w.total > workspace_bytes) { set_error("encoder_forward: workspace too small (" + std::to_string(workspace_bytes) + " < " + std::to_string(x.w.total) + ")"); return SVT_ERR_WORKSPACE; }
   SVT_HIP(hipSetDevice(e->device));
   if (int r = check_norm_groups(x, clips_per_norm_group)) return r;
@@ -1036,6 +1072,8 @@ int encoder_forward_impl(svt_encoder* e, const float* wav, int32_t B, int64_t L,
     if (int r = conv_stack(x, &cur)) return r;
   }
   if (int r = feature_projection(x, cur)) return r;
+  if (masks)
+    if (int r = spec_augment(x)) return r;
   if (int r = positional_conv(x)) return r;
   float* final_x = nullptr;
   if (int r = encoder_layers(x, &final_x)) return r;

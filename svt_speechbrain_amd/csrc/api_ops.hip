@@ -283,6 +283,23 @@ int svt_drop_freq_chunk(const float* in, int32_t rows, int64_t n, int64_t ld_in,
   return SVT_OK;
 }
 
+// ---- SpecAugment masks on a (B, T, D) fp32 tensor, in place (spec_augment.hip) ----
+int svt_spec_augment(float* h, int32_t B, int32_t T, int32_t D, int64_t ld, const uint8_t* time_mask, const uint8_t* feature_mask,
+                     const float* embed, int device, void* stream) {
+  if (B < 1 || T < 1 || D < 1) { set_error("svt_spec_augment: empty tensor"); return SVT_ERR_INVALID; }
+  if (D % 4) { set_error("svt_spec_augment: D must be a multiple of 4 (16-byte accesses)"); return SVT_ERR_INVALID; }
+  if (ld % 4) { set_error("svt_spec_augment: ld must be a multiple of 4 (16-byte accesses)"); return SVT_ERR_INVALID; }
+  if (ld < D) { set_error("svt_spec_augment: ld < D"); return SVT_ERR_INVALID; }
+  if (!h) { set_error("svt_spec_augment: null argument"); return SVT_ERR_INVALID; }
+  if (time_mask && !embed) { set_error("svt_spec_augment: a time mask needs embed_dev (masked_spec_embed)"); return SVT_ERR_INVALID; }
+  if (((uintptr_t)h | (uintptr_t)embed) & 15) { set_error("svt_spec_augment: h_dev and embed_dev must be 16-byte aligned"); return SVT_ERR_INVALID; }
+  if ((uintptr_t)feature_mask & 3) { set_error("svt_spec_augment: feature_mask_dev must be 4-byte aligned"); return SVT_ERR_INVALID; }
+  if (ld > (INT64_MAX / 4 - D) / ((int64_t)B * T)) { set_error("svt_spec_augment: a row pitch too large to address"); return SVT_ERR_INVALID; }
+  if (int r = check_device(device)) return r;
+  if (launch_spec_augment(h, B, T, D, ld, time_mask, feature_mask, embed, (hipStream_t)stream)) return SVT_ERR_HIP;
+  return SVT_OK;
+}
+
 // ---- PCM <-> fp32 on the bytes of a wav file (pcm.hip); the header's parser and writer are host.cpp's ----
 int svt_pcm_decode(const void* src, int32_t format, int32_t channels, int64_t frames, float* out, int64_t ld_out, int32_t downmix,
                    int device, void* stream) {

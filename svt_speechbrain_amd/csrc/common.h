@@ -535,6 +535,11 @@ int launch_resample(const float* in, int rows_out, int64_t n_in, int64_t ld_in, 
 // max_chunks 0: none.  One launch
 int launch_drop_freq_chunk(const float* in, int rows, int64_t n, int64_t ld_in, const float* filter, int taps, const int64_t* chunks,
                            int max_chunks, float* out, int64_t ld_out, hipStream_t s);
+// SpecAugment masks on the feature projection's output (spec_augment.hip), in place on h (B, T, D) fp32 with row pitch ld: a frame whose
+// time byte is set becomes embed, then the columns whose feature byte is set are zeroed in every frame of the clip.  Either mask may be
+// null (both: no launch).  One launch; frames with nothing to do are neither read nor written
+int launch_spec_augment(float* h, int B, int T, int D, int64_t ld, const uint8_t* time_mask, const uint8_t* feat_mask, const float* embed,
+                        hipStream_t s);
 // PCM <-> fp32 on the bytes of a wav file (pcm.hip): interleaved little-endian frames at any byte address <-> planar fp32 rows (4-byte
 // aligned, pitch ld >= frames); format = svt_pcm_format (encode: S16 or F32); downmix: 2 channels -> the one row 0.5 * (l + r).  One launch
 int launch_pcm_decode(const void* src, int format, int channels, int64_t frames, float* out, int64_t ld, bool downmix, hipStream_t s);

@@ -115,7 +115,10 @@ def _config_from_dir(path: str) -> Optional[EncoderConfig]:
         feat_proj_layer_norm=bool(j.get("feat_proj_layer_norm", True)) or fam != "hubert",
         num_conv_pos_embedding_groups=j.get("num_conv_pos_embedding_groups", 16),
         layer_norm_eps=j.get("layer_norm_eps", 1e-5),
-        conv_pos_batch_norm=bool(j.get("conv_pos_batch_norm", False)) and fam == "hubert", **kw)
+        conv_pos_batch_norm=bool(j.get("conv_pos_batch_norm", False)) and fam == "hubert",
+        mask_time_prob=float(j.get("mask_time_prob", 0.05)), mask_time_length=int(j.get("mask_time_length", 10)),
+        mask_time_min_masks=int(j.get("mask_time_min_masks", 2)), mask_feature_prob=float(j.get("mask_feature_prob", 0.0)),
+        mask_feature_length=int(j.get("mask_feature_length", 10)), mask_feature_min_masks=int(j.get("mask_feature_min_masks", 0)), **kw)
 
 
 class _DevF64:
@@ -157,8 +160,7 @@ class HuggingFaceWav2Vec2(ReplicaAware, nn.Module):
                  precision: Optional[str] = None, normalize_wav: Optional[bool] = None, seed: int = 1986,
                  allow_random_init: bool = True):
         super().__init__()
-        if apply_spec_augment:
-            raise NotImplementedError("apply_spec_augment is a training-time mask; the MI355X path is forward-only")
+        self.apply_spec_augment = bool(apply_spec_augment)
         cfg = config
         local_ckpt = None
         if cfg is None and isinstance(source, str) and os.path.isdir(source):
@@ -212,6 +214,13 @@ class HuggingFaceWav2Vec2(ReplicaAware, nn.Module):
         self.model = ParamTree()
         for k, v in seeded_encoder_state_dict(cfg, seed=seed).items():
             self.model.add(k, v)
+        if self.apply_spec_augment:
+            # HF's masked_spec_embed (hidden_size,), uniform_() like Wav2Vec2Model.__init__, from a generator of ITS OWN: inside the
+            # sequential draw above it would move every other seeded weight.  A local checkpoint's value replaces it below
+            g = torch.Generator().manual_seed((int(seed) + 0x5BEC) & 0x7FFFFFFFFFFFFFFF)
+            self.model.add("masked_spec_embed", torch.empty(cfg.hidden_size, dtype=torch.float32).uniform_(generator=g))
+        self._mask_staging = None   # spec_augment.MaskStaging, made by the first forward that uploads a mask
+        self.last_spec_masks = (None, None)   # (time, feature) bool arrays the last forward applied (None: that mask was not applied)
         # device side: one C object per device (shared with nn.DataParallel replicas, see _device.py) and ONE generation
         # counter of the parameter values, shared BY REFERENCE with every replica(): whoever changes the weights bumps it,
         # every device object compares it before a forward
@@ -261,13 +270,15 @@ class HuggingFaceWav2Vec2(ReplicaAware, nn.Module):
 
     def _pre_load_hook(self, state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs):
         """Runs at the top of ``self.model``'s ``_load_from_state_dict`` (whatever module ``load_state_dict`` was called
-        on): both weight-norm spellings of the positional conv are accepted, HF's ``masked_spec_embed`` is dropped."""
+        on): both weight-norm spellings of the positional conv are accepted, HF's ``masked_spec_embed`` is dropped unless
+        ``apply_spec_augment`` made it a parameter."""
         pc = prefix + "encoder.pos_conv_embed.conv."
         for old, new in ((pc + "weight_g", pc + "parametrizations.weight.original0"),
                          (pc + "weight_v", pc + "parametrizations.weight.original1")):
             if old in state_dict:
                 state_dict[new] = state_dict.pop(old)
-        state_dict.pop(prefix + "masked_spec_embed", None)
+        if not self.apply_spec_augment:
+            state_dict.pop(prefix + "masked_spec_embed", None)
 
     def _post_load_hook(self, module, incompatible_keys):
         self._invalidate()
@@ -313,7 +324,7 @@ class HuggingFaceWav2Vec2(ReplicaAware, nn.Module):
 
     def _normalise_keys(self, sd):
         """Accept both weight-norm spellings of the positional conv and drop the HF-only
-        ``masked_spec_embed`` (SpecAugment embedding, unused: apply_spec_augment=False, reference :127)."""
+        ``masked_spec_embed`` (SpecAugment embedding, reference :127) unless ``apply_spec_augment`` made it a parameter."""
         pc = "encoder.pos_conv_embed.conv."
         ren = {pc + "weight_g": pc + "parametrizations.weight.original0",
                pc + "weight_v": pc + "parametrizations.weight.original1"}
@@ -323,7 +334,7 @@ class HuggingFaceWav2Vec2(ReplicaAware, nn.Module):
                 if k.startswith(pre) and k[len(pre):] in ren:
                     k = pre + ren[k[len(pre):]]
                     break
-            if k.endswith("masked_spec_embed"):
+            if k.endswith("masked_spec_embed") and not self.apply_spec_augment:
                 continue
             out[k] = v
         return out
@@ -463,24 +474,97 @@ class HuggingFaceWav2Vec2(ReplicaAware, nn.Module):
         else:
             _lib.check(lib.svt_encoder_set_norm_reduce(handle, C.cast(nr[0], C.c_void_p), None, nr[1]), "svt_encoder_set_norm_reduce", lib)
 
+    # ------------------------------------------------------------------ SpecAugment (HF _mask_hidden_states)
+    def _as_mask(self, m, device, cols: int, what: str):
+        """An explicit mask -> [bool array for ``last_spec_masks`` or None, uint8 device tensor or None, host array to upload or None,
+        its (rows, columns)].  ``cols`` = 0: any column count (the C side checks a time mask's frames against the forward's)."""
+        if torch.is_tensor(m) and m.is_cuda:
+            if m.dim() != 2 or (cols and m.shape[1] != cols):
+                raise ValueError(f"{what} must be a (batch, {cols or 'frames'}) mask, got shape {tuple(m.shape)}")
+            return [None, m.to(device=device, dtype=torch.uint8).contiguous(), None, tuple(m.shape)]
+        import numpy as np
+        a = np.ascontiguousarray(m.numpy() if torch.is_tensor(m) else m).astype(bool)
+        if a.ndim != 2 or (cols and a.shape[1] != cols):
+            raise ValueError(f"{what} must be a (batch, {cols or 'frames'}) mask, got shape {a.shape}")
+        return [a, None, a, a.shape]
+
+    def _set_spec_masks(self, lib, slot, device, B: int, T: int, mask_time_indices, mask_feature_indices) -> None:
+        """Point the device object at this forward's masks, or clear them.  With ``apply_spec_augment`` and the model in training
+        mode the two masks are drawn as HF draws them (time, then feature, each only with a probability above 0); explicit masks
+        bypass the draw and apply in any mode, as a passed ``mask_time_indices`` does in HF.  Otherwise nothing is drawn -- numpy's
+        generator is not touched -- and the forward is the plain one."""
+        from . import spec_augment as SA
+        explicit = mask_time_indices is not None or mask_feature_indices is not None
+        if explicit and not self.apply_spec_augment:
+            raise ValueError("mask_time_indices / mask_feature_indices need apply_spec_augment=True (HF applies no mask without it)")
+        tm, fm = [None, None, None, None], [None, None, None, None]
+        if explicit:
+            if mask_time_indices is not None:
+                tm = self._as_mask(mask_time_indices, device, 0, "mask_time_indices")
+            if mask_feature_indices is not None:
+                fm = self._as_mask(mask_feature_indices, device, self.config.hidden_size, "mask_feature_indices")
+        elif self.apply_spec_augment and self.model.training:
+            t, f = SA.draw_masks(self.config, B, T)
+            tm, fm = [t, None, t, getattr(t, "shape", None)], [f, None, f, getattr(f, "shape", None)]
+        if tm[2] is not None or fm[2] is not None:
+            if self._mask_staging is None:
+                self._mask_staging = SA.MaskStaging()
+            with torch.cuda.device(device):
+                up = self._mask_staging.upload(device, tm[2], fm[2])
+            if tm[2] is not None:
+                tm[1] = up[0]
+            if fm[2] is not None:
+                fm[1] = up[1]
+        self.last_spec_masks = (tm[0], fm[0])
+        t_dev, f_dev = tm[1], fm[1]
+        if t_dev is None and f_dev is None:
+            if slot.masks is not None:   # only a handle that had masks is told to drop them: the plain path makes no extra call
+                _lib.check(lib.svt_encoder_set_spec_augment(slot.handle, None, None, 0, 0), "svt_encoder_set_spec_augment", lib)
+                slot.masks = None
+            return
+        rows = {int(m[3][0]) for m in (tm, fm) if m[1] is not None}
+        if len(rows) != 1:
+            raise ValueError("mask_time_indices and mask_feature_indices disagree on the batch size")
+        # the geometry the masks were made for: the C side refuses a forward whose (batch, frames) differ
+        _lib.check(lib.svt_encoder_set_spec_augment(slot.handle, _lib.ptr(t_dev) if t_dev is not None else None,
+                                                    _lib.ptr(f_dev) if f_dev is not None else None, rows.pop(),
+                                                    int(tm[3][1]) if t_dev is not None else T),
+                   "svt_encoder_set_spec_augment", lib)
+        slot.masks = (t_dev, f_dev)
+
     # ------------------------------------------------------------------ forward (reference :263-297)
-    def forward(self, wav: torch.Tensor, clips_per_norm_group: int = 0) -> torch.Tensor:
+    def forward(self, wav: torch.Tensor, clips_per_norm_group: int = 0, *, mask_time_indices=None,
+                mask_feature_indices=None) -> torch.Tensor:
         """``clips_per_norm_group`` (extension; 0 = the reference: both whole-tensor layer norms over the entire batch):
         with 1, a batch of B equal-length utterances returns what B batch-1 forwards return, which is how the reference
-        evaluates (``train_audio_ssl.py:90`` asserts batch 1) -- one batched launch sequence instead of B."""
+        evaluates (``train_audio_ssl.py:90`` asserts batch 1) -- one batched launch sequence instead of B.
+
+        ``apply_spec_augment=True`` (reference :97,126-127; HF ``_mask_hidden_states``): in training mode (``freeze=False``;
+        ``freeze=True`` puts the model in ``eval()``) every forward draws the ``(B, T)`` time mask and then the ``(B, D)`` feature
+        mask from numpy's global generator exactly as HF does (``spec_augment.compute_mask_indices``; ``mask_*`` fields of the
+        checkpoint's config.json), and one kernel between the feature projection and the positional conv overwrites the masked
+        frames with ``masked_spec_embed`` and zeroes the masked columns.  ``last_spec_masks`` holds what was applied.  In eval mode
+        nothing is drawn and the forward is the plain one.  ``mask_time_indices`` / ``mask_feature_indices`` (extension, keyword
+        only; bool ``(B, T)`` / ``(B, D)`` on the host or the device) bypass the draw and apply in any mode; they need the flag.
+        The reference in training mode also runs the checkpoint's dropouts and layerdrop; this path does not (it stays
+        deterministic), so parity is with the reference at dropout = layerdrop = 0, which is how every golden is made.  Under
+        ``nn.DataParallel`` each replica draws for its own sub-batch: the draws match the reference's for the single-process order only."""
         if not self.freeze and torch.is_grad_enabled() and not self._warned_grad:
             warnings.warn("svt_speechbrain_amd.HuggingFaceWav2Vec2 is forward-only: the output is detached "
                           "(fine-tuning the encoder is out of scope of the MI355X path)")
             self._warned_grad = True
         with torch.no_grad():
-            return self.extract_features(wav, clips_per_norm_group).detach()
+            return self.extract_features(wav, clips_per_norm_group, mask_time_indices=mask_time_indices,
+                                         mask_feature_indices=mask_feature_indices).detach()
 
     def forward_head(self, wav: torch.Tensor, head, clips_per_norm_group: int = 0, frames: Optional[torch.Tensor] = None,
-                     pitch_octave_num: int = 4, pitch_class_num: int = 12) -> torch.Tensor:
+                     pitch_octave_num: int = 4, pitch_class_num: int = 12, *, mask_time_indices=None,
+                     mask_feature_indices=None) -> torch.Tensor:
         """``head(self(wav))`` -- the two module calls of ``AMT.compute_forward`` (train_audio_ssl.py:36-39) -- as ONE C-ABI call
         that never writes the (B, T, D) features: the whole-batch output norm, the frame head (``svt_speechbrain_amd.Linear``
         with <= 32 outputs) and, when ``frames`` (a ``(B*T, 4)`` int32 device tensor) is given, the per-frame sigmoid / argmax
-        are fused behind the encoder (``svt_encoder_forward_head``).  Returns the ``(B, T, n_out)`` logits."""
+        are fused behind the encoder (``svt_encoder_forward_head``).  Returns the ``(B, T, n_out)`` logits.  SpecAugment masks are
+        drawn or taken as in ``forward``."""
         if wav.dim() != 2:
             raise ValueError(f"expected a (batch, samples) waveform, got shape {tuple(wav.shape)}")
         if not wav.is_cuda:
@@ -502,6 +586,7 @@ class HuggingFaceWav2Vec2(ReplicaAware, nn.Module):
         if frames is not None and (frames.dtype != torch.int32 or frames.numel() != B * T * 4 or not frames.is_contiguous()):
             raise ValueError("frames must be a contiguous int32 tensor of B*T*4 elements (16 bytes per frame)")
         self._apply_norm_reduce(lib, slot.handle)
+        self._set_spec_masks(lib, slot, x.device, B, T, mask_time_indices, mask_feature_indices)
         with torch.no_grad():
             _lib.check(lib.svt_encoder_forward_head(slot.handle, hslot.handle, _lib.ptr(x), B, L, _lib.ptr(logits),
                                                     _lib.ptr(frames) if frames is not None else None, int(pitch_octave_num),
@@ -516,7 +601,8 @@ class HuggingFaceWav2Vec2(ReplicaAware, nn.Module):
         return (isinstance(head, Linear) and not head.combine_dims and head.w.in_features in (512, 768, 1024)
                 and 1 <= head.w.out_features <= 32)
 
-    def extract_features(self, wav: torch.Tensor, clips_per_norm_group: int = 0) -> torch.Tensor:
+    def extract_features(self, wav: torch.Tensor, clips_per_norm_group: int = 0, *, mask_time_indices=None,
+                         mask_feature_indices=None) -> torch.Tensor:
         if wav.dim() != 2:
             raise ValueError(f"expected a (batch, samples) waveform, got shape {tuple(wav.shape)}")
         if not wav.is_cuda:
@@ -534,6 +620,7 @@ class HuggingFaceWav2Vec2(ReplicaAware, nn.Module):
         ws = slot.workspace(need, x.device)
         out = torch.empty((B, T, self.config.hidden_size), dtype=torch.float32, device=x.device)
         self._apply_norm_reduce(lib, slot.handle)
+        self._set_spec_masks(lib, slot, x.device, B, T, mask_time_indices, mask_feature_indices)
         _lib.check(lib.svt_encoder_forward_ex(slot.handle, _lib.ptr(x), B, L, _lib.ptr(out), _lib.ptr(ws),
                                               ws.numel(), _lib.stream_ptr(x.device), int(clips_per_norm_group)),
                    "svt_encoder_forward", lib)

@@ -299,7 +299,10 @@ class LinearProbe:
 
     def fit_batch(self, wavs: torch.Tensor, wav_lens: Optional[torch.Tensor], anno: torch.Tensor,
                   anno_lens: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """One training step from waveforms: the frozen encoder, then ``fit_features``."""
+        """One training step from waveforms: the frozen encoder, then ``fit_features``.  An encoder built with
+        ``apply_spec_augment=True, freeze=False`` (weights untouched by this step, model in training mode) draws and applies its
+        SpecAugment masks inside that call -- one time-mask draw (and one feature-mask draw when its probability is above 0) per
+        step, nothing to do here (tests/test_gpu_spec_augment.py checks the draws and the loss terms)."""
         with torch.no_grad():
             feats = self.amt._get("wav2vec2")(wavs)
         return self.fit_features(feats, wav_lens, anno, anno_lens)
