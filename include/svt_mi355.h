@@ -767,9 +767,63 @@ int svt_debug_rca_attn_bwd(int32_t precision, const void* qkv, const void* qc, c
  * host by every branch of the three launchers of csrc/video.hip) as 100 * family + form: family 1 = video_pad*_kernel (float input),
  * 2 = video_pad*_u8_kernel (svt_video_forward_u8), 3 = video_pad*_u8_clips_kernel (svt_video_forward_u8_clips); form 0 = the generic
  * kernel writing fp32, 1 = the generic kernel writing 16-bit, 2 = the 8-pixels-per-16-byte-store kernel of the 16-bit modes
- * (tests/test_gpu_video_train.py asserts the id of every case).
- * Returns 0 (keys 24, 31: the count; keys 38, 39, 40, 41, 42: the id), SVT_ERR_INVALID for an unknown key or a value a key does not accept (21, 28, 30, 37 above). */
+ * (tests/test_gpu_video_train.py asserts the id of every case), 43 = query: returns which kernels the last step of the lip front-end
+ * launched in this process (value ignored; 0 = none yet; set on the host by every branch of the launchers of csrc/video.hip and, for a
+ * BasicBlock, by video_block of csrc/api_video.hip; a forward leaves its last block's or pooling launch's id): 100 =
+ * conv3d_front_f32_kernel, 101 = conv3d_front_bf16_kernel (the 16-bit stem alone), 300 = conv3d_front_pool_kernel (stem + max-pool);
+ * 200 = maxpool_3x3s2_kernel<float>, 201 = maxpool_3x3s2_kernel<16-bit>, 202 = maxpool_3x3s2_bf16x8_kernel; 400 = zero_halo_kernel;
+ * 600 = avgpool_interior_kernel<float>, 601 = <16-bit>; a BasicBlock 5000 + 100 * conv1 + 10 * downsample + conv2 with the codes
+ * 0 = none (downsample of a block that has none), 1 = conv3x3_c64_kernel, 2 = conv3x3_c128_kernel, 3 = grouped product G = 2,
+ * 4 = grouped product G = 4, 5 = plain product, 6 = the combined conv1 + downsample product (conv1 and downsample both 6); for the
+ * product launches key 39 names the GEMM kernel of the block's last product (tests/test_gpu_video_kernels.py asserts the id of every
+ * case).
+ * Returns 0 (keys 24, 31: the count; keys 38, 39, 40, 41, 42, 43: the id), SVT_ERR_INVALID for an unknown key or a value a key does not accept (21, 28, 30, 37 above). */
 int svt_debug_set(int key, int value);
+
+/* ---- test hook: ONE step of a finalized lip front-end on caller-supplied device buffers; tests/test_gpu_video_kernels.py ----
+ * The step runs with the handle's own uploaded weights (the BatchNorm folds, grouped matrices, fragment images and the combined
+ * conv1 + downsample matrix of svt_video_finalize are inside the tested unit), through the same functions the forward calls, with the
+ * forward's own choice of kernel; the stream is synchronised before the call returns.  Elements are fp32 for an fp32 / split-operand
+ * handle and the build's 16-bit type otherwise; "haloed" = channels-last [F][H + 2][W + 2][C] with a one-pixel halo that the CALLER zeroes
+ * (the kernels write interiors only).  H0 = (h - 1) / 2 + 1, H1 = (H0 - 1) / 2 + 1, likewise for widths.  `step`:
+ *   1  the stem alone: launch_video_pad of the fp32 video `x` (B, 1, T, h, w) into scratch of the hook, then launch_conv3d_front ->
+ *      out [B T][H0][W0][64].
+ *   2  launch_maxpool_3x3s2: x [F][H][W][64] (H, W = H0, W0) -> the interior of the haloed out [F][H1 + 2][W1 + 2][64].
+ *   3  pad as in step 1, then the fused launch_conv3d_front_pool -> the interior of the haloed out [B T][H1 + 2][W1 + 2][64].
+ *   4  launch_zero_halo of out [F][H][W][C] (H, W = the PADDED sizes here).
+ *   5  BasicBlock `b` of stage `li` over the haloed block input `x` [F][H + 2][W + 2][Cin]: conv1 -> t1, the 1x1 / 2 downsample of the first
+ *      block of stages 1 .. 3 -> ds, the block's output -> out (all haloed, at the block's output size: (H - 1) / 2 + 1 where the block
+ *      has stride 2).  svt_debug_set(43, 0) afterwards says which of them were written and by what.  As in the workspace, the combined
+ *      conv1 + downsample product runs only when ds lies behind t1 at a multiple of 32 bytes (16-bit) -- carve both from one
+ *      allocation.  The grouped product G = 4 reads ONE pixel (64 elements) behind the last frame of `x` and of t1, which the forward
+ *      keeps zero behind its stage-1 buffers: the caller provides and zeroes it.
+ *   6  launch_avgpool_interior: haloed x [F][H + 2][W + 2][512] -> out [F][512].
+ * The padded operand of steps 1 and 3 is filled with 0xFF bytes before the pad launch: padding a pad kernel does not write is NaN.
+ * workgroups: 0 = the launcher's choice; n > 0 caps the persistent grid of conv3x3_c64_kernel, conv3x3_c128_kernel and
+ * conv3d_front_pool_kernel, so that a few frames give each workgroup several (ignored by the other kernels).
+ * The hook never forces a path the forward would not take: svt_debug_set keys 23, 26 and 27 select the other arms, and step 3 refuses
+ * where conv3d_front_pool_ok is false.  It is NARROWER than the launchers: it refuses (SVT_ERR_INVALID, nothing is launched) a wrong
+ * struct_size, a NULL or unfinalized handle, step outside 1 .. 6, workgroups < 0, a NULL pointer where the step needs one (x, out; t1
+ * for step 5; ds for a block with a downsample), ANY non-NULL pointer that is not 16-byte aligned, B < 1, T < 1, h < 8 or w < 8 (steps
+ * 1, 3), a 16-bit stem whose five padded planes do not fit 160 KB of LDS (step 1), a geometry the fused kernel is not eligible for (step
+ * 3), F < 1, H < 1 or W < 1 (steps 2, 4, 5, 6), H < 3, W < 3 or C outside {64, 128, 256, 512} (step 4), li outside 0 .. 3 or b outside
+ * 0 .. 1 (step 5), more than 2e9 pixels.  A launcher's own refusal comes back as SVT_ERR_INVALID too.  struct_size = the size of the
+ * structure. */
+typedef struct svt_debug_video_desc {
+  int32_t struct_size;
+  int32_t step;
+  int32_t B, T;
+  int32_t h, w;
+  int64_t F;
+  int32_t H, W;
+  int32_t C, li;
+  int32_t b, workgroups;
+  const void* x;
+  void* t1;
+  void* ds;
+  void* out;
+} svt_debug_video_desc;
+int svt_debug_video_step(svt_video* v, const svt_debug_video_desc* d, void* stream);
 
 /* ---- measurement hook: HIP-event timing of the dominant kernel on the stream it runs on ----
  * When enabled, forward calls bracket every launch of the dense contraction kernel with hipEvents on

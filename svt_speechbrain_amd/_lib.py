@@ -114,6 +114,21 @@ class Conv0DescC(C.Structure):
     ]
 
 
+class VideoStepDescC(C.Structure):
+    """svt_debug_video_desc: one step of a finalized lip front-end on caller-supplied device buffers (svt_debug_video_step); step 1 .. 6."""
+    _fields_ = [
+        ("struct_size", C.c_int32),
+        ("step", C.c_int32),
+        ("B", C.c_int32), ("T", C.c_int32),
+        ("h", C.c_int32), ("w", C.c_int32),
+        ("F", C.c_int64),
+        ("H", C.c_int32), ("W", C.c_int32),
+        ("C", C.c_int32), ("li", C.c_int32),
+        ("b", C.c_int32), ("workgroups", C.c_int32),
+        ("x", C.c_void_p), ("t1", C.c_void_p), ("ds", C.c_void_p), ("out", C.c_void_p),
+    ]
+
+
 class WavInfoC(C.Structure):
     """svt_wav_info: what svt_wav_parse reads from a RIFF/WAVE header; format is a svt_pcm_format (U8 = 1 .. F64 = 6)."""
     _fields_ = [("format", C.c_int32), ("channels", C.c_int32), ("sample_rate", C.c_int32), ("bits_per_sample", C.c_int32),
@@ -180,6 +195,7 @@ SYMBOLS = {
     "svt_debug_gemm_batched": (C.c_int, [C.c_int32, C.POINTER(GemmDescC), C.c_int, _P]),
     "svt_debug_layernorm": (C.c_int, [C.POINTER(LayerNormDescC), C.c_int, _P]),
     "svt_debug_conv0": (C.c_int, [C.POINTER(Conv0DescC), C.c_int, _P]),
+    "svt_debug_video_step": (C.c_int, [_P, C.POINTER(VideoStepDescC), _P]),
     "svt_debug_attention_scores": (C.c_int, [C.c_int32, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64,
                                              C.c_int64, C.c_float, _P, _P, C.c_int, _P]),
     "svt_debug_gemm_pairs": (C.c_int, [C.c_int32, _P, C.c_int64, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64,

@@ -69,7 +69,8 @@ size_t video_carve(const svt_video* v, int B, int T, const VGeom& g, void* base,
   w.vp = c.take((size_t)B * (T + 4) * g.Hp0 * g.Wp0 * es);
   w.o0 = c.take(F * g.H0 * g.W0 * 64 * es);
   for (int i = 0; i < 4; ++i)
-    for (int j = 0; j < 3; ++j) w.buf[i][j] = c.take(F * (g.Hs[i] + 2) * (g.Ws[i] + 2) * kVC[i] * es);
+    // stage 1: one tail pixel behind the last frame, zeroed with the halos -- the four-pixel grouped product's window reads it (video_group_width)
+    for (int j = 0; j < 3; ++j) w.buf[i][j] = c.take((F * (g.Hs[i] + 2) * (g.Ws[i] + 2) + (i == 0 ? 1 : 0)) * kVC[i] * es);
   w.pooled = c.take(F * 512 * es);
   if (out) *out = w;
   return c.off;
@@ -173,6 +174,163 @@ int upload_vec_rep(const ParamMap& P, const std::string& key, int C, int G, DevB
   std::vector<float> t;
   for (int j = 0; j < G; ++j) t.insert(t.end(), p->v.begin(), p->v.end());
   return upload_f32(*out, t.data(), t.size());
+}
+
+// ---- the steps of a forward: video_forward_impl and svt_debug_video_step (one step on the caller's buffers) call the same functions ----
+// what every step needs: the finalized handle, the frame count and the stream
+struct VRun {
+  const svt_video* v;
+  long F;
+  hipStream_t s;
+};
+// svt_debug_set key 43: codes of a block's convolutions (include/svt_mi355.h)
+enum { VK_NONE = 0, VK_C64 = 1, VK_C128 = 2, VK_G2 = 3, VK_G4 = 4, VK_PLAIN = 5, VK_COMB = 6 };
+
+// stem alone (the fused stem + pool does not apply): padded operand -> [F][H0][W0][64]
+int video_stem(const VRun& r, const void* vp, int t, const VGeom& g, void* o0) {
+  const svt_video* v = r.v;
+  return launch_conv3d_front(v->prec, vp, v->stem_w.p, v->stem_bias.as<float>(), v->stem_slope.as<float>(), r.F, t, g.Hp0, g.Wp0, g.H0, g.W0, o0,
+                             r.s) ? SVT_ERR_HIP : SVT_OK;
+}
+// stem + max-pool in one kernel -> interior of the zero-haloed stage-1 input
+int video_stem_pool(const VRun& r, const void* vp, int t, const VGeom& g, void* out, int max_workgroups = 0) {
+  const svt_video* v = r.v;
+  return launch_conv3d_front_pool(vp, v->stem_w.p, v->stem_bias.as<float>(), v->stem_slope.as<float>(), r.F, t, g.Hp0, g.Wp0, g.H0, g.W0, g.Hs[0],
+                                  g.Ws[0], out, r.s, max_workgroups) ? SVT_ERR_HIP : SVT_OK;
+}
+// 3x3 / 2 max-pool of the stem's output -> interior of the zero-haloed stage-1 input
+int video_pool(const VRun& r, const void* o0, int H0, int W0, void* out) {
+  return launch_maxpool_3x3s2(r.v->prec, o0, r.F, H0, W0, 64, (H0 - 1) / 2 + 1, (W0 - 1) / 2 + 1, out, r.s) ? SVT_ERR_HIP : SVT_OK;
+}
+// one k x k convolution (k = 3: pad 1; k = 1: no pad) over the zero-haloed channels-last tensor `in`
+int video_conv(const VRun& r, const void* in, int Hin, int Win, int Cin, void* out, int Ho, int Wo, int Cout, int stride, int k, const VConv& cw,
+               const float* slope, const void* resid, long second_out = 0) {
+  const size_t es = esize(r.v->prec);
+  const long F = r.F;
+  GemmArgs a;
+  const long Wpi = Win + 2, Hpi = Hin + 2, Wpo = Wo + 2, Hpo = Ho + 2;
+  a.gen = 1;
+  a.A = (const char*)in + (k == 1 ? (size_t)(Wpi + 1) * Cin * es : 0);
+  a.W = cw.w.p; a.C = out; a.bias = cw.bias.as<float>();
+  a.M = (int)(F * Ho * Wo); a.N = second_out ? 2 * Cout : Cout; a.K = k * k * Cin;
+  a.c_nsplit = second_out ? Cout : 0; a.c_nstride = second_out;   // columns >= Cout: the tensor second_out elements behind `out`
+  a.a_rstride = (long)stride * Cin;
+  a.a_d1 = Wo; a.a_e1 = (long)stride * Wpi * Cin - (long)Wo * stride * Cin;
+  a.a_d2 = Wo * Ho; a.a_e2 = Hpi * Wpi * Cin - (long)Ho * stride * Wpi * Cin;
+  if (k == 3) { a.kseg = 3 * Cin; a.kseg_stride = Wpi * Cin; }
+  a.ldw = (long)k * k * Cin; a.ldc = Cout;
+  a.c_d1 = Wo; a.c_e1 = 2L * Cout;
+  a.c_d2 = Wo * Ho; a.c_e2 = (Hpo * Wpo - (long)Ho * Wpo) * Cout;
+  a.c_base = (Wpo + 1) * Cout;
+  a.act = slope ? ACT_PRELU : ACT_NONE; a.slope = slope;
+  a.resid = (const float*)resid; a.resid_first = 1; a.resid_op_type = 1;
+  return launch_gemm(r.v->gp, a, r.s);
+}
+// stage 1 in the 16-bit modes: G output pixels per GEMM row (see fold_conv_group).  G = 4 computes one pixel past the end of a row of
+// width 4 n + 3 (it lands on the right halo, re-zeroed afterwards, and its window reads one pixel past the row's right halo: the next
+// row's left halo, or, behind the last row of the last frame, the tail pixel video_carve keeps behind every stage-1 buffer); G = 2 needs
+// an even width; otherwise (0) the plain 64-wide product is used.
+int video_group_width(int prec, long F, int Hs, int Ws) {
+  int grp = 0;
+  if (prec) {
+    if (Ws % 2 == 0) grp = 2;                        // measured on 22 x 22 x 64: G = 2 794 us, G = 4 871 us, plain 901 us per conv
+    else if ((Ws + 3) / 4 * 4 - Ws <= 2) grp = 4;
+    if (grp && F * Hs * ((Ws + grp - 1) / grp) < 128) grp = 0;
+  }
+  return grp;
+}
+int video_conv_group(const VRun& r, int grp, const void* in, int Hh, int Ww, void* out, const VConv& cw, const float* slope_rep, const void* resid) {
+  GemmArgs a;
+  const long F = r.F;
+  const long Wp = Ww + 2, Hp = Hh + 2, Wq = (Ww + grp - 1) / grp;
+  a.gen = 1;
+  a.A = in; a.W = cw.w.p; a.C = out; a.bias = cw.bias.as<float>();
+  a.M = (int)(F * Hh * Wq); a.N = grp * 64; a.K = 3 * (grp + 2) * 64;
+  a.a_rstride = (long)grp * 64;
+  a.a_d1 = (int)Wq; a.a_e1 = (Wp - Wq * grp) * 64;
+  a.a_d2 = (int)(Wq * Hh); a.a_e2 = (Hp * Wp - (long)Hh * Wp) * 64;
+  a.kseg = (grp + 2) * 64; a.kseg_stride = Wp * 64;
+  a.ldw = a.K; a.ldc = (long)grp * 64;
+  a.c_d1 = (int)Wq; a.c_e1 = (Wp - Wq * grp) * 64;
+  a.c_d2 = (int)(Wq * Hh); a.c_e2 = (Hp * Wp - (long)Hh * Wp) * 64;
+  a.c_base = (Wp + 1) * 64;
+  a.act = ACT_PRELU; a.slope = slope_rep;
+  a.resid = (const float*)resid; a.resid_first = 1; a.resid_op_type = 1;
+  if (int rc = launch_gemm(r.v->gp, a, r.s)) return rc;
+  if (Wq * grp != Ww) return launch_zero_halo(r.v->prec, out, F, (int)Hp, (int)Wp, 64, r.s);
+  return 0;
+}
+// BasicBlock b of stage li over the zero-haloed block input x (Hin x Win interior; it is also the identity residual and survives).
+// fr: the stage's buffers the block may write -- fr[0] receives conv1, and a block with a downsample (b == 0, li > 0) puts it into fr[1]
+// and its output into fr[2], every other block its output into fr[1].  *xout = the buffer that holds the block's output.
+int video_block(const VRun& r, int li, int b, int Hin, int Win, const void* x, void* const fr[3], void** xout, int max_workgroups = 0) {
+  const svt_video* v = r.v;
+  const int prec = v->prec;
+  const size_t es = esize(prec);
+  const long F = r.F;
+  const int C = kVC[li], stride = (b == 0 && li > 0) ? 2 : 1, cin = stride == 2 ? kVC[li - 1] : C;
+  const int Ho = stride == 2 ? (Hin - 1) / 2 + 1 : Hin, Wo = stride == 2 ? (Win - 1) / 2 + 1 : Win;
+  void* t1 = fr[0];
+  void* outb = fr[1];
+  const void* res = x;
+  int k1 = VK_PLAIN, kd = VK_NONE, k2 = VK_PLAIN;
+  auto done = [&]() { g_vstep_kernel_id = 5000 + 100 * k1 + 10 * kd + k2; *xout = outb; return (int)SVT_OK; };
+  if (li == 0 && v->gp == 1 && conv3x3_c64_ok(prec, Ho, Wo)) {
+    // frame-resident direct convolution (conv3x3_c64.hip): every input pixel fetched once, weights resident in LDS
+    if (launch_conv3x3_c64(x, v->frag1[b].p, v->conv1[0][b].bias.as<float>(), v->conv1[0][b].slope.as<float>(), nullptr, t1, F, Ho, Wo, r.s,
+                           max_workgroups)) return SVT_ERR_HIP;
+    if (launch_conv3x3_c64(t1, v->frag2[b].p, v->conv2[0][b].bias.as<float>(), v->slope2[0][b].as<float>(), x, outb, F, Ho, Wo, r.s,
+                           max_workgroups)) return SVT_ERR_HIP;
+    k1 = k2 = VK_C64;
+    return done();
+  }
+  const int grp = li == 0 ? video_group_width(prec, F, Ho, Wo) : 0;
+  if (grp) {
+    const int gi = grp == 4 ? 1 : 0;
+    if (int rc = video_conv_group(r, grp, x, Ho, Wo, t1, v->grp1[gi][b], v->gslope1[gi][b].as<float>(), nullptr)) return rc;
+    if (int rc = video_conv_group(r, grp, t1, Ho, Wo, outb, v->grp2[gi][b], v->gslope2[gi][b].as<float>(), x)) return rc;
+    k1 = k2 = grp == 4 ? VK_G4 : VK_G2;
+    return done();
+  }
+  const bool direct128 = li == 1 && v->gp == 1 && conv3x3_c128_ok(prec, Ho, Wo);
+  if (direct128 && stride == 1) {
+    if (launch_conv3x3_c128(x, v->frag128[1].p, v->conv1[1][b].bias.as<float>(), v->conv1[1][b].slope.as<float>(), nullptr, t1, F, Ho, Wo, r.s,
+                            max_workgroups)) return SVT_ERR_HIP;
+    k1 = VK_C128;
+  } else if (li == 1 && stride == 2 && v->gp == 1 && g_conv_down_fused && (const char*)fr[1] > (const char*)t1 &&
+             ((const char*)fr[1] - (const char*)t1) % (16 * es) == 0) {
+    // conv1 + downsample as one 256-column product (svt_video_finalize): t1 <- columns 0..127, fr[1] <- columns 128..255
+    if (int rc = video_conv(r, x, Hin, Win, cin, t1, Ho, Wo, C, 2, 3, v->comb2, v->comb2.slope.as<float>(), nullptr,
+                            (long)(((const char*)fr[1] - (const char*)t1) / es))) return rc;
+    res = fr[1];
+    outb = fr[2];
+    k1 = kd = VK_COMB;
+  } else {
+    if (int rc = video_conv(r, x, Hin, Win, cin, t1, Ho, Wo, C, stride, 3, v->conv1[li][b], v->conv1[li][b].slope.as<float>(), nullptr)) return rc;
+    if (stride == 2) {  // first block of stages 2-4: the residual is the 1x1 stride-2 conv + BN of the block input
+      if (int rc = video_conv(r, x, Hin, Win, cin, fr[1], Ho, Wo, C, 2, 1, v->down[li], nullptr, nullptr)) return rc;
+      res = fr[1];
+      outb = fr[2];
+      kd = VK_PLAIN;
+    }
+  }
+  if (direct128) {
+    if (launch_conv3x3_c128(t1, v->frag128[b == 0 ? 0 : 2].p, v->conv2[1][b].bias.as<float>(), v->slope2[1][b].as<float>(), res, outb, F, Ho, Wo,
+                            r.s, max_workgroups)) return SVT_ERR_HIP;
+    k2 = VK_C128;
+  } else if (int rc = video_conv(r, t1, Ho, Wo, C, outb, Ho, Wo, C, 1, 3, v->conv2[li][b], v->slope2[li][b].as<float>(), res)) return rc;
+  return done();
+}
+// mean over the last stage's interior -> [F][512], the projection's operand
+int video_avgpool(const VRun& r, const void* x, int H, int W, void* pooled) {
+  return launch_avgpool_interior(r.v->prec, x, r.F, H, W, 512, pooled, r.s) ? SVT_ERR_HIP : SVT_OK;
+}
+int video_project(const VRun& r, const void* pooled, float* out_dev, int64_t out_ld) {
+  const svt_video* v = r.v;
+  GemmArgs pj;
+  pj.A = pooled; pj.W = v->proj_w.p; pj.C = out_dev; pj.bias = v->proj_b.as<float>();
+  pj.M = (int)r.F; pj.N = v->E; pj.K = 512; pj.a_rpb = (int)r.F; pj.a_rstride = 512; pj.ldw = 512; pj.ldc = out_ld; pj.out_f32 = 1;
+  return launch_gemm(v->gp, pj, r.s) ? SVT_ERR_HIP : SVT_OK;
 }
 }  // namespace
 
@@ -327,7 +485,6 @@ static int video_forward_impl(svt_video* v, const float* video_dev, const unsign
   SVT_HIP(hipSetDevice(v->device));
   hipStream_t s = (hipStream_t)stream;
   const int prec = v->prec;
-  const size_t es = esize(prec);
   const long F = (long)batch * t;
   if (roi_dev && clips) {
     if (launch_video_pad_u8_clips(prec, roi_dev, batch, t, h_in, w_in, h, w, g.Hp0, g.Wp0, *tf, clips, ws.vp, s)) return SVT_ERR_HIP;
@@ -336,9 +493,10 @@ static int video_forward_impl(svt_video* v, const float* video_dev, const unsign
   } else if (launch_video_pad(prec, video_dev, batch, t, h, w, g.Hp0, g.Wp0, ws.vp, s)) return SVT_ERR_HIP;
   if (zero_left > 0)
     if (launch_zero_cols(out_dev - zero_left, F, zero_left, out_ld, s)) return SVT_ERR_HIP;
+  const VRun run{v, F, s};
   const bool fused_stem = v->gp == 1 && conv3d_front_pool_ok(prec, g.Hp0, g.Wp0, g.W0);
-  if (!fused_stem && launch_conv3d_front(prec, ws.vp, v->stem_w.p, v->stem_bias.as<float>(), v->stem_slope.as<float>(), F, t, g.Hp0, g.Wp0,
-                                         g.H0, g.W0, ws.o0, s)) return SVT_ERR_HIP;
+  if (!fused_stem)
+    if (int r = video_stem(run, ws.vp, t, g, ws.o0)) return r;
   // zero halos: the padded stage buffers are written in their interior only (12 launches, 1.3 GB of stores per 16 x 500 frames of
   // 88 x 88: 0.25 ms) -- skipped when the caller keeps the workspace to this object and the halos of this geometry are still there
   const bool halos_there = v->keep_ws && v->halo_ws == workspace_dev && v->halo_stream == stream && v->halo_geom[0] == batch &&
@@ -346,128 +504,28 @@ static int video_forward_impl(svt_video* v, const float* video_dev, const unsign
   if (!halos_there) {
     for (int i = 0; i < 4; ++i)
       for (int j = 0; j < 3; ++j)
-        if (launch_zero_halo(prec, ws.buf[i][j], F, g.Hs[i] + 2, g.Ws[i] + 2, kVC[i], s)) return SVT_ERR_HIP;
+        if (launch_zero_halo(prec, ws.buf[i][j], F, g.Hs[i] + 2, g.Ws[i] + 2, kVC[i], s, i == 0 ? 1 : 0)) return SVT_ERR_HIP;
     v->halo_ws = v->keep_ws ? workspace_dev : nullptr;
     v->halo_stream = stream;
     v->halo_geom[0] = batch; v->halo_geom[1] = t; v->halo_geom[2] = h; v->halo_geom[3] = w;
   }
   if (fused_stem) {
-    if (launch_conv3d_front_pool(ws.vp, v->stem_w.p, v->stem_bias.as<float>(), v->stem_slope.as<float>(), F, t, g.Hp0, g.Wp0, g.H0, g.W0,
-                                 g.Hs[0], g.Ws[0], ws.buf[0][0], s)) return SVT_ERR_HIP;
-  } else if (launch_maxpool_3x3s2(prec, ws.o0, F, g.H0, g.W0, 64, g.Hs[0], g.Ws[0], ws.buf[0][0], s)) return SVT_ERR_HIP;
+    if (int r = video_stem_pool(run, ws.vp, t, g, ws.buf[0][0])) return r;
+  } else if (int r = video_pool(run, ws.o0, g.H0, g.W0, ws.buf[0][0])) return r;
 
-  // one k x k convolution (k = 3: pad 1; k = 1: no pad) over the zero-haloed channels-last tensor `in`
-  auto conv = [&](const void* in, int Hin, int Win, int Cin, void* out, int Ho, int Wo, int Cout, int stride, int k,
-                  const VConv& cw, const float* slope, const void* resid, long second_out = 0) -> int {
-    GemmArgs a;
-    const long Wpi = Win + 2, Hpi = Hin + 2, Wpo = Wo + 2, Hpo = Ho + 2;
-    a.gen = 1;
-    a.A = (const char*)in + (k == 1 ? (size_t)(Wpi + 1) * Cin * es : 0);
-    a.W = cw.w.p; a.C = out; a.bias = cw.bias.as<float>();
-    a.M = (int)(F * Ho * Wo); a.N = second_out ? 2 * Cout : Cout; a.K = k * k * Cin;
-    a.c_nsplit = second_out ? Cout : 0; a.c_nstride = second_out;   // columns >= Cout: the tensor second_out elements behind `out`
-    a.a_rstride = (long)stride * Cin;
-    a.a_d1 = Wo; a.a_e1 = (long)stride * Wpi * Cin - (long)Wo * stride * Cin;
-    a.a_d2 = Wo * Ho; a.a_e2 = Hpi * Wpi * Cin - (long)Ho * stride * Wpi * Cin;
-    if (k == 3) { a.kseg = 3 * Cin; a.kseg_stride = Wpi * Cin; }
-    a.ldw = (long)k * k * Cin; a.ldc = Cout;
-    a.c_d1 = Wo; a.c_e1 = 2L * Cout;
-    a.c_d2 = Wo * Ho; a.c_e2 = (Hpo * Wpo - (long)Ho * Wpo) * Cout;
-    a.c_base = (Wpo + 1) * Cout;
-    a.act = slope ? ACT_PRELU : ACT_NONE; a.slope = slope;
-    a.resid = (const float*)resid; a.resid_first = 1; a.resid_op_type = 1;
-    return launch_gemm(v->gp, a, s);
-  };
-  // stage 1 in bf16 mode: G output pixels per GEMM row (see fold_conv_group).  G = 4 may compute up to two pixels past the
-  // end of a row (they land on the right halo and on the next row's left halo, re-zeroed afterwards); G = 2 needs an even
-  // width; otherwise the plain 64-wide product is used.
-  int grp = 0;
-  if (prec) {
-    const int Wd = g.Ws[0];
-    if (Wd % 2 == 0) grp = 2;                        // measured on 22 x 22 x 64: G = 2 794 us, G = 4 871 us, plain 901 us per conv
-    else if ((Wd + 3) / 4 * 4 - Wd <= 2) grp = 4;
-    if (grp && F * g.Hs[0] * ((Wd + grp - 1) / grp) < 128) grp = 0;
-  }
-  auto conv_group = [&](const void* in, int Hh, int Ww, void* out, const VConv& cw, const float* slope_rep, const void* resid) -> int {
-    GemmArgs a;
-    const long Wp = Ww + 2, Hp = Hh + 2, Wq = (Ww + grp - 1) / grp;
-    a.gen = 1;
-    a.A = in; a.W = cw.w.p; a.C = out; a.bias = cw.bias.as<float>();
-    a.M = (int)(F * Hh * Wq); a.N = grp * 64; a.K = 3 * (grp + 2) * 64;
-    a.a_rstride = (long)grp * 64;
-    a.a_d1 = (int)Wq; a.a_e1 = (Wp - Wq * grp) * 64;
-    a.a_d2 = (int)(Wq * Hh); a.a_e2 = (Hp * Wp - (long)Hh * Wp) * 64;
-    a.kseg = (grp + 2) * 64; a.kseg_stride = Wp * 64;
-    a.ldw = a.K; a.ldc = (long)grp * 64;
-    a.c_d1 = (int)Wq; a.c_e1 = (Wp - Wq * grp) * 64;
-    a.c_d2 = (int)(Wq * Hh); a.c_e2 = (Hp * Wp - (long)Hh * Wp) * 64;
-    a.c_base = (Wp + 1) * 64;
-    a.act = ACT_PRELU; a.slope = slope_rep;
-    a.resid = (const float*)resid; a.resid_first = 1; a.resid_op_type = 1;
-    if (int r = launch_gemm(v->gp, a, s)) return r;
-    if (Wq * grp != Ww) return launch_zero_halo(prec, out, F, (int)Hp, (int)Wp, 64, s);
-    return 0;
-  };
   const void* x = ws.buf[0][0];
-  int Hin = g.Hs[0], Win = g.Ws[0], cin = 64;
-  for (int li = 0; li < 4; ++li) {
-    const int C = kVC[li], Ho = g.Hs[li], Wo = g.Ws[li];
+  for (int li = 0; li < 4; ++li)
     for (int b = 0; b < 2; ++b) {
-      const int stride = (b == 0 && li > 0) ? 2 : 1;
       // the stage's three buffers minus the block input (which is also the identity residual and must survive)
-      void* fr[3]; int nf = 0;
+      void* fr[3] = {nullptr, nullptr, nullptr}; int nf = 0;
       for (int j = 0; j < 3; ++j) if (ws.buf[li][j] != x) fr[nf++] = ws.buf[li][j];
-      void* t1 = fr[0];
-      void* outb = fr[1];
-      const void* res = x;
-      if (li == 0 && v->gp == 1 && conv3x3_c64_ok(prec, Ho, Wo)) {
-        // frame-resident direct convolution (conv3x3_c64.hip): every input pixel fetched once, weights resident in LDS
-        if (launch_conv3x3_c64(x, v->frag1[b].p, v->conv1[0][b].bias.as<float>(), v->conv1[0][b].slope.as<float>(), nullptr, t1, F, Ho, Wo, s))
-          return SVT_ERR_HIP;
-        if (launch_conv3x3_c64(t1, v->frag2[b].p, v->conv2[0][b].bias.as<float>(), v->slope2[0][b].as<float>(), x, outb, F, Ho, Wo, s))
-          return SVT_ERR_HIP;
-        x = outb;
-        continue;
-      }
-      if (li == 0 && grp) {
-        const int gi = grp == 4 ? 1 : 0;
-        if (int r = conv_group(x, Ho, Wo, t1, v->grp1[gi][b], v->gslope1[gi][b].as<float>(), nullptr)) return r;
-        if (int r = conv_group(t1, Ho, Wo, outb, v->grp2[gi][b], v->gslope2[gi][b].as<float>(), x)) return r;
-        x = outb;
-        continue;
-      }
-      const bool direct128 = li == 1 && v->gp == 1 && conv3x3_c128_ok(prec, Ho, Wo);
-      if (direct128 && stride == 1) {
-        if (launch_conv3x3_c128(x, v->frag128[1].p, v->conv1[1][b].bias.as<float>(), v->conv1[1][b].slope.as<float>(), nullptr, t1, F, Ho, Wo, s))
-          return SVT_ERR_HIP;
-      } else if (li == 1 && stride == 2 && v->gp == 1 && g_conv_down_fused && (const char*)fr[1] > (const char*)t1 &&
-                 ((const char*)fr[1] - (const char*)t1) % (16 * es) == 0) {
-        // conv1 + downsample as one 256-column product (svt_video_finalize): t1 <- columns 0..127, fr[1] <- columns 128..255
-        if (int r = conv(x, Hin, Win, cin, t1, Ho, Wo, C, 2, 3, v->comb2, v->comb2.slope.as<float>(), nullptr,
-                         (long)(((const char*)fr[1] - (const char*)t1) / es))) return r;
-        res = fr[1];
-        outb = fr[2];
-      } else {
-        if (int r = conv(x, Hin, Win, cin, t1, Ho, Wo, C, stride, 3, v->conv1[li][b], v->conv1[li][b].slope.as<float>(), nullptr)) return r;
-        if (stride == 2) {  // first block of stages 2-4: the residual is the 1x1 stride-2 conv + BN of the block input
-          if (int r = conv(x, Hin, Win, cin, fr[1], Ho, Wo, C, 2, 1, v->down[li], nullptr, nullptr)) return r;
-          res = fr[1];
-          outb = fr[2];
-        }
-      }
-      if (direct128) {
-        if (launch_conv3x3_c128(t1, v->frag128[b == 0 ? 0 : 2].p, v->conv2[1][b].bias.as<float>(), v->slope2[1][b].as<float>(), res, outb, F, Ho, Wo, s))
-          return SVT_ERR_HIP;
-      } else if (int r = conv(t1, Ho, Wo, C, outb, Ho, Wo, C, 1, 3, v->conv2[li][b], v->slope2[li][b].as<float>(), res)) return r;
-      x = outb; Hin = Ho; Win = Wo; cin = C;
+      const int pl = (b == 0 && li > 0) ? li - 1 : li;   // the stage whose geometry the block input has
+      void* xo = nullptr;
+      if (int r = video_block(run, li, b, g.Hs[pl], g.Ws[pl], x, fr, &xo)) return r;
+      x = xo;
     }
-  }
-  if (launch_avgpool_interior(prec, x, F, g.Hs[3], g.Ws[3], 512, ws.pooled, s)) return SVT_ERR_HIP;
-  GemmArgs pj;
-  pj.A = ws.pooled; pj.W = v->proj_w.p; pj.C = out_dev; pj.bias = v->proj_b.as<float>();
-  pj.M = (int)F; pj.N = v->E; pj.K = 512; pj.a_rpb = (int)F; pj.a_rstride = 512; pj.ldw = 512; pj.ldc = out_ld; pj.out_f32 = 1;
-  if (launch_gemm(v->gp, pj, s)) return SVT_ERR_HIP;
-  return SVT_OK;
+  if (int r = video_avgpool(run, x, g.Hs[3], g.Ws[3], ws.pooled)) return r;
+  return video_project(run, ws.pooled, out_dev, out_ld);
 }
 
 int svt_video_forward(svt_video* v, const float* video_dev, int32_t batch, int32_t t, int32_t h, int32_t w, float* out_dev,
@@ -518,6 +576,70 @@ int svt_video_forward_u8_clips(svt_video* v, const uint8_t* roi_dev, int32_t bat
   const VideoTransform vt{tf->sub0, tf->div0, tf->mean, tf->std};
   return video_forward_impl(v, nullptr, roi_dev, h_in, w_in, 0, 0, &vt, reinterpret_cast<const VideoClip*>(clips_host), batch, t, tf->crop_h,
                             tf->crop_w, out_dev, out_ld, zero_left, workspace_dev, workspace_bytes, stream);
+}
+
+// One step of a finalized front-end on the caller's device buffers (include/svt_mi355.h documents the steps, buffers and refusals)
+int svt_debug_video_step(svt_video* v, const svt_debug_video_desc* d, void* stream) {
+  auto refuse = [](const char* why) { set_error(std::string("svt_debug_video_step: ") + why); return (int)SVT_ERR_INVALID; };
+  auto aligned = [](auto... p) { return !((... | (uintptr_t)p) & 15); };   // a null pointer passes
+  if (!d || d->struct_size != (int32_t)sizeof(svt_debug_video_desc)) return refuse("struct_size");
+  if (!v) return refuse("null handle");
+  if (!v->finalized) return refuse("call svt_video_finalize first");
+  const int step = d->step;
+  if (step < 1 || step > 6) return refuse("step is 1 .. 6");
+  if (d->workgroups < 0) return refuse("workgroups must not be negative");
+  if (!aligned(d->x, d->t1, d->ds, d->out)) return refuse("every buffer 16-byte aligned");
+  if (!d->out || (step != 4 && !d->x)) return refuse("null buffer");
+  const int prec = v->prec;
+  const size_t es = esize(prec);
+  VGeom g{};
+  long F = d->F;
+  if (step == 1 || step == 3) {
+    if (d->B < 1 || d->T < 1 || d->h < 8 || d->w < 8) return refuse("B, T >= 1 and h, w >= 8");
+    g = video_geom(d->h, d->w);
+    F = (long)d->B * d->T;
+    if ((double)F * g.Hp0 * g.Wp0 > 2.0e9) return refuse("too many frames for one call");
+    if (step == 1 && prec && (size_t)5 * g.Hp0 * g.Wp0 * 2 > 160 * 1024) return refuse("the stem's five planes do not fit the LDS");
+    if (step == 3 && !(v->gp == 1 && conv3d_front_pool_ok(prec, g.Hp0, g.Wp0, g.W0)))
+      return refuse("the forward does not run the fused stem + pool at this geometry (conv3d_front_pool_ok; svt_debug_set key 26)");
+  } else {
+    if (F < 1 || d->H < 1 || d->W < 1) return refuse("F, H and W must be positive");
+    if ((double)F * (d->H + 2) * (d->W + 2) > 2.0e9) return refuse("too many frames for one call");
+  }
+  if (step == 4 && (d->H < 3 || d->W < 3 || (d->C != 64 && d->C != 128 && d->C != 256 && d->C != 512)))
+    return refuse("zero-halo: Hp, Wp >= 3 and C one of 64, 128, 256, 512");
+  if (step == 5) {
+    if (d->li < 0 || d->li > 3 || d->b < 0 || d->b > 1) return refuse("li is 0 .. 3 and b is 0 or 1");
+    if (!d->t1 || (d->li > 0 && d->b == 0 && !d->ds)) return refuse("null buffer");
+  }
+  SVT_HIP(hipSetDevice(v->device));
+  hipStream_t s = (hipStream_t)stream;
+  const VRun run{v, F, s};
+  void* vp = nullptr;
+  int rc = SVT_OK;
+  if (step == 1 || step == 3) {
+    // the padded operand is the hook's own: 0xFF bytes first, so padding that the pad kernel does not write is NaN to the stem
+    const size_t bytes = (size_t)d->B * (d->T + 4) * g.Hp0 * g.Wp0 * es;
+    rc = dev_alloc(&vp, bytes);
+    if (!rc && hipMemsetAsync(vp, 0xFF, bytes, s) != hipSuccess) { set_error("svt_debug_video_step: hipMemsetAsync"); rc = SVT_ERR_HIP; }
+    if (!rc && launch_video_pad(prec, (const float*)d->x, d->B, d->T, d->h, d->w, g.Hp0, g.Wp0, vp, s)) rc = SVT_ERR_HIP;
+    if (!rc) rc = step == 1 ? video_stem(run, vp, d->T, g, d->out) : video_stem_pool(run, vp, d->T, g, d->out, d->workgroups);
+  } else if (step == 2) {
+    rc = video_pool(run, d->x, d->H, d->W, d->out);
+  } else if (step == 4) {
+    rc = launch_zero_halo(prec, d->out, F, d->H, d->W, d->C, s) ? SVT_ERR_HIP : SVT_OK;
+  } else if (step == 5) {
+    const bool has_ds = d->li > 0 && d->b == 0;
+    void* const fr[3] = {d->t1, has_ds ? d->ds : d->out, has_ds ? d->out : nullptr};
+    void* xo = nullptr;
+    rc = video_block(run, d->li, d->b, d->H, d->W, d->x, fr, &xo, d->workgroups);
+  } else {
+    rc = video_avgpool(run, d->x, d->H, d->W, d->out);
+  }
+  if (rc && rc != SVT_ERR_HIP) rc = SVT_ERR_INVALID;   // a launcher's own refusal
+  if (hipStreamSynchronize(s) != hipSuccess && !rc) { set_error("svt_debug_video_step: hipStreamSynchronize"); rc = SVT_ERR_HIP; }
+  if (vp) dev_free(vp);
+  return rc;
 }
 
 }  // extern "C"

@@ -557,6 +557,7 @@ struct VideoClip { int dy, dx, flip, n_frames; };
 constexpr int kVideoClipsPerLaunch = 64;
 int launch_video_pad_u8_clips(int prec, const unsigned char* v, int B, int T, int Hin, int Win, int H, int W, int Hp, int Wp,
                               const VideoTransform& tf, const VideoClip* clips, void* out, hipStream_t s);
+extern int g_vstep_kernel_id;  // key 43 (query): which kernels the last step of the lip front-end launched (video.hip, api_video.hip; include/svt_mi355.h lists the ids)
 extern int g_vpad_kernel_id;   // key 42 (query): which padding kernel the last lip front-end call launched (video.hip; include/svt_mi355.h lists the ids)
 int launch_conv3d_front(int prec, const void* vp, const void* w, const float* bias, const float* slope, long F, int T, int Hp,
                         int Wp, int H0, int W0, void* out, hipStream_t s);
@@ -565,17 +566,17 @@ int launch_maxpool_3x3s2(int prec, const void* in, long F, int H0, int W0, int C
 extern int g_stem_pool_fused;
 bool conv3d_front_pool_ok(int prec, int Hp, int Wp, int W0);
 int launch_conv3d_front_pool(const void* vp, const void* w, const float* bias, const float* slope, long F, int T, int Hp, int Wp, int H0,
-                             int W0, int H1, int W1, void* out, hipStream_t s);
-int launch_zero_halo(int prec, void* buf, long F, int Hp, int Wp, int C, hipStream_t s);
+                             int W0, int H1, int W1, void* out, hipStream_t s, int max_workgroups = 0);   // max_workgroups > 0 caps the persistent grid
+int launch_zero_halo(int prec, void* buf, long F, int Hp, int Wp, int C, hipStream_t s, int tail_pixels = 0);
 int launch_avgpool_interior(int prec, const void* in, long F, int H, int W, int C, void* out, hipStream_t s);
 // conv3x3_c64.hip: stage 1 of the lip front-end (64 -> 64 channels, 3x3) with the frame and the weights resident in LDS
 extern int g_conv3x3_c64, g_conv3x3_c64_launches, g_conv3x3_c64_form;
 bool conv3x3_c64_ok(int prec, int Hs, int Ws);
 int launch_conv3x3_c64(const void* in, const void* wimg, const float* bias, const float* slope, const void* resid, void* out, long F,
-                       int Hs, int Ws, hipStream_t s);
+                       int Hs, int Ws, hipStream_t s, int max_workgroups = 0);   // max_workgroups > 0 caps the persistent grid
 bool conv3x3_c128_ok(int prec, int Hs, int Ws);   // stage 2's stride-1 convolutions (128 -> 128 channels), same file
 int launch_conv3x3_c128(const void* in, const void* wimg, const float* bias, const float* slope, const void* resid, void* out, long F,
-                        int Hs, int Ws, hipStream_t s);
+                        int Hs, int Ws, hipStream_t s, int max_workgroups = 0);
 // head-only training step (train.hip): the recipe's objective + d/dlogits, the head's weight gradient, clip_grad_norm_ + Adadelta
 int launch_amt_objective_grad(const float* x, int64_t B, int64_t t_pred, int n_out, int n_oct_cols, const float* on_t,
                               const float* off_t, const int64_t* oct_t, const int64_t* cls_t, int64_t t_tgt, int64_t T,

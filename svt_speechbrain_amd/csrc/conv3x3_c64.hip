@@ -308,7 +308,7 @@ bool conv3x3_c64_ok(int prec, int Hs, int Ws) {
 // in / out / resid: [F][Hs+2][Ws+2][64] 16-bit, halos zero (out: written in its interior only); wimg: svt_video_finalize's fragment
 // image of the 3x3 kernel with the BatchNorm scale folded; bias / slope: 64 floats
 int launch_conv3x3_c64(const void* in, const void* wimg, const float* bias, const float* slope, const void* resid, void* out, long F,
-                       int Hs, int Ws, hipStream_t s) {
+                       int Hs, int Ws, hipStream_t s, int max_workgroups) {
   const size_t shm = c3_lds_bytes(Hs, Ws);
   static int ncu = 0;
   if (!ncu) {
@@ -317,7 +317,8 @@ int launch_conv3x3_c64(const void* in, const void* wimg, const float* bias, cons
     if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&pr, dev) != hipSuccess) return 1;
     ncu = pr.multiProcessorCount;
   }
-  const int grid = (int)(F < ncu ? F : ncu);
+  const int nwg = max_workgroups > 0 && max_workgroups < ncu ? max_workgroups : ncu;   // the persistent grid's cap (tests: several frames per workgroup)
+  const int grid = (int)(F < nwg ? F : nwg);
   ++g_conv3x3_c64_launches;
   auto go = [&](auto kern) -> int {
     if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm) != hipSuccess) return 1;
@@ -342,7 +343,7 @@ bool conv3x3_c128_ok(int prec, int Hs, int Ws) {
 }
 // in / out / resid: [F][Hs+2][Ws+2][128] 16-bit, halos zero; wimg: fold_conv_frag128's image; bias / slope: 128 floats
 int launch_conv3x3_c128(const void* in, const void* wimg, const float* bias, const float* slope, const void* resid, void* out, long F,
-                        int Hs, int Ws, hipStream_t s) {
+                        int Hs, int Ws, hipStream_t s, int max_workgroups) {
   const size_t shm = c128_lds_bytes(Hs, Ws);
   const unsigned fbytes = (unsigned)c128_ring_slots(Hs, Ws) * 256u;
   static int ncu = 0;
@@ -352,7 +353,8 @@ int launch_conv3x3_c128(const void* in, const void* wimg, const float* bias, con
     if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&pr, dev) != hipSuccess) return 1;
     ncu = pr.multiProcessorCount;
   }
-  const int grid = (int)(F < ncu ? F : ncu);
+  const int nwg = max_workgroups > 0 && max_workgroups < ncu ? max_workgroups : ncu;   // the persistent grid's cap (tests: several frames per workgroup)
+  const int grid = (int)(F < nwg ? F : nwg);
   ++g_conv3x3_c64_launches;
   auto go = [&](auto kern) -> int {
     if (ensure_dyn_lds((const void*)kern, (int)shm)) return 1;

@@ -501,11 +501,13 @@ __global__ void maxpool_3x3s2_bf16x8_kernel(const bf16_t* in, long F, int H0, in
   }
 }
 
-// zero the one-pixel halo of [F][Hp][Wp][C] (16-byte stores; C * sizeof(T) is a multiple of 16)
-__global__ void zero_halo_kernel(uint4* buf, long F, int Hp, int Wp, int c16) {
+// zero the one-pixel halo of [F][Hp][Wp][C] (16-byte stores; C * sizeof(T) is a multiple of 16) and the tail16 16-byte pieces behind the
+// last frame (the tail pixel of a stage-1 workspace buffer)
+__global__ void zero_halo_kernel(uint4* buf, long F, int Hp, int Wp, int c16, int tail16) {
   const int nh = 2 * Wp + 2 * (Hp - 2);
   const long n = F * nh * c16;
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n + tail16; i += (long)gridDim.x * blockDim.x) {
+    if (i >= n) { buf[F * Hp * Wp * c16 + (i - n)] = uint4{0, 0, 0, 0}; continue; }
     const int c = (int)(i % c16);
     long r = i / c16;
     const int hidx = (int)(r % nh);
@@ -544,6 +546,9 @@ unsigned grid_of(long n) {
 // 3 = video_pad*_u8_clips_kernel (uint8 ROI, per-clip crop / flip / length); form 0 = generic fp32, 1 = generic 16-bit, 2 = 8 pixels
 // per 16-byte store (16-bit)
 int g_vpad_kernel_id = 0;
+// svt_debug_set key 43 (query): which kernels the last step of the lip front-end launched (include/svt_mi355.h lists the ids), set on the
+// host by every branch of the launchers below and, for a BasicBlock, by video_block (api_video.hip)
+int g_vstep_kernel_id = 0;
 
 int launch_video_pad(int prec, const float* v, int B, int T, int H, int W, int Hp, int Wp, void* out, hipStream_t s) {
   const long n = (long)B * (T + 4) * Hp * Wp;
@@ -612,12 +617,14 @@ int launch_conv3d_front(int prec, const void* vp, const void* w, const float* bi
     const size_t lds_bytes = (size_t)5 * Hp * Wp * 2;
     if (lds_bytes > 160 * 1024) { set_error("video front-end: the lip ROI is too large for the LDS-resident stem (5 frames must fit 160 KB)"); return -1; }
     if (int r_ = ensure_dyn_lds((const void*)conv3d_front_bf16_kernel, (int)lds_bytes)) return r_;
+    g_vstep_kernel_id = 101;
     prof_begin(s);
     hipLaunchKernelGGL(conv3d_front_bf16_kernel, dim3((unsigned)F), dim3(512), lds_bytes, s, (const bf16_t*)vp, (const uint4*)w, bias,
                        slope, T, Hp, Wp, H0, W0, (bf16_t*)out);
     prof_end(s, 2.0 * F * H0 * W0 * 64.0 * 245.0, 0.0, 1);
   } else {
     const long npix = F * H0 * W0;
+    g_vstep_kernel_id = 100;
     hipLaunchKernelGGL(conv3d_front_f32_kernel, dim3((unsigned)((npix + 3) / 4)), dim3(256), 0, s, (const float*)vp, (const float*)w,
                        bias, slope, T, Hp, Wp, H0, W0, npix, (float*)out);
   }
@@ -633,7 +640,7 @@ bool conv3d_front_pool_ok(int prec, int Hp, int Wp, int W0) {
 }
 // stem + 3x3/2 max-pool -> interior of the zero-haloed [F][H1+2][W1+2][64] (16-bit storage modes)
 int launch_conv3d_front_pool(const void* vp, const void* w, const float* bias, const float* slope, long F, int T, int Hp, int Wp, int H0,
-                             int W0, int H1, int W1, void* out, hipStream_t s) {
+                             int W0, int H1, int W1, void* out, hipStream_t s, int max_workgroups) {
   const size_t lds_bytes = stem_pool_lds(Hp, Wp, W0);
   if (int r_ = ensure_dyn_lds((const void*)conv3d_front_pool_kernel, (int)lds_bytes)) return r_;
   static int ncu = 0;
@@ -644,8 +651,10 @@ int launch_conv3d_front_pool(const void* vp, const void* w, const float* bias, c
     SVT_HIP(hipGetDeviceProperties(&pr, dev));
     ncu = pr.multiProcessorCount;
   }
-  const int fpb = (int)((F + ncu - 1) / ncu);
+  const int nwg = max_workgroups > 0 && max_workgroups < ncu ? max_workgroups : ncu;   // the persistent grid's cap (tests: runs of several frames)
+  const int fpb = (int)((F + nwg - 1) / nwg);
   const unsigned grid = (unsigned)((F + fpb - 1) / fpb);
+  g_vstep_kernel_id = 300;
   prof_begin(s);
   hipLaunchKernelGGL(conv3d_front_pool_kernel, dim3(grid), dim3(512), lds_bytes, s, (const bf16_t*)vp, (const uint4*)w, bias, slope, T, Hp,
                      Wp, H0, W0, H1, W1, F, fpb, (bf16_t*)out, g_stem_pool_fused >> 4);
@@ -656,6 +665,7 @@ int launch_conv3d_front_pool(const void* vp, const void* w, const float* bias, c
 
 int launch_maxpool_3x3s2(int prec, const void* in, long F, int H0, int W0, int C, int H1, int W1, void* out, hipStream_t s) {
   const long n = F * H1 * W1 * C;
+  g_vstep_kernel_id = prec && C % 8 == 0 ? 202 : (prec ? 201 : 200);
   if (prec && C % 8 == 0) hipLaunchKernelGGL(maxpool_3x3s2_bf16x8_kernel, dim3(grid_of(n / 8)), dim3(256), 0, s, (const bf16_t*)in, F, H0, W0, C, H1, W1, (bf16_t*)out);
   else if (prec) hipLaunchKernelGGL(maxpool_3x3s2_kernel<bf16_t>, dim3(grid_of(n)), dim3(256), 0, s, (const bf16_t*)in, F, H0, W0, C, H1, W1, (bf16_t*)out);
   else hipLaunchKernelGGL(maxpool_3x3s2_kernel<float>, dim3(grid_of(n)), dim3(256), 0, s, (const float*)in, F, H0, W0, C, H1, W1, (float*)out);
@@ -663,16 +673,19 @@ int launch_maxpool_3x3s2(int prec, const void* in, long F, int H0, int W0, int C
   return 0;
 }
 
-int launch_zero_halo(int prec, void* buf, long F, int Hp, int Wp, int C, hipStream_t s) {
+// tail_pixels: pixels behind the last frame zeroed as well (the caller's buffer holds them: video_carve, stage 1)
+int launch_zero_halo(int prec, void* buf, long F, int Hp, int Wp, int C, hipStream_t s, int tail_pixels) {
   const int c16 = C * (prec ? 2 : 4) / 16;
-  const long n = F * (2 * Wp + 2 * (Hp - 2)) * c16;
-  hipLaunchKernelGGL(zero_halo_kernel, dim3(grid_of(n)), dim3(256), 0, s, (uint4*)buf, F, Hp, Wp, c16);
+  const long n = F * (2 * Wp + 2 * (Hp - 2)) * c16 + (long)tail_pixels * c16;
+  g_vstep_kernel_id = 400;
+  hipLaunchKernelGGL(zero_halo_kernel, dim3(grid_of(n)), dim3(256), 0, s, (uint4*)buf, F, Hp, Wp, c16, tail_pixels * c16);
   SVT_LAUNCH_CHECK();
   return 0;
 }
 
 int launch_avgpool_interior(int prec, const void* in, long F, int H, int W, int C, void* out, hipStream_t s) {
   const long n = F * C;
+  g_vstep_kernel_id = prec ? 601 : 600;
   if (prec) hipLaunchKernelGGL(avgpool_interior_kernel<bf16_t>, dim3(grid_of(n)), dim3(256), 0, s, (const bf16_t*)in, F, H, W, C, (bf16_t*)out);
   else hipLaunchKernelGGL(avgpool_interior_kernel<float>, dim3(grid_of(n)), dim3(256), 0, s, (const float*)in, F, H, W, C, (float*)out);
   SVT_LAUNCH_CHECK();
