@@ -135,6 +135,45 @@ int svt_encoder_set_norm_reduce(svt_encoder* enc, svt_norm_reduce_fn fn, void* u
  * SVT_ERR_KEY: a time mask on an encoder that never received "masked_spec_embed" (shape (hidden_size,)). */
 int svt_encoder_set_spec_augment(svt_encoder* enc, const uint8_t* time_mask_dev, const uint8_t* feature_mask_dev, int32_t batch,
                                  int32_t frames);
+/* Training-mode dropouts and layerdrop inside the encoder (HF modeling_wav2vec2.py: the model in train() mode; the wrapper's
+ * freeze=False).  While a state is set, every forward of this encoder (svt_encoder_forward, _ex and _forward_head) skips the layers of
+ * skip_mask and applies the element dropouts whose rate is above 0.  The mask of an element is a function of its POSITION:
+ *     word = Philox4x32-10(key = (seed_lo, seed_hi), counter = (q_lo, q_hi, site | layer << 8, step))[e & 3],   q = e >> 2
+ *     e is kept iff word >= floor(p * 2^32); a kept value is multiplied by float(1 / (1 - p)), a dropped one becomes +0
+ * with e the element's LOGICAL index -- (b*T + t)*W + c in a (B, T, W) tensor, ((b*H + h)*T + i)*T + j in the attention
+ * probabilities -- never a padded or tiled one, seed_lo / seed_hi the halves of `seed`, and the sites
+ *     0  output of the feature projection (feat_proj_dropout), in front of SpecAugment
+ *     1  the encoder's own dropout (hidden_dropout): behind the positional conv and the first LayerNorm (post-LN), or behind the
+ *        positional conv alone, in front of the layers (stable_layer_norm)
+ *     2  attention probabilities (attention_dropout): softmax -> dropout -> P V, as HF's eager attention
+ *     3  the attention branch behind the out-projection (hidden_dropout)
+ *     4  behind FFN-1's GELU (activation_dropout)
+ *     5  behind FFN-2 (hidden_dropout)
+ * (sites 0 and 1: layer = 0).  No parity with the masks torch's device generator would draw is claimed: those depend on torch's launch
+ * geometry.  Where the residual stream is stored twice (an fp32 copy beside the operand copy) both copies receive the same mask; the
+ * bf16 (hi, lo) stream has its value float(hi) + float(lo) scaled or zeroed and is cut again (hi' = T(o), lo' = T(o - hi')).
+ * With attention_dropout > 0 the attention takes the score-matrix path for every geometry (the fused kernels have no mask), whose
+ * score and probability buffers svt_encoder_workspace_bytes counts ONLY while such a state is set: set the state BEFORE the size query.
+ * With hidden_dropout > 0 FFN-2 takes its un-split form.  skip_mask: bit l set = layer l is skipped and launches nothing (HF's
+ * layerdrop; the caller draws -- torch.rand([]) < layerdrop per layer, in layer order); `layerdrop` itself is only recorded.
+ * The state is sticky on the handle; NULL clears it, and the forward is then the plain one: no launch added, no kernel changed.
+ * SVT_ERR_INVALID: a rate outside [0, 1), a bit of skip_mask at or above num_layers, more than 64 layers with a skip, an element
+ * rate above 0 in a split-operand precision (SVT_PREC_BF16X3 / SVT_PREC_FP16X3 serve layerdrop only: their activations travel as
+ * pair rows, which these kernels do not read), attention_dropout > 0 with a relative position bias (WavLM: the reference runs torch's
+ * fused multi-head attention there, which offers no seam to pin a mask against), layer 0 of such an encoder skipped while a later layer runs (the
+ * reference cannot: only layer 0 holds the position embedding). */
+typedef struct svt_dropout {
+  int32_t struct_size;
+  uint32_t step;
+  double feat_proj_dropout;
+  double hidden_dropout;
+  double attention_dropout;
+  double activation_dropout;
+  double layerdrop;
+  uint64_t seed;
+  uint64_t skip_mask;
+} svt_dropout;
+int svt_encoder_set_dropout(svt_encoder* enc, const svt_dropout* state);
 /* copy one parameter by its HF state-dict key (without the wrapper's "model." prefix); both weight-norm
  * spellings of the positional conv are accepted (…conv.weight_g/_v and …parametrizations.weight.original0/1).
  * "masked_spec_embed" (hidden_size) is optional: kept in fp32 for svt_encoder_set_spec_augment.
@@ -147,6 +186,7 @@ int svt_encoder_finalize(svt_encoder* e);
 /* read a (possibly folded) parameter back as fp32 by HF key — for state_dict() round trips */
 int svt_encoder_get_param(svt_encoder* e, const char* key, void* out_host, int64_t capacity_elems);
 int64_t svt_encoder_num_frames(const svt_encoder* e, int64_t n_samples);
+/* (the size follows the dropout state of the handle: svt_encoder_set_dropout, which must be called before this query) */
 int64_t svt_encoder_workspace_bytes(const svt_encoder* e, int32_t batch, int64_t n_samples);
 /* replaces: HuggingFaceWav2Vec2.extract_features (:279-297): wav f32 (B,L) -> feats f32 (B,T,D) */
 int svt_encoder_forward(svt_encoder* e, const float* wav_dev, int32_t batch, int64_t n_samples,
@@ -509,6 +549,36 @@ typedef struct svt_debug_layernorm_desc {
 } svt_debug_layernorm_desc;
 int svt_debug_layernorm(const svt_debug_layernorm_desc* d, int device, void* stream);
 
+/* ---- test hook: ONE launch of a dropout kernel (csrc/dropout.hip) on caller-supplied device buffers; tests/test_gpu_dropout_kernels.py ----
+ * form 0: launch_dropout_rows, in place on x -- n elements of fp32 (prec 0) or of the build's 16-bit operand type (prec 1);
+ * form 1: launch_dropout_hilo, in place on the 16-bit pair (xh, xl) of n elements each;
+ * form 2: launch_softmax_dropout, S (rows, Tp) fp32 -> P (rows, Tp) fp32 (prec 0) or 16-bit (prec 1), T real columns (n is ignored).
+ * The mask is svt_dropout's: rate p in [0, 1), seed, step, site, layer; element i of forms 0 / 1 has the logical index e0 + i, column j
+ * of row r of form 2 the index e0 + r*T + j -- e0 lets a small tensor reach q_hi != 0 and every alignment of the four-word groups.
+ * Pointers: element-aligned; 16-byte accesses are used when e0 % 4 == 0 and the pointers are 16-byte aligned, as in the encoder.
+ * svt_debug_set(44, 0) says which kernel ran.  struct_size = the size of the structure. */
+typedef struct svt_debug_dropout_desc {
+  int32_t struct_size;
+  int32_t form;
+  int32_t prec;
+  int32_t site;
+  int32_t layer;
+  uint32_t step;
+  double p;
+  uint64_t seed;
+  uint64_t e0;
+  int64_t n;
+  int64_t rows;
+  int32_t T;
+  int32_t Tp;
+  void* x;
+  void* xh;
+  void* xl;
+  const float* S;
+  void* P;
+} svt_debug_dropout_desc;
+int svt_debug_dropout(const svt_debug_dropout_desc* d, int device, void* stream);
+
 /* ---- test hook: one launch of ONE launcher of the waveform front end (csrc/stats.hip, csrc/conv0.hip, csrc/conv0_mfma.hip) on
  * caller-supplied device buffers; tests/test_gpu_conv0.py ----
  * The descriptor holds the union of the seven launchers' arguments; `form` says which one runs (fields of another form are ignored):
@@ -776,8 +846,11 @@ int svt_debug_rca_attn_bwd(int32_t precision, const void* qkv, const void* qc, c
  * 0 = none (downsample of a block that has none), 1 = conv3x3_c64_kernel, 2 = conv3x3_c128_kernel, 3 = grouped product G = 2,
  * 4 = grouped product G = 4, 5 = plain product, 6 = the combined conv1 + downsample product (conv1 and downsample both 6); for the
  * product launches key 39 names the GEMM kernel of the block's last product (tests/test_gpu_video_kernels.py asserts the id of every
- * case).
- * Returns 0 (keys 24, 31: the count; keys 38, 39, 40, 41, 42, 43: the id), SVT_ERR_INVALID for an unknown key or a value a key does not accept (21, 28, 30, 37 above). */
+ * case), 44 = query: returns which dropout kernel the last launch of csrc/dropout.hip in this process chose (value ignored; 0 = none
+ * yet): 1 = dropout_rows_kernel<float>, 2 = dropout_rows_kernel<16-bit>, 3 = dropout_hilo_kernel, each + 10 for its element-by-element
+ * instantiation (e0 % 4 != 0 or a pointer that is not 16-byte aligned); 4 = softmax_dropout_kernel<float>, 5 = <16-bit>
+ * (tests/test_gpu_dropout_kernels.py asserts the id of every case).
+ * Returns 0 (keys 24, 31: the count; keys 38, 39, 40, 41, 42, 43, 44: the id), SVT_ERR_INVALID for an unknown key or a value a key does not accept (21, 28, 30, 37 above). */
 int svt_debug_set(int key, int value);
 
 /* ---- test hook: ONE step of a finalized lip front-end on caller-supplied device buffers; tests/test_gpu_video_kernels.py ----

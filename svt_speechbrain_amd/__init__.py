@@ -25,6 +25,8 @@ from . import augment  # noqa: F401
 from .augment import notch_filter, drop_filter, DropFreq, DropChunk, TimeDomainSpecAugment  # noqa: F401
 from . import spec_augment  # noqa: F401
 from .spec_augment import compute_mask_indices  # noqa: F401
+from . import dropout  # noqa: F401
+from .dropout import draw_layerdrop  # noqa: F401
 from . import audio_io  # noqa: F401
 from .audio_io import info, load, save, read_audio, write_audio  # noqa: F401
 from .dataio import read_utterance  # noqa: F401

@@ -41,11 +41,12 @@ class ReplicaAware:
 
 class DeviceSlot:
     """One C object on one device: its handle, what was uploaded into it, and its workspace."""
-    __slots__ = ("key", "handle", "sig", "gen", "ws", "masks")
+    __slots__ = ("key", "handle", "sig", "gen", "ws", "masks", "dropout")
 
     def __init__(self, key):
         self.key = key
         self.handle = None
+        self.dropout = False  # encoder: svt_encoder_set_dropout holds a state on this handle
         self.masks = None  # encoder: the device tensors svt_encoder_set_spec_augment currently points at (kept alive here), or None
         self.sig = None   # signature of the uploaded parameters (tuple of (data_ptr, version)), or None
         self.gen = -1     # generation of the owner's parameters at upload time
@@ -84,6 +85,7 @@ class DeviceObjects:
             s.handle = None
         s.ws = None
         s.masks = None
+        s.dropout = False
 
     def close(self) -> None:
         for s in list(self._slots.values()):

@@ -94,6 +94,26 @@ class LayerNormDescC(C.Structure):
     ]
 
 
+class DropoutC(C.Structure):
+    """svt_dropout: the training-mode state of svt_encoder_set_dropout -- five rates, (seed, step) of the mask function, skipped layers."""
+    _fields_ = [
+        ("struct_size", C.c_int32), ("step", C.c_uint32),
+        ("feat_proj_dropout", C.c_double), ("hidden_dropout", C.c_double), ("attention_dropout", C.c_double),
+        ("activation_dropout", C.c_double), ("layerdrop", C.c_double),
+        ("seed", C.c_uint64), ("skip_mask", C.c_uint64),
+    ]
+
+
+class DropoutDescC(C.Structure):
+    """svt_debug_dropout_desc: one launch of a dropout kernel (svt_debug_dropout); form 0 / 1 / 2, device pointers."""
+    _fields_ = [
+        ("struct_size", C.c_int32), ("form", C.c_int32), ("prec", C.c_int32), ("site", C.c_int32), ("layer", C.c_int32), ("step", C.c_uint32),
+        ("p", C.c_double), ("seed", C.c_uint64), ("e0", C.c_uint64), ("n", C.c_int64), ("rows", C.c_int64),
+        ("T", C.c_int32), ("Tp", C.c_int32),
+        ("x", C.c_void_p), ("xh", C.c_void_p), ("xl", C.c_void_p), ("S", C.c_void_p), ("P", C.c_void_p),
+    ]
+
+
 class Conv0DescC(C.Structure):
     """svt_debug_conv0_desc: one launch of a launcher of the waveform front end (svt_debug_conv0); form 0 .. 6, device pointers
     (tickets_out: a host pointer)."""
@@ -186,6 +206,8 @@ SYMBOLS = {
     "svt_drop_freq_chunk": (C.c_int, [_P, C.c_int32, C.c_int64, C.c_int64, _P, C.c_int32, _P, C.c_int32, _P, C.c_int64, C.c_int, _P]),
     "svt_spec_augment": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int64, _P, _P, _P, C.c_int, _P]),
     "svt_encoder_set_spec_augment": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32]),
+    "svt_encoder_set_dropout": (C.c_int, [_P, C.POINTER(DropoutC)]),
+    "svt_debug_dropout": (C.c_int, [C.POINTER(DropoutDescC), C.c_int, _P]),
     "svt_wav_parse": (C.c_int, [_P, C.c_int64, C.c_int64, C.POINTER(WavInfoC), _I64P]),
     "svt_wav_header": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int64, _P, C.c_int64, _I64P]),
     "svt_pcm_decode": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int64, _P, C.c_int64, C.c_int32, C.c_int, _P]),

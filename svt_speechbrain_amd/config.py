@@ -47,6 +47,13 @@ class EncoderConfig:
     mask_feature_prob: float = 0.0
     mask_feature_length: int = 10
     mask_feature_min_masks: int = 0
+    # the checkpoint's dropouts and layerdrop (HF config fields of the same names; read only in training mode, freeze=False): filled
+    # from a model directory's config.json, 0 in every preset.  They travel to the device per forward (svt_encoder_set_dropout)
+    hidden_dropout: float = 0.0
+    attention_dropout: float = 0.0
+    activation_dropout: float = 0.0
+    feat_proj_dropout: float = 0.0
+    layerdrop: float = 0.0
 
     @property
     def head_dim(self) -> int:

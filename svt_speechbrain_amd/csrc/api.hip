@@ -214,9 +214,9 @@ int attn_tp(int prec, int dh, int T, bool bias) {
 
 int attention_scores_path(int prec, const void* Q, long ldq, const void* K, const void* V, long ldkv, int B,
                           int T, int H, int dh, float scale, const AttnBufs& ab, bool vt_ready, void* out,
-                          long ldo, hipStream_t s, const float* gate, const float* relpb, int gp, int o_pairs) {
+                          long ldo, hipStream_t s, const float* gate, const float* relpb, int gp, int o_pairs, const DropSpec* pdrop) {
   if (gp < 0) gp = prec;
-  if (gp >= 2 && !gate && flash_attention_x3_ok(dh) && ab.pl_qkv && ldkv == 3L * H * dh &&
+  if (gp >= 2 && !pdrop && !gate && flash_attention_x3_ok(dh) && ab.pl_qkv && ldkv == 3L * H * dh &&
       (const float*)V == (const float*)K + (long)H * dh) {
     // split-operand fused attention: cut the fp32 projections into 16-bit planes once, then three MFMAs per product
     // (attention_x3.hip flash_attn_x3_kernel) -- no (B, H, T, T) score tensor
@@ -238,7 +238,7 @@ int attention_scores_path(int prec, const void* Q, long ldq, const void* K, cons
                                      (long)T * ldo, B, T, H, dh, scale, s, o_pairs);
   }
   if (o_pairs) { set_error("attention: pair-row output is served by the fused split attention only"); return -1; }
-  if (use_flash(prec, dh, gate != nullptr, T)) {
+  if (!pdrop && use_flash(prec, dh, gate != nullptr, T)) {
     (void)vt_ready;
     return launch_flash_attention(Q, ldq, (long)T * ldq, K, V, ldkv, (long)T * ldkv, out, ldo, (long)T * ldo, B, T, H, dh,
                                   scale, s, gate, gate ? relpb : nullptr);
@@ -257,7 +257,8 @@ int attention_scores_path(int prec, const void* Q, long ldq, const void* K, cons
   if (int r = launch_gemm(gp, g, s)) return r;
   if (gate)
     if (int r = launch_scores_add_relbias(ab.S, (int64_t)B * H, H, T, Tp, gate, relpb, s)) return r;
-  if (int r = launch_softmax_rows(prec, ab.S, (int64_t)B * H * T, T, Tp, ab.P, s)) return r;
+  if (pdrop) { if (int r = launch_softmax_dropout(prec, ab.S, (int64_t)B * H * T, T, Tp, ab.P, 0, *pdrop, s)) return r; }
+  else if (int r = launch_softmax_rows(prec, ab.S, (int64_t)B * H * T, T, Tp, ab.P, s)) return r;
   if (!vt_ready)
     if (int r = launch_transpose_v(prec, V, B, T, H, dh, ldkv, 0, Tp, ab.Vt, s)) return r;
   GemmArgs o;
@@ -418,6 +419,31 @@ int svt_debug_layernorm(const svt_debug_layernorm_desc* d, int device, void* str
     rc = launch_layernorm_hilo_parts(d->parts, d->nparts, (long)d->part_stride, d->pbias, (const bf16_t*)d->rh, (const bf16_t*)d->rl,
                                      d->rows, d->D, d->gamma, d->beta, d->eps, (bf16_t*)d->yh, (bf16_t*)d->yl, d->yF, s);
   }
+  return rc ? SVT_ERR_INVALID : SVT_OK;
+}
+
+int svt_debug_dropout(const svt_debug_dropout_desc* d, int device, void* stream) {
+  auto refuse = [](const char* why) { set_error(std::string("svt_debug_dropout: ") + why); return SVT_ERR_INVALID; };
+  if (!d || d->struct_size != (int32_t)sizeof(svt_debug_dropout_desc)) return refuse("struct_size");
+  if (d->form < 0 || d->form > 2) return refuse("form is 0, 1 or 2");
+  if (!(d->p >= 0.0 && d->p < 1.0)) return refuse("p must lie in [0, 1)");
+  if (d->site < 0 || d->site > 255 || d->layer < 0 || d->layer >= (1 << 24)) return refuse("site 0 .. 255, layer 0 .. 2^24 - 1");
+  if (d->prec != 0 && d->prec != 1) return refuse("prec is 0 or 1");
+  if (d->form == 2) {
+    if (!d->S || !d->P || d->rows < 1 || d->T < 1 || d->Tp < d->T) return refuse("form 2 needs S, P, rows >= 1 and 1 <= T <= Tp");
+    if (((uintptr_t)d->S & 3) || ((uintptr_t)d->P & (d->prec ? 1 : 3))) return refuse("misaligned pointer");
+  } else {
+    if (d->n < 1) return refuse("n must be positive");
+    if (d->form == 0 ? !d->x : (!d->xh || !d->xl)) return refuse(d->form == 0 ? "null x" : "null xh / xl");
+  }
+  if (int r = check_device(device)) return r;
+  SVT_HIP(hipSetDevice(device));
+  hipStream_t s = (hipStream_t)stream;
+  const DropSpec spec = make_drop_spec(d->p, d->seed, d->step, d->site, d->layer);
+  int rc;
+  if (d->form == 0) rc = launch_dropout_rows(d->prec, d->x, d->n, d->e0, spec, s);
+  else if (d->form == 1) rc = launch_dropout_hilo((bf16_t*)d->xh, (bf16_t*)d->xl, d->n, d->e0, spec, s);
+  else rc = launch_softmax_dropout(d->prec, d->S, d->rows, d->T, d->Tp, d->P, d->e0, spec, s);
   return rc ? SVT_ERR_INVALID : SVT_OK;
 }
 
@@ -685,6 +711,7 @@ int svt_debug_set(int key, int value) {
   else if (key == 41) return g_c0_kernel_id;
   else if (key == 42) return g_vpad_kernel_id;
   else if (key == 43) return g_vstep_kernel_id;
+  else if (key == 44) return g_dropout_kernel_id;
   else { set_error("svt_debug_set: unknown key"); return SVT_ERR_INVALID; }
   return SVT_OK;
 }

@@ -4,6 +4,7 @@
 //   finalize: finalize_conv_stack -> finalize_projection -> finalize_pos_conv(_stack) -> encoder LayerNorm -> finalize_layer
 //   forward:  plan_encoder -> carve_encoder -> input_statistics -> choose_pair_rows -> conv_layer0 -> conv_stack -> feature_projection
 //             [-> spec_augment] -> positional_conv -> encoder_layers (post_ln_layers / pre_ln_layers) -> forward_tail
+//   training mode (svt_encoder_set_dropout): drop_rows / launch_dropout_hilo / the softmax form at the six sites of the header, skipped layers launch nothing
 #include "../../include/svt_mi355.h"
 #include "api.h"
 #include "common.h"
@@ -54,6 +55,9 @@ struct svt_encoder {
   const uint8_t* sa_feat = nullptr;
   int sa_B = 0, sa_T = 0;
   DevBuf spec_embed;
+  // optional training-mode state (svt_encoder_set_dropout): rates, (seed, step) and the skipped layers of the forwards to come
+  bool drop_on = false;
+  svt_dropout drop = {};
 };
 
 // every mode but plain fp32 (16-bit storage, or fp32 storage with split-operand products): conv layer 0 on the matrix pipe, the
@@ -302,6 +306,34 @@ int svt_encoder_set_spec_augment(svt_encoder* e, const uint8_t* time_mask, const
   return SVT_OK;
 }
 
+int svt_encoder_set_dropout(svt_encoder* e, const svt_dropout* st) {
+  auto refuse = [](const std::string& why) { set_error("svt_encoder_set_dropout: " + why); return SVT_ERR_INVALID; };
+  if (!e) return refuse("null encoder");
+  if (!st) { e->drop_on = false; e->drop = svt_dropout{}; return SVT_OK; }
+  if (st->struct_size != (int32_t)sizeof(svt_dropout)) return refuse("struct_size");
+  const svt_encoder_config& c = e->cfg;
+  const double rates[5] = {st->feat_proj_dropout, st->hidden_dropout, st->attention_dropout, st->activation_dropout, st->layerdrop};
+  for (double r : rates)
+    if (!(r >= 0.0 && r < 1.0)) return refuse("every rate must lie in [0, 1)");
+  if (st->skip_mask && c.num_layers > 64) return refuse("the skip bitmask serves up to 64 layers");
+  if (c.num_layers < 64 && (st->skip_mask >> c.num_layers)) return refuse("skip_mask names a layer at or above num_layers");
+  const bool elem = st->feat_proj_dropout > 0 || st->hidden_dropout > 0 || st->attention_dropout > 0 || st->activation_dropout > 0;
+  if (elem && c.precision >= 2)
+    return refuse(std::string("precision ") + (c.precision == SVT_PREC_FP16X3 ? "fp16x3" : "bf16x3") +
+                  " serves layerdrop only: the split-operand modes keep their activations as pair rows, which the dropout kernels do not "
+                  "read; use fp32, bf16 or fp16 for a nonzero element dropout");
+  if (st->attention_dropout > 0 && c.rel_pos_buckets > 0)
+    return refuse("attention_dropout > 0 with a relative position bias (WavLM) is not served: the reference runs torch's fused multi-head "
+                  "attention there, which offers no seam to pin a mask against; set attention_dropout to 0");
+  const uint64_t all_layers = c.num_layers >= 64 ? ~0ull : ((1ull << c.num_layers) - 1);
+  if ((st->skip_mask & 1) && c.rel_pos_buckets > 0 && (st->skip_mask & all_layers) != all_layers)
+    return refuse("layer 0 of an encoder with a relative position bias (WavLM) cannot be skipped: only that layer holds the position "
+                  "embedding, and the reference fails in the next layer");
+  e->drop = *st;
+  e->drop_on = true;
+  return SVT_OK;
+}
+
 int svt_encoder_load_param(svt_encoder* e, const char* key, const void* data_host, int dtype, const int64_t* shape,
                            int ndim) {
   if (!e) { set_error("null encoder"); return SVT_ERR_INVALID; }
@@ -375,6 +407,7 @@ struct EncPlan {
   bool pos_multi = false;  // this batch has enough rows for the multi-frame form
   bool hilo = false;       // post-LN encoder with the residual stream as a bf16 (hi, lo) pair
   bool ksplit_ws = false;  // few enough rows for the K-split FFN-2: its partial products get workspace
+  bool attn_drop = false;  // training mode with attention_dropout > 0: the score-matrix attention for every geometry
 };
 
 // false: the waveform is shorter than the receptive field
@@ -390,9 +423,10 @@ bool plan_encoder(const svt_encoder* e, int B, int64_t L, EncPlan* out) {
   p.D = c.hidden_size; p.F = c.intermediate_size; p.H = c.num_heads; p.dh = p.D / p.H;
   p.sp = storage_prec(c.precision); p.gp = c.precision; p.reduced = reduced_mode(c);
   p.rel = c.rel_pos_buckets > 0;
-  p.flash = use_flash(p.sp, p.dh, p.rel, p.T);
+  p.attn_drop = e->drop_on && e->drop.attention_dropout > 0;
+  p.flash = !p.attn_drop && use_flash(p.sp, p.dh, p.rel, p.T);
   p.planes = p.gp >= 2 && flash_attention_x3_ok(p.dh) && !p.rel;
-  p.attn_Tp = attn_tp(p.sp, p.dh, (int)p.T, p.rel);
+  p.attn_Tp = p.attn_drop ? round_up_int((int)p.T, 8) : attn_tp(p.sp, p.dh, (int)p.T, p.rel);
   p.Pf = e->pos_P;
   p.pos_Tq = p.Pf ? (p.T + p.Pf - 1) / p.Pf : 0;
   p.pos_Tp = p.Pf ? p.pos_Tq * p.Pf + c.pos_conv_kernel : p.T + c.pos_conv_kernel;
@@ -554,7 +588,20 @@ struct EncRun {
   // choose_pair_rows
   int pk_front = 0, pk_enc = 0;  // pair rows (kind of the pieces: 2 = bf16, 3 = fp16; 0 = none) for conv 1..n-1 + the feature projection / the encoder layers
   float* resid = nullptr;      // the fp32 residual stream of the encoder layers: w.xF, or w.xb where the layer input is itself fp32
+  // training mode (svt_encoder_set_dropout), or null: the plain forward
+  const svt_dropout* drop = nullptr;
+  bool skipped(int l) const { return drop && l < 64 && ((drop->skip_mask >> l) & 1); }
+  int last_active() const {    // the last layer that runs, -1: none
+    for (int l = c.num_layers - 1; l >= 0; --l) if (!skipped(l)) return l;
+    return -1;
+  }
 };
+
+// one dropout site on a whole (rows, W) tensor, in place; kind 0 = fp32, 1 = the 16-bit operand type.  rate 0: nothing is launched
+int drop_rows(const EncRun& x, int site, int layer, double p, void* buf, int kind, int64_t n) {
+  if (!x.drop || !(p > 0)) return SVT_OK;
+  return launch_dropout_rows(kind, buf, n, 0, make_drop_spec(p, x.drop->seed, x.drop->step, site, layer), x.s) ? SVT_ERR_HIP : SVT_OK;
+}
 
 LnArgs ln_f32(const EncRun& x, const void* in, int64_t rows, int D, const DevBuf& gamma, const DevBuf& beta, float eps) {
   LnArgs a;
@@ -836,7 +883,7 @@ int rows_gemm(const EncRun& x, const void* A, int K, const DevBuf& W, const DevB
 }
 
 // QKV projection -> attention -> out-projection: w.xb -> the attention branch in w.hF
-int attention_block(const EncRun& x, const EncLayerW& Lw, const LayerForm& f) {
+int attention_block(const EncRun& x, const EncLayerW& Lw, const LayerForm& f, int l) {
   const EncPlan& p = x.p;
   const EncWs& w = x.w;
   const int D = p.D;
@@ -849,21 +896,32 @@ int attention_block(const EncRun& x, const EncLayerW& Lw, const LayerForm& f) {
                                    Lw.g_const.as<float>(), w.gate, x.s)) return r;
     gate = w.gate;
   }
+  DropSpec ad;   // site 2
+  if (p.attn_drop) ad = make_drop_spec(x.drop->attention_dropout, x.drop->seed, x.drop->step, 2, l);
   if (int r = attention_scores_path(p.sp, w.qkv, 3L * D, (const char*)w.qkv + (size_t)D * esize(p.sp),
                                     (const char*)w.qkv + (size_t)2 * D * esize(p.sp), 3L * D, p.B, (int)p.T, p.H, p.dh,
-                                    1.0f / std::sqrt((float)p.dh), w.ab, p.planes, w.attn_o, D, x.s, gate, w.relpb, p.gp, x.pk_enc ? 1 : 0)) return r;
+                                    1.0f / std::sqrt((float)p.dh), w.ab, p.planes, w.attn_o, D, x.s, gate, w.relpb, p.gp, x.pk_enc ? 1 : 0,
+                                    p.attn_drop ? &ad : nullptr)) return r;
   // (rounds 1-2 fused this projection with the residual add and the LayerNorm in one row-complete kernel, 44 us against 29 + 23; with
   //  the projection on gemm_pps_kernel the pair costs 20.6 + 23.9 us and the fused kernel -- every workgroup streaming all of W,
   //  0.16 of the matrix pipe -- is gone: C2 6 093-6 110 against 6 066-6 074 clips/s on one box)
-  return rows_gemm(x, w.attn_o, D, Lw.wo, Lw.bo, D, w.hF, f.branch_f32, ACT_NONE);
+  if (int r = rows_gemm(x, w.attn_o, D, Lw.wo, Lw.bo, D, w.hF, f.branch_f32, ACT_NONE)) return r;
+  if (!x.drop) return SVT_OK;
+  return drop_rows(x, 3, l, x.drop->hidden_dropout, w.hF, f.branch_f32 ? 0 : (p.sp ? 1 : 0), p.rows * D);   // site 3: the branch, before the LayerNorm adds it
 }
 
 // FFN-1 (GELU) -> FFN-2: w.xb -> the feed-forward branch in w.hF (K-split form: in w.ksplit)
-int ffn_block(const EncRun& x, const EncLayerW& Lw, const LayerForm& f) {
+int ffn_block(const EncRun& x, const EncLayerW& Lw, const LayerForm& f, int l) {
   const EncWs& w = x.w;
   const int D = x.p.D, F = x.p.F, rows = (int)x.p.rows;
   if (int r = rows_gemm(x, w.xb, D, Lw.w1, Lw.b1, F, w.ffn, f.ffn1_f32, ACT_GELU, nullptr, f.ffn1_pairs)) return r;
-  if (!f.ffn2_ksplit) return rows_gemm(x, w.ffn, F, Lw.w2, Lw.b2, D, w.hF, f.branch_f32, ACT_NONE);
+  if (x.drop)   // site 4, behind GELU
+    if (int r = drop_rows(x, 4, l, x.drop->activation_dropout, w.ffn, f.ffn1_f32 ? 0 : (x.p.sp ? 1 : 0), x.p.rows * F)) return r;
+  if (!f.ffn2_ksplit) {
+    if (int r = rows_gemm(x, w.ffn, F, Lw.w2, Lw.b2, D, w.hF, f.branch_f32, ACT_NONE)) return r;
+    if (!x.drop) return SVT_OK;
+    return drop_rows(x, 5, l, x.drop->hidden_dropout, w.hF, f.branch_f32 ? 0 : (x.p.sp ? 1 : 0), x.p.rows * D);   // site 5, behind FFN-2
+  }
   // a few utterances: K = F split four ways over workgroups, raw fp32 partial tiles, summed (+ bias, rounded to the operand type
   // like the un-split product's stored result) by the LayerNorm that reads them
   GemmArgs g;
@@ -879,12 +937,14 @@ int ffn_block(const EncRun& x, const EncLayerW& Lw, const LayerForm& f) {
 template <class Ln0, class Ln>
 int post_ln_layers(const EncRun& x, const LayerForm& f, Ln0&& ln0, Ln&& ln) {
   if (int r = ln0()) return r;
+  const int last = x.last_active();   // (the plain forward: num_layers - 1)
   for (int l = 0; l < x.c.num_layers; ++l) {
+    if (x.skipped(l)) continue;       // layerdrop: a skipped layer launches nothing
     const EncLayerW& Lw = x.e->layers[l];
-    if (int r = attention_block(x, Lw, f)) return r;
+    if (int r = attention_block(x, Lw, f, l)) return r;
     if (int r = ln(Lw, false, false)) return r;
-    if (int r = ffn_block(x, Lw, f)) return r;
-    if (int r = ln(Lw, true, l + 1 == x.c.num_layers)) return r;
+    if (int r = ffn_block(x, Lw, f, l)) return r;
+    if (int r = ln(Lw, true, l == last)) return r;
   }
   return SVT_OK;
 }
@@ -911,9 +971,15 @@ int post_ln_hilo(const EncRun& x) {
   // branch outputs (out-proj / FFN-2) are stored in the operand type (bf16: half the store burst of the GEMM epilogue and half the
   // read of the LayerNorm) and widened when added to the residual stream
   f.branch_f32 = 0;
-  f.ffn2_ksplit = ffn2_ksplit_ok(x);
+  // (hidden_dropout > 0: the un-split FFN-2 -- the K-split form hands raw partials to the LayerNorm, and there is no tensor to drop)
+  f.ffn2_ksplit = ffn2_ksplit_ok(x) && !(x.drop && x.drop->hidden_dropout > 0);
   return post_ln_layers(x, f,
-    [&] { return launch_layernorm_hilo(nullptr, nullptr, nullptr, w.preF, rows, D, x.e->enc_g.as<float>(), x.e->enc_b.as<float>(), eps, xh, xl, nullptr, x.s); },
+    [&]() -> int {
+      if (int r = launch_layernorm_hilo(nullptr, nullptr, nullptr, w.preF, rows, D, x.e->enc_g.as<float>(), x.e->enc_b.as<float>(), eps, xh, xl, nullptr, x.s)) return r;
+      if (!x.drop || !(x.drop->hidden_dropout > 0)) return SVT_OK;
+      // site 1 on the stream as this family stores it: the value hi + lo, cut again
+      return launch_dropout_hilo(xh, xl, rows * D, 0, make_drop_spec(x.drop->hidden_dropout, x.drop->seed, x.drop->step, 1, 0), x.s) ? SVT_ERR_HIP : SVT_OK;
+    },
     [&](const EncLayerW& Lw, bool second, bool last) {
       const float *g = (second ? Lw.ln2g : Lw.ln1g).as<float>(), *b = (second ? Lw.ln2b : Lw.ln1b).as<float>();
       float* const yF = last ? x.resid : nullptr;
@@ -936,7 +1002,9 @@ int post_ln_pairs(const EncRun& x) {
   return post_ln_layers(x, f,
     [&] {
       LnArgs n = ln_f32(x, w.preF, x.p.rows, x.p.D, x.e->enc_g, x.e->enc_b, x.c.layer_norm_eps);
-      n.yP = w.xb; n.pair_kind = x.pk_enc; n.yF = pair_resid ? nullptr : x.resid;
+      // (every layer skipped: the first LayerNorm is also the last, and leaves the fp32 result.  Element dropouts are refused in the
+      //  split modes -- svt_encoder_set_dropout -- so site 1 never reaches pair rows)
+      n.yP = w.xb; n.pair_kind = x.pk_enc; n.yF = (pair_resid && x.last_active() >= 0) ? nullptr : x.resid;
       return launch_layernorm(n, x.s);
     },
     [&](const EncLayerW& Lw, bool second, bool last) {
@@ -956,7 +1024,14 @@ int post_ln_plain(const EncRun& x, int branch_f32) {
   f.branch_f32 = branch_f32;
   auto out = [&](LnArgs n) { n.yT = w.xb; n.yF = x.p.sp ? x.resid : nullptr; return launch_layernorm(n, x.s); };
   return post_ln_layers(x, f,
-    [&] { return out(ln_f32(x, w.preF, x.p.rows, x.p.D, x.e->enc_g, x.e->enc_b, x.c.layer_norm_eps)); },
+    [&]() -> int {
+      if (int r = out(ln_f32(x, w.preF, x.p.rows, x.p.D, x.e->enc_g, x.e->enc_b, x.c.layer_norm_eps))) return r;
+      if (!x.drop) return SVT_OK;
+      // site 1: the operand copy and, where it is a buffer of its own, the fp32 residual stream beside it -- the same mask
+      const int64_t n = x.p.rows * x.p.D;
+      if (int r = drop_rows(x, 1, 0, x.drop->hidden_dropout, w.xb, x.p.sp ? 1 : 0, n)) return r;
+      return (void*)x.resid != w.xb ? drop_rows(x, 1, 0, x.drop->hidden_dropout, x.resid, 0, n) : SVT_OK;
+    },
     [&](const EncLayerW& Lw, bool second, bool) {
       LnArgs n = ln_f32(x, w.hF, x.p.rows, x.p.D, second ? Lw.ln2g : Lw.ln1g, second ? Lw.ln2b : Lw.ln1b, x.c.layer_norm_eps);
       n.x_is_f32 = branch_f32; n.add = x.resid;
@@ -979,7 +1054,8 @@ int pre_ln_layers(const EncRun& x, int branch_f32, float** final_x) {
     if (x.pk_enc && y_op) {   // pair rows for the products; h (fp32) += branch in place
       n.add = (const float*)branch; n.yP = y_op; n.pair_kind = x.pk_enc;
     } else if (!branch) {
-      n.yT = y_op; n.yF = y_f32;
+      if (y_op) { n.yT = y_op; n.yF = y_f32; }
+      else { n.prec = 0; n.yT = y_f32; }   // every layer skipped: the final LayerNorm of the untouched stream, in fp32
     } else if (!branch_f32) {  // x = bf16 branch, add = fp32 residual, sumF = residual updated in place
       n.x = branch; n.x_is_f32 = 0; n.add = h; n.yT = y_op; n.yF = y_f32;
     } else {
@@ -988,13 +1064,16 @@ int pre_ln_layers(const EncRun& x, int branch_f32, float** final_x) {
     }
     return launch_layernorm(n, x.s);
   };
+  if (x.drop)   // site 1: in this family in front of the layers, on the fp32 stream
+    if (int r = drop_rows(x, 1, 0, x.drop->hidden_dropout, h, 0, x.p.rows * x.p.D)) return r;
   const void* pending = nullptr;  // branch output not yet added to h
   for (int l = 0; l < x.c.num_layers; ++l) {
+    if (x.skipped(l)) continue;   // layerdrop: a skipped layer launches nothing
     const EncLayerW& Lw = x.e->layers[l];
     if (int r = ln_add(Lw.ln1g, Lw.ln1b, pending, w.xb, nullptr)) return r;
-    if (int r = attention_block(x, Lw, f)) return r;
+    if (int r = attention_block(x, Lw, f, l)) return r;
     if (int r = ln_add(Lw.ln2g, Lw.ln2b, w.hF, w.xb, nullptr)) return r;
-    if (int r = ffn_block(x, Lw, f)) return r;
+    if (int r = ffn_block(x, Lw, f, l)) return r;
     pending = w.hF;
   }
   // final LN(h + last FFN branch) -> fp32 (xF is unused in this family when prec == 0 it aliases xb: use qkv space)
@@ -1013,7 +1092,9 @@ int encoder_layers(const EncRun& x, float** final_x) {
   const int branch_f32 = (p.sp && vecD) ? 0 : 1;
   if (x.c.stable_layer_norm) return pre_ln_layers(x, branch_f32, final_x);
   *final_x = x.resid;
-  if (p.hilo) return post_ln_hilo(x);
+  // (every layer skipped: no product reads the (hi, lo) pair, and its first LayerNorm -- layernorm_f32_to_hilo_kernel -- leaves no
+  //  fp32 result; the plain form's does)
+  if (p.hilo && x.last_active() >= 0) return post_ln_hilo(x);
   if (x.pk_enc) return post_ln_pairs(x);
   return post_ln_plain(x, branch_f32);
 }
@@ -1050,6 +1131,7 @@ int encoder_forward_impl(svt_encoder* e, const float* wav, int32_t B, int64_t L,
   EncPlan plan;
   if (!plan_encoder(e, B, L, &plan)) { set_error("encoder_forward: waveform shorter than the receptive field"); return SVT_ERR_INVALID; }
   EncRun x{e, e->cfg, plan, carve_encoder(e, plan, workspace), (hipStream_t)stream};
+  x.drop = e->drop_on ? &e->drop : nullptr;
   const bool masks = e->sa_time || e->sa_feat;
   if (masks && (e->sa_B != B || e->sa_T != plan.T)) {
     set_error("encoder_forward: the SpecAugment masks were set for (" + std::to_string(e->sa_B) + ", " + std::to_string(e->sa_T) + ") clips x frames, this call has (" +
@@ -1072,6 +1154,8 @@ int encoder_forward_impl(svt_encoder* e, const float* wav, int32_t B, int64_t L,
     if (int r = conv_stack(x, &cur)) return r;
   }
   if (int r = feature_projection(x, cur)) return r;
+  if (x.drop)    // site 0, in front of SpecAugment as in HF's feature projection
+    if (int r = drop_rows(x, 0, 0, x.drop->feat_proj_dropout, x.w.hF, 0, plan.rows * plan.D)) return r;
   if (masks)
     if (int r = spec_augment(x)) return r;
   if (int r = positional_conv(x)) return r;

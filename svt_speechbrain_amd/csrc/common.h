@@ -540,6 +540,17 @@ int launch_drop_freq_chunk(const float* in, int rows, int64_t n, int64_t ld_in, 
 // null (both: no launch).  One launch; frames with nothing to do are neither read nor written
 int launch_spec_augment(float* h, int B, int T, int D, int64_t ld, const uint8_t* time_mask, const uint8_t* feat_mask, const float* embed,
                         hipStream_t s);
+// Training-mode dropout (dropout.hip; the mask function: philox.h).  make_drop_spec: thr = floor(p * 2^32), scale = float(1 / (1 - p)),
+// 0 <= p < 1.  All in place, one launch each, logical index of element i = e0 + i:
+//   launch_dropout_rows     n elements of fp32 (kind 0) or the 16-bit operand type (kind 1)
+//   launch_dropout_hilo     the bf16 (hi, lo) residual stream: the value hi + lo is scaled or zeroed and cut again
+//   launch_softmax_dropout  launch_softmax_rows with the mask on the probabilities; row r, column j: e0 + r*T + j
+struct DropSpec;
+DropSpec make_drop_spec(double p, uint64_t seed, uint32_t step, int site, int layer);
+int launch_dropout_rows(int kind, void* x, int64_t n, uint64_t e0, const DropSpec& d, hipStream_t s);
+int launch_dropout_hilo(bf16_t* xh, bf16_t* xl, int64_t n, uint64_t e0, const DropSpec& d, hipStream_t s);
+int launch_softmax_dropout(int prec, const float* S, int64_t rows, int T, int Tp, void* P, uint64_t e0, const DropSpec& d, hipStream_t s);
+extern int g_dropout_kernel_id;   // key 44 (query): which dropout kernel the last launch chose (dropout.hip; include/svt_mi355.h lists the ids)
 // PCM <-> fp32 on the bytes of a wav file (pcm.hip): interleaved little-endian frames at any byte address <-> planar fp32 rows (4-byte
 // aligned, pitch ld >= frames); format = svt_pcm_format (encode: S16 or F32); downmix: 2 channels -> the one row 0.5 * (l + r).  One launch
 int launch_pcm_decode(const void* src, int format, int channels, int64_t frames, float* out, int64_t ld, bool downmix, hipStream_t s);

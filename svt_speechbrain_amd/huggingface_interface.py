@@ -118,7 +118,11 @@ def _config_from_dir(path: str) -> Optional[EncoderConfig]:
         conv_pos_batch_norm=bool(j.get("conv_pos_batch_norm", False)) and fam == "hubert",
         mask_time_prob=float(j.get("mask_time_prob", 0.05)), mask_time_length=int(j.get("mask_time_length", 10)),
         mask_time_min_masks=int(j.get("mask_time_min_masks", 2)), mask_feature_prob=float(j.get("mask_feature_prob", 0.0)),
-        mask_feature_length=int(j.get("mask_feature_length", 10)), mask_feature_min_masks=int(j.get("mask_feature_min_masks", 0)), **kw)
+        mask_feature_length=int(j.get("mask_feature_length", 10)), mask_feature_min_masks=int(j.get("mask_feature_min_masks", 0)),
+        # HF's class defaults again (Wav2Vec2Config and its siblings: 0.1 each, feat_proj_dropout 0.0); read in training mode only
+        hidden_dropout=float(j.get("hidden_dropout", 0.1)), attention_dropout=float(j.get("attention_dropout", 0.1)),
+        activation_dropout=float(j.get("activation_dropout", 0.1)), feat_proj_dropout=float(j.get("feat_proj_dropout", 0.0)),
+        layerdrop=float(j.get("layerdrop", 0.1)), **kw)
 
 
 class _DevF64:
@@ -221,6 +225,8 @@ class HuggingFaceWav2Vec2(ReplicaAware, nn.Module):
             self.model.add("masked_spec_embed", torch.empty(cfg.hidden_size, dtype=torch.float32).uniform_(generator=g))
         self._mask_staging = None   # spec_augment.MaskStaging, made by the first forward that uploads a mask
         self.last_spec_masks = (None, None)   # (time, feature) bool arrays the last forward applied (None: that mask was not applied)
+        self._dropout_step = 0     # `step` of the dropout mask function: advances once per training-mode forward (dropout_step)
+        self.last_dropout = None   # dict(seed, step, skipped) of the last forward that ran dropouts / layerdrop, None for a plain one
         # device side: one C object per device (shared with nn.DataParallel replicas, see _device.py) and ONE generation
         # counter of the parameter values, shared BY REFERENCE with every replica(): whoever changes the weights bumps it,
         # every device object compares it before a forward
@@ -532,9 +538,68 @@ class HuggingFaceWav2Vec2(ReplicaAware, nn.Module):
                    "svt_encoder_set_spec_augment", lib)
         slot.masks = (t_dev, f_dev)
 
+    # ------------------------------------------------------------------ dropouts and layerdrop (HF's model in train() mode)
+    @property
+    def dropout_step(self) -> int:
+        """The ``step`` word of the dropout mask function the NEXT training-mode forward uses; it advances by one per such forward."""
+        return self._dropout_step
+
+    @dropout_step.setter
+    def dropout_step(self, v: int) -> None:
+        self._dropout_step = int(v) & 0xFFFFFFFF
+
+    def _dropout_rates(self):
+        c = self.config
+        return (c.feat_proj_dropout, c.hidden_dropout, c.attention_dropout, c.activation_dropout, c.layerdrop)
+
+    def _set_dropout(self, lib, slot, dropout_seed, dropout_step, skip_layers) -> None:
+        """Hand this forward's training-mode state to the device object, or clear it.  Active only with ``freeze=False``, the module and
+        its model in training mode and at least one of the five rates above 0; otherwise nothing is drawn, nothing is called (a handle
+        that had a state is told once to drop it) and the forward is the plain one.  Called BEFORE the workspace query, whose size
+        follows the state."""
+        c = self.config
+        active = (not self.freeze) and self.training and self.model.training and any(r > 0 for r in self._dropout_rates())
+        if not active:
+            if dropout_seed is not None or dropout_step is not None or skip_layers is not None:
+                raise ValueError("dropout_seed / dropout_step / skip_layers apply to a training-mode forward (freeze=False, train()) of a "
+                                 "model with a nonzero dropout or layerdrop rate")
+            self.last_dropout = None
+            if slot.dropout:
+                _lib.check(lib.svt_encoder_set_dropout(slot.handle, None), "svt_encoder_set_dropout", lib)
+                slot.dropout = False
+            return
+        n = c.num_hidden_layers
+        if skip_layers is not None:
+            skipped = tuple(bool(v) for v in skip_layers)
+            if len(skipped) != n:
+                raise ValueError(f"skip_layers needs one bool per layer ({n}), got {len(skipped)}")
+        else:
+            # HF's encoder loop: one torch.rand([]) per layer, in layer order, from torch's HOST default generator -- drawn whatever
+            # layerdrop is, as HF draws it -- and the layer is skipped iff the draw is below layerdrop
+            from .dropout import draw_layerdrop
+            skipped = draw_layerdrop(n, c.layerdrop, c.family)
+        if n > 64 and any(skipped):
+            raise _lib.SvtError("layerdrop: the skip bitmask of svt_encoder_set_dropout serves up to 64 layers")
+        # the device generator's seed: reading it consumes no host draw, so the layerdrop parity above is kept
+        seed = int(torch.cuda.initial_seed() if dropout_seed is None else dropout_seed) & 0xFFFFFFFFFFFFFFFF
+        if dropout_step is None:
+            step = self._dropout_step
+            self._dropout_step = (step + 1) & 0xFFFFFFFF
+        else:
+            step = int(dropout_step) & 0xFFFFFFFF   # an explicit step leaves the module's counter alone
+        st = _lib.DropoutC()
+        st.struct_size = C.sizeof(_lib.DropoutC)
+        st.step = step
+        st.feat_proj_dropout, st.hidden_dropout, st.attention_dropout, st.activation_dropout, st.layerdrop = self._dropout_rates()
+        st.seed = seed
+        st.skip_mask = sum(1 << l for l, v in enumerate(skipped) if v)
+        self.last_dropout = dict(seed=seed, step=step, skipped=skipped)
+        _lib.check(lib.svt_encoder_set_dropout(slot.handle, C.byref(st)), "svt_encoder_set_dropout", lib)
+        slot.dropout = True
+
     # ------------------------------------------------------------------ forward (reference :263-297)
     def forward(self, wav: torch.Tensor, clips_per_norm_group: int = 0, *, mask_time_indices=None,
-                mask_feature_indices=None) -> torch.Tensor:
+                mask_feature_indices=None, dropout_seed=None, dropout_step=None, skip_layers=None) -> torch.Tensor:
         """``clips_per_norm_group`` (extension; 0 = the reference: both whole-tensor layer norms over the entire batch):
         with 1, a batch of B equal-length utterances returns what B batch-1 forwards return, which is how the reference
         evaluates (``train_audio_ssl.py:90`` asserts batch 1) -- one batched launch sequence instead of B.
@@ -546,25 +611,46 @@ class HuggingFaceWav2Vec2(ReplicaAware, nn.Module):
         frames with ``masked_spec_embed`` and zeroes the masked columns.  ``last_spec_masks`` holds what was applied.  In eval mode
         nothing is drawn and the forward is the plain one.  ``mask_time_indices`` / ``mask_feature_indices`` (extension, keyword
         only; bool ``(B, T)`` / ``(B, D)`` on the host or the device) bypass the draw and apply in any mode; they need the flag.
-        The reference in training mode also runs the checkpoint's dropouts and layerdrop; this path does not (it stays
-        deterministic), so parity is with the reference at dropout = layerdrop = 0, which is how every golden is made.  Under
-        ``nn.DataParallel`` each replica draws for its own sub-batch: the draws match the reference's for the single-process order only."""
+        Under ``nn.DataParallel`` each replica draws for its own sub-batch: the draws match the reference's for the single-process
+        order only.
+
+        Dropouts and layerdrop (HF's model in ``train()`` mode, which the reference's ``freeze=False`` leaves it in): with
+        ``freeze=False``, this module in training mode and at least one of ``hidden_dropout``, ``attention_dropout``,
+        ``activation_dropout``, ``feat_proj_dropout``, ``layerdrop`` of the config above 0 (a model directory's config.json fills
+        them; every preset carries 0), each forward
+        * draws one ``torch.rand([])`` per layer, in layer order, from torch's host generator and skips layer ``l`` iff its draw is
+          ``< layerdrop`` -- HF's loop, so a run seeded alike (``torch.manual_seed``) skips the same layers and leaves the generator
+          in the same state; a skipped layer launches nothing;
+        * applies the element dropouts with a mask that is a function of position: element ``e`` of site ``s`` in layer ``l`` is kept
+          iff ``Philox4x32-10(key=(seed_lo, seed_hi), counter=(q_lo, q_hi, s | l << 8, step))[e & 3] >= floor(p * 2**32)`` with
+          ``q = e >> 2``; kept values are multiplied by ``float(1 / (1 - p))``, dropped ones become +0.  ``e`` is the logical index
+          (``(b*T + t)*W + c``; ``((b*H + h)*T + i)*T + j`` for the attention probabilities).  Sites: 0 feature projection, 1 the
+          encoder's dropout, 2 attention probabilities, 3 attention branch, 4 behind GELU, 5 behind FFN-2.  ``seed`` is
+          ``torch.cuda.initial_seed()``, ``step`` the module's ``dropout_step`` counter, which advances once per such forward.  The
+          masks are NOT the ones torch's device generator would draw (those depend on its launch geometry): parity with the
+          reference holds for masks injected into it (tests/golden/make_golden_encoder_dropout.py), not for its own draws.
+        ``dropout_seed=`` / ``dropout_step=`` override the two words for one call (an explicit step leaves the counter alone);
+        ``skip_layers=`` (one bool per layer) bypasses the layerdrop draw.  ``last_dropout`` records seed, step and skipped layers.
+        In ``eval()``, with ``freeze=True`` or with all five rates 0 nothing is drawn and the forward is the plain one.  Refused with
+        an ``SvtError``: a nonzero element rate in "fp16x3" / "bf16x3" (they serve layerdrop only), ``attention_dropout > 0`` for WavLM,
+        and a skipped layer 0 for WavLM.  HuBERT's positional BatchNorm stays in eval mode."""
         if not self.freeze and torch.is_grad_enabled() and not self._warned_grad:
             warnings.warn("svt_speechbrain_amd.HuggingFaceWav2Vec2 is forward-only: the output is detached "
                           "(fine-tuning the encoder is out of scope of the MI355X path)")
             self._warned_grad = True
         with torch.no_grad():
             return self.extract_features(wav, clips_per_norm_group, mask_time_indices=mask_time_indices,
-                                         mask_feature_indices=mask_feature_indices).detach()
+                                         mask_feature_indices=mask_feature_indices, dropout_seed=dropout_seed,
+                                         dropout_step=dropout_step, skip_layers=skip_layers).detach()
 
     def forward_head(self, wav: torch.Tensor, head, clips_per_norm_group: int = 0, frames: Optional[torch.Tensor] = None,
                      pitch_octave_num: int = 4, pitch_class_num: int = 12, *, mask_time_indices=None,
-                     mask_feature_indices=None) -> torch.Tensor:
+                     mask_feature_indices=None, dropout_seed=None, dropout_step=None, skip_layers=None) -> torch.Tensor:
         """``head(self(wav))`` -- the two module calls of ``AMT.compute_forward`` (train_audio_ssl.py:36-39) -- as ONE C-ABI call
         that never writes the (B, T, D) features: the whole-batch output norm, the frame head (``svt_speechbrain_amd.Linear``
         with <= 32 outputs) and, when ``frames`` (a ``(B*T, 4)`` int32 device tensor) is given, the per-frame sigmoid / argmax
-        are fused behind the encoder (``svt_encoder_forward_head``).  Returns the ``(B, T, n_out)`` logits.  SpecAugment masks are
-        drawn or taken as in ``forward``."""
+        are fused behind the encoder (``svt_encoder_forward_head``).  Returns the ``(B, T, n_out)`` logits.  SpecAugment masks,
+        dropouts and layerdrop are drawn or taken as in ``forward``."""
         if wav.dim() != 2:
             raise ValueError(f"expected a (batch, samples) waveform, got shape {tuple(wav.shape)}")
         if not wav.is_cuda:
@@ -577,6 +663,7 @@ class HuggingFaceWav2Vec2(ReplicaAware, nn.Module):
         T = self.config.frames(L)
         if B < 1 or T < 1:
             raise ValueError(f"waveform of {L} samples is shorter than the encoder's receptive field")
+        self._set_dropout(lib, slot, dropout_seed, dropout_step, skip_layers)
         need = lib.svt_encoder_workspace_bytes(slot.handle, B, L)
         if need < 0:
             raise _lib.SvtError(_lib.last_error(lib))
@@ -602,7 +689,7 @@ class HuggingFaceWav2Vec2(ReplicaAware, nn.Module):
                 and 1 <= head.w.out_features <= 32)
 
     def extract_features(self, wav: torch.Tensor, clips_per_norm_group: int = 0, *, mask_time_indices=None,
-                         mask_feature_indices=None) -> torch.Tensor:
+                         mask_feature_indices=None, dropout_seed=None, dropout_step=None, skip_layers=None) -> torch.Tensor:
         if wav.dim() != 2:
             raise ValueError(f"expected a (batch, samples) waveform, got shape {tuple(wav.shape)}")
         if not wav.is_cuda:
@@ -614,6 +701,7 @@ class HuggingFaceWav2Vec2(ReplicaAware, nn.Module):
         T = self.config.frames(L)
         if B < 1 or T < 1:
             raise ValueError(f"waveform of {L} samples is shorter than the encoder's receptive field")
+        self._set_dropout(lib, slot, dropout_seed, dropout_step, skip_layers)
         need = lib.svt_encoder_workspace_bytes(slot.handle, B, L)
         if need < 0:
             raise _lib.SvtError(_lib.last_error(lib))

@@ -302,7 +302,10 @@ class LinearProbe:
         """One training step from waveforms: the frozen encoder, then ``fit_features``.  An encoder built with
         ``apply_spec_augment=True, freeze=False`` (weights untouched by this step, model in training mode) draws and applies its
         SpecAugment masks inside that call -- one time-mask draw (and one feature-mask draw when its probability is above 0) per
-        step, nothing to do here (tests/test_gpu_spec_augment.py checks the draws and the loss terms)."""
+        step, nothing to do here (tests/test_gpu_spec_augment.py checks the draws and the loss terms).  The same holds for the
+        checkpoint's dropouts and layerdrop of a ``freeze=False`` encoder: they run inside the module's forward, one layerdrop draw per
+        layer and one ``dropout_step`` per step (tests/test_gpu_encoder_dropout.py checks the loss against ``encoder.forward`` at the
+        same seed and step)."""
         with torch.no_grad():
             feats = self.amt._get("wav2vec2")(wavs)
         return self.fit_features(feats, wav_lens, anno, anno_lens)
