@@ -744,6 +744,23 @@ int svt_clip_adadelta_step(int32_t n_tensors, float* const* params_dev, float* c
                            float* const* acc_delta_dev, const int64_t* numels, float lr, double rho, float eps, float weight_decay,
                            int32_t maximize, float max_norm, float* total_norm_dev, void* workspace_dev, size_t* workspace_bytes,
                            int device, void* stream);
+/* clip_grad_norm_ (when max_norm > 0, as svt_clip_adadelta_step: total_norm_dev, may be NULL, receives the pre-clip norm and every
+ * gradient is scaled in place) then torch.optim.Adam's single-tensor update of n_tensors >= 1 contiguous f32 tensors -- any number: the
+ * tensor table travels in the workspace, not in kernel arguments.  flags: SVT_ADAM_MAXIMIZE | SVT_ADAM_AMSGRAD (max_exp_avg_sq_dev is
+ * then required, else it must be NULL) | SVT_ADAM_DECOUPLED (AdamW: p *= 1 - lr * weight_decay, nothing added to the gradient).  The
+ * pointer arrays, numels, step_size (lr / (1 - beta1^step) per tensor) and bc2_sqrt (sqrt(1 - beta2^step) per tensor) are HOST arrays;
+ * the bias corrections are per tensor because a parameter whose gradient was None in some step has a smaller step.  Alignment: every
+ * tensor pointer may be ANY 4-byte-aligned address (a view into a flat buffer); 16-byte accesses are used where the arrays of a tensor
+ * share one offset from a 16-byte boundary.  A tensor of 0 elements is skipped (its pointers may be NULL).  Workspace: the size-query
+ * convention (workspace_dev NULL -> *workspace_bytes), 16-byte aligned.  No host-device synchronisation, no copy on the stream; two
+ * calls on equal inputs at equal addresses give equal bits. */
+#define SVT_ADAM_MAXIMIZE 1
+#define SVT_ADAM_AMSGRAD 2
+#define SVT_ADAM_DECOUPLED 4
+int svt_clip_adam_step(int32_t n_tensors, float* const* params_dev, float* const* grads_dev, float* const* exp_avg_dev,
+                       float* const* exp_avg_sq_dev, float* const* max_exp_avg_sq_dev, const int64_t* numels, const float* step_size,
+                       const float* bc2_sqrt, double lr, double beta1, double beta2, double eps, double weight_decay, int32_t flags,
+                       float max_norm, float* total_norm_dev, void* workspace_dev, size_t* workspace_bytes, int device, void* stream);
 
 /* Fused attention kernel alone (bf16, head_dim 64 or 128): o[b,t,h*dh+d] = softmax(scale q k^T) v with q rows at
  * q + (b*t_len + t)*ldq + h*dh, k / v rows likewise with ldkv, o with ldo (element strides).  Replaces the eager

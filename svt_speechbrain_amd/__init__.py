@@ -31,13 +31,13 @@ from . import audio_io  # noqa: F401
 from .audio_io import info, load, save, read_audio, write_audio  # noqa: F401
 from .dataio import read_utterance  # noqa: F401
 from . import training  # noqa: F401
-from .training import Adadelta, LinearProbe, FusionTrainer, VideoProbe  # noqa: F401
+from .training import Adadelta, Adam, AdamW, LinearProbe, FusionTrainer, VideoProbe  # noqa: F401
 
 __all__ = ["EncoderConfig", "PRESETS", "config_from_source", "HuggingFaceWav2Vec2", "Linear", "FusionRCA", "Fbank",
            "decode_frames", "frame2note", "frames2note", "frames2note_batch", "frames_to_info", "ctc_greedy_decode", "filter_ctc_output", "AMTForward",
            "SongTranscriber", "utterance_bounds", "save_song_features", "feature_path", "song_video_features",
            "save_song_video_features", "video_feature_path", "EvalTransform", "TrainTransform", "VideoClip", "pad_roi_batch", "FairseqAVHubertPretrain",
-           "Adadelta", "LinearProbe", "FusionTrainer", "VideoProbe",
+           "Adadelta", "Adam", "AdamW", "LinearProbe", "FusionTrainer", "VideoProbe",
            "SNRS_DB", "compute_amplitude", "mix_at_snrs", "assemble_noise_track", "split_natural_files", "natural_keep", "babble_keep",
            "babble_split", "noise_pools", "natural_pools", "babble_pools", "noisy_wav_path", "NoiseSweep",
            "Resample", "SpeedPerturb", "resample_table", "resample_to_mono",

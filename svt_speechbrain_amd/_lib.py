@@ -250,6 +250,9 @@ SYMBOLS = {
     "svt_clip_adadelta_step": (C.c_int, [C.c_int32, C.POINTER(_P), C.POINTER(_P), C.POINTER(_P), C.POINTER(_P), _I64P, C.c_float,
                                          C.c_double, C.c_float, C.c_float, C.c_int32, C.c_float, _P, _P, C.POINTER(C.c_size_t), C.c_int,
                                          _P]),
+    "svt_clip_adam_step": (C.c_int, [C.c_int32, C.POINTER(_P), C.POINTER(_P), C.POINTER(_P), C.POINTER(_P), C.POINTER(_P), _I64P,
+                                     C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_double, C.c_double, C.c_double, C.c_double,
+                                     C.c_double, C.c_int32, C.c_float, _P, _P, C.POINTER(C.c_size_t), C.c_int, _P]),
     "svt_debug_attention": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
                                       C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_float, C.c_int, C.c_void_p]),
     "svt_debug_attention_bias": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int64,

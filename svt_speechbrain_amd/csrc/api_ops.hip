@@ -526,4 +526,57 @@ int svt_clip_adadelta_step(int32_t n_tensors, float* const* params, float* const
   return SVT_OK;
 }
 
+int svt_clip_adam_step(int32_t n_tensors, float* const* params, float* const* grads, float* const* exp_avg, float* const* exp_avg_sq,
+                       float* const* max_exp_avg_sq, const int64_t* numels, const float* step_size, const float* bc2_sqrt, double lr,
+                       double beta1, double beta2, double eps, double weight_decay, int32_t flags, float max_norm, float* total_norm,
+                       void* workspace, size_t* workspace_bytes, int device, void* stream) {
+  const char* who = "svt_clip_adam_step";
+  if (n_tensors < 1) { set_error(std::string(who) + ": n_tensors must be at least 1"); return SVT_ERR_INVALID; }
+  if (!numels) { set_error(std::string(who) + ": null argument"); return SVT_ERR_INVALID; }
+  for (int i = 0; i < n_tensors; ++i)
+    if (numels[i] < 0) { set_error(std::string(who) + ": negative numel"); return SVT_ERR_INVALID; }
+  if (adam_chunks(numels, n_tensors) > 2147483647LL) { set_error(std::string(who) + ": more than 2^31 - 1 chunks of 4096 elements"); return SVT_ERR_INVALID; }
+  bool query = false;
+  if (int r = ws_query(who, workspace, workspace_bytes, adam_workspace_bytes(numels, n_tensors), &query)) return r;
+  if (query) return SVT_OK;
+  const bool ams = (flags & SVT_ADAM_AMSGRAD) != 0;
+  if (flags & ~(SVT_ADAM_MAXIMIZE | SVT_ADAM_AMSGRAD | SVT_ADAM_DECOUPLED)) { set_error(std::string(who) + ": unknown flag"); return SVT_ERR_INVALID; }
+  if (!params || !grads || !exp_avg || !exp_avg_sq || !step_size || !bc2_sqrt || (ams && !max_exp_avg_sq)) {
+    set_error(std::string(who) + ": null argument"); return SVT_ERR_INVALID;
+  }
+  if (!ams && max_exp_avg_sq) { set_error(std::string(who) + ": max_exp_avg_sq given without SVT_ADAM_AMSGRAD"); return SVT_ERR_INVALID; }
+  uintptr_t bits = (uintptr_t)total_norm;
+  for (int i = 0; i < n_tensors; ++i) {
+    if (numels[i] == 0) continue;
+    if (!params[i] || !grads[i] || !exp_avg[i] || !exp_avg_sq[i] || (ams && !max_exp_avg_sq[i])) {
+      set_error(std::string(who) + ": null tensor pointer"); return SVT_ERR_INVALID;
+    }
+    bits |= (uintptr_t)params[i] | (uintptr_t)grads[i] | (uintptr_t)exp_avg[i] | (uintptr_t)exp_avg_sq[i] | (ams ? (uintptr_t)max_exp_avg_sq[i] : 0);
+  }
+  if (bits & 3) { set_error(std::string(who) + ": tensors must be 4-byte aligned"); return SVT_ERR_INVALID; }
+  if ((uintptr_t)workspace & 15) { set_error(std::string(who) + ": workspace must be 16-byte aligned"); return SVT_ERR_INVALID; }
+  if (!(lr >= 0.0) || !(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0) || !(eps >= 0.0) || !(weight_decay >= 0.0) ||
+      std::isnan(max_norm)) {
+    set_error(std::string(who) + ": lr, eps and weight_decay must be >= 0 and the betas in [0, 1)"); return SVT_ERR_INVALID;
+  }
+  if (int r = check_device(device)) return r;
+  SVT_HIP(hipSetDevice(device));
+  // torch forms 1 - beta1, 1 - beta2 and 1 - lr * weight_decay as Python floats, i.e. in double before the fp32 operation
+  AdamHyper h{};
+  h.w1 = (float)(1.0 - beta1);
+  h.one_minus_w1 = 1.f - h.w1;
+  h.lerp_far = h.w1 >= 0.5f ? 1 : 0;
+  h.beta2 = (float)beta2;
+  h.one_minus_beta2 = (float)(1.0 - beta2);
+  h.eps = (float)eps;
+  h.weight_decay = (float)weight_decay;
+  h.decay_mul = (float)(1.0 - lr * weight_decay);
+  h.maximize = (flags & SVT_ADAM_MAXIMIZE) ? 1 : 0;
+  h.decoupled = (flags & SVT_ADAM_DECOUPLED) ? 1 : 0;
+  if (launch_clip_adam(n_tensors, params, grads, exp_avg, exp_avg_sq, ams ? max_exp_avg_sq : nullptr, numels, step_size, bc2_sqrt, h,
+                       max_norm, total_norm, workspace, (hipStream_t)stream))
+    return SVT_ERR_HIP;
+  return SVT_OK;
+}
+
 }  // extern "C"

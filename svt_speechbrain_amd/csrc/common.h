@@ -604,6 +604,19 @@ size_t ada_workspace_bytes(const int64_t* numels, int count);
 int launch_clip_adadelta(int count, float* const* params, float* const* grads, float* const* square_avg, float* const* acc_delta,
                          const int64_t* numels, float lr, float rho, float one_minus_rho, float eps, float weight_decay, int maximize,
                          float max_norm, float* total_norm, void* ws, hipStream_t s);
+// clip_grad_norm_ + torch.optim.Adam / AdamW over any number of tensors (adam.hip): the scalars of one call, rounded to fp32 from the
+// host's doubles as torch's scalar arguments are
+struct AdamHyper {
+  float w1, one_minus_w1;   // lerp weight 1 - beta1, and 1 - w1 for torch's branch at w1 >= 0.5
+  float beta2, one_minus_beta2, eps, weight_decay;
+  float decay_mul;          // 1 - lr * weight_decay (the decoupled form's factor)
+  int maximize, decoupled, lerp_far;
+};
+size_t adam_workspace_bytes(const int64_t* numels, int count);
+int64_t adam_chunks(const int64_t* numels, int count);
+int launch_clip_adam(int count, float* const* params, float* const* grads, float* const* exp_avg, float* const* exp_avg_sq,
+                     float* const* max_exp_avg_sq, const int64_t* numels, const float* step_size, const float* bc2_sqrt,
+                     const AdamHyper& h, float max_norm, float* total_norm, void* ws, hipStream_t s);
 // RCA training step (train_rca.hip): weight refresh, attention statistics and backward, LayerNorm backward, weight gradients
 struct RcaRefreshJob {
   const float* src;   // rows x cols fp32

@@ -12,6 +12,10 @@ precomputed, frozen audio and video features, with the RCA layers' backward of `
 
 ``VideoProbe`` is the video recipe's linear-probe step (``N20EMv2/video_only/train_video_ssl.py``): ``LinearProbe`` behind the frozen
 AV-HuBERT encoder on raw uint8 lip ROIs, with the recipe's ``transform_train`` drawn on the host and applied in the padding kernel.
+
+``Adam`` / ``AdamW`` are the recipes' second optimizer class (``wav2vec_opt_class`` / ``encoder_opt_class: torch.optim.Adam``): the
+clip and torch's single-tensor update for a parameter list of any length in one call of ``svt_clip_adam_step`` (``csrc/adam.hip``).
+The three trainers take one as ``optimizer=``; their default stays ``Adadelta``.
 """
 from __future__ import annotations
 
@@ -26,6 +30,7 @@ from .amt import AMTForward
 
 TERMS = ("onset", "offset", "octave", "pitch")
 _MAX_TENSORS = 32   # tensors per svt_clip_adadelta_step call (csrc/common.h kAdaMaxTensors)
+ADAM_MAXIMIZE, ADAM_AMSGRAD, ADAM_DECOUPLED = 1, 2, 4   # svt_clip_adam_step's flags (include/svt_mi355.h)
 
 
 def _workspace(query, device) -> torch.Tensor:
@@ -35,9 +40,9 @@ def _workspace(query, device) -> torch.Tensor:
     return torch.empty(max(16, int(n.value)), dtype=torch.uint8, device=device)
 
 
-def _bump(t: torch.Tensor) -> None:
-    """A kernel wrote ``t`` through its pointer: advance its version counter so every cached upload of it (``Linear._sync``,
-    the fused tail) sees a change."""
+def _bump(t) -> None:
+    """A kernel wrote ``t`` (a tensor or a list of tensors) through its pointer: advance its version counter so every cached upload of
+    it (``Linear._sync``, the fused tail) sees a change."""
     torch.autograd.graph.increment_version(t)
 
 
@@ -75,6 +80,55 @@ def clip_adadelta_step(params, grads, square_avgs, acc_deltas, lr: float, rho: f
     if max_norm > 0:
         for t in grads:
             _bump(t)
+
+
+def clip_adam_step(params, grads, exp_avgs, exp_avg_sqs, max_exp_avg_sqs, step_sizes, bc2_sqrts, lr: float, beta1: float, beta2: float,
+                   eps: float, weight_decay: float = 0.0, maximize: bool = False, decoupled_weight_decay: bool = False,
+                   max_norm: float = 0.0, total_norm: Optional[torch.Tensor] = None, workspace=None, validate: bool = True) -> None:
+    """``clip_grad_norm_(grads, max_norm)`` (when ``max_norm > 0``) then one ``torch.optim.Adam`` update of every parameter, in one call
+    of ``svt_clip_adam_step`` (``csrc/adam.hip``) -- any number of tensors.  ``max_exp_avg_sqs`` is None without amsgrad; ``step_sizes``
+    (``lr / (1 - beta1**step)``) and ``bc2_sqrts`` (``sqrt(1 - beta2**step)``) are Python floats per tensor.  All tensors contiguous fp32
+    on one GPU (views into a flat buffer are fine: any 4-byte-aligned address); ``total_norm`` (0-d fp32 on that GPU) receives the
+    pre-clip norm.  ``workspace`` (a callable ``query -> uint8 tensor``) lets the caller keep the scratch between steps;
+    ``validate=False`` is for a caller that has checked the tensors itself (``Adam.step``: the checks cost host time per tensor)."""
+    dev = params[0].device
+    groups = [params, grads, exp_avgs, exp_avg_sqs] + ([max_exp_avg_sqs] if max_exp_avg_sqs is not None else [])
+    n = len(params)
+    for group in groups if validate else ():
+        if len(group) != n:
+            raise ValueError("clip_adam_step: the tensor lists differ in length")
+        for t, p in zip(group, params):
+            if not t.is_cuda:
+                raise _lib.SvtError("Adam needs its parameters on the GPU; there is no CPU fallback")
+            if t.dtype != torch.float32 or not t.is_contiguous() or t.device != dev:
+                raise _lib.SvtError("Adam: parameters, gradients and state must be contiguous fp32 tensors on one device")
+            if t.numel() != p.numel():
+                raise ValueError("clip_adam_step: a gradient or state tensor differs in size from its parameter")
+    lib = _lib.load()
+    arr = C.c_void_p * n
+    ptrs = [arr(*[t.data_ptr() for t in g]) for g in groups]
+    vmax = ptrs[4] if max_exp_avg_sqs is not None else None
+    numels = (C.c_int64 * n)(*[t.numel() for t in params])
+    ss = (C.c_float * n)(*step_sizes)
+    bc = (C.c_float * n)(*bc2_sqrts)
+    flags = (ADAM_MAXIMIZE if maximize else 0) | (ADAM_AMSGRAD if max_exp_avg_sqs is not None else 0) | \
+        (ADAM_DECOUPLED if decoupled_weight_decay else 0)
+    idx, stream = _lib.dev_index(dev), _lib.stream_ptr(dev)
+
+    def call(ws, nbytes):
+        return lib.svt_clip_adam_step(n, ptrs[0], ptrs[1], ptrs[2], ptrs[3], vmax, numels, ss, bc, float(lr), float(beta1), float(beta2),
+                                      float(eps), float(weight_decay), flags, float(max_norm),
+                                      _lib.ptr(total_norm) if total_norm is not None else None, ws, nbytes, idx, stream)
+
+    def query(nb):
+        _lib.check(call(None, nb), "svt_clip_adam_step")
+
+    ws = workspace(query) if workspace is not None else _workspace(query, dev)
+    nbytes = C.c_size_t(ws.numel())
+    _lib.check(call(_lib.ptr(ws), C.byref(nbytes)), "svt_clip_adam_step")
+    _bump(params)
+    if max_norm > 0:
+        _bump(grads)
 
 
 def amt_objective_grad(logits, onset, offset, octave, pitch_class, rel_len=None, onset_pos_weight: float = 15.0,
@@ -251,6 +305,183 @@ class Adadelta(torch.optim.Optimizer):
         return loss
 
 
+class Adam(torch.optim.Optimizer):
+    """``torch.optim.Adam`` on GPU parameters, updated by the HIP kernels of ``csrc/adam.hip``: the installed torch's constructor,
+    validation and messages, the same ``param_groups`` keys and the same ``state_dict()`` (per parameter ``step`` -- a 0-d fp32 CPU tensor
+    --, ``exp_avg``, ``exp_avg_sq`` and, with amsgrad, ``max_exp_avg_sq``), so a checkpoint moves both ways and a scheduler that sets
+    ``param_groups[i]["lr"]`` works unchanged.  Any number of parameters per call.  ``foreach`` / ``fused`` / ``capturable`` are accepted
+    and stored, and change nothing: there is one implementation.  fp32 parameters only; CPU parameters raise ``SvtError``."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, amsgrad=False, *, foreach=None, maximize=False,
+                 capturable=False, differentiable=False, fused=None, decoupled_weight_decay=False):
+        Tensor = torch.Tensor
+        if isinstance(lr, Tensor):
+            if foreach and not capturable:
+                raise ValueError("lr as a Tensor is not supported for capturable=False and foreach=True")
+            if lr.numel() != 1:
+                raise ValueError("Tensor lr must be 1-element")
+        if not 0.0 <= lr:
+            raise ValueError(f"Invalid learning rate: {lr}")
+        if not 0.0 <= eps:
+            raise ValueError(f"Invalid epsilon value: {eps}")
+        if not 0.0 <= betas[0] < 1.0:
+            raise ValueError(f"Invalid beta parameter at index 0: {betas[0]}")
+        if not 0.0 <= betas[1] < 1.0:
+            raise ValueError(f"Invalid beta parameter at index 1: {betas[1]}")
+        if not 0.0 <= weight_decay:
+            raise ValueError(f"Invalid weight_decay value: {weight_decay}")
+        if not ((isinstance(betas[0], float) and isinstance(betas[1], float))
+                or (isinstance(betas[0], Tensor) and isinstance(betas[1], Tensor))):
+            raise ValueError("betas must be either both floats or both Tensors")
+        for i in (0, 1):
+            if isinstance(betas[i], Tensor):
+                if not capturable and foreach:
+                    raise ValueError(f"betas[{i}] as a Tensor is not supported for capturable=False and foreach=True")
+                if betas[i].numel() != 1:
+                    raise ValueError(f"Tensor betas[{i}] must be 1-element")
+        betas = tuple(b.item() if isinstance(b, Tensor) else b for b in betas)
+        if differentiable:
+            raise NotImplementedError(f"{type(self).__name__}: differentiable=True is not provided (the update is a HIP kernel)")
+        if fused and foreach:
+            raise RuntimeError("`fused` and `foreach` cannot be `True` together.")
+        defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=amsgrad, maximize=maximize, foreach=foreach,
+                        capturable=capturable, differentiable=differentiable, fused=fused, decoupled_weight_decay=decoupled_weight_decay)
+        super().__init__(params, defaults)
+        self._ws: Dict[torch.device, torch.Tensor] = {}
+        self._seen: dict = {}         # parameter -> the state tensors that were checked (_group_tensors)
+        self._step_views: dict = {}   # id(step tensor) -> (the tensor, its numpy view) (_advance)
+
+    def __setstate__(self, state):
+        super().__setstate__(state)
+        for name in ("_ws", "_seen", "_step_views"):   # not part of the pickled state
+            self.__dict__[name] = {}
+        for group in self.param_groups:
+            group.setdefault("amsgrad", False)
+            group.setdefault("maximize", False)
+            group.setdefault("foreach", None)
+            group.setdefault("capturable", False)
+            group.setdefault("differentiable", False)
+            group.setdefault("decoupled_weight_decay", False)
+            group.setdefault("fused", None)
+            for p in group["params"]:
+                p_state = self.state.get(p, [])
+                if len(p_state) != 0 and not torch.is_tensor(p_state["step"]):
+                    p_state["step"] = torch.tensor(float(p_state["step"]), dtype=torch.float32)
+
+    def _scratch(self, query, device) -> torch.Tensor:
+        n = C.c_size_t(0)
+        query(n)
+        ws = self._ws.get(device)
+        if ws is None or ws.numel() < int(n.value):
+            ws = torch.empty(max(16, int(n.value)), dtype=torch.uint8, device=device)
+            self._ws[device] = ws
+        return ws
+
+    def _group_tensors(self, group):
+        """The tensors of the parameters that have a gradient, checked: parameters and gradients at every step, the state tensors when
+        they are first seen (``_seen`` keeps them by identity, so a state replaced by ``load_state_dict`` or by hand is checked again)."""
+        params, grads, avgs, sqs, maxs, steps = [], [], [], [], [], []
+        name, ams, seen, dev, f32 = type(self).__name__, group["amsgrad"], self._seen, None, torch.float32
+        for p in group["params"]:
+            g = p.grad
+            if g is None:
+                continue
+            if g.is_sparse:
+                raise RuntimeError("Adam does not support sparse gradients, please consider SparseAdam instead")
+            if not p.is_cuda:
+                raise _lib.SvtError(f"svt_speechbrain_amd.{name} needs its parameters on the GPU; there is no CPU fallback")
+            if dev is None:
+                dev = p.device
+            if not g.is_contiguous():
+                g = g.contiguous()
+            if p.dtype is not f32 or g.dtype is not f32 or not p.is_contiguous() or p.device != dev or g.device != dev or g.numel() != p.numel():
+                raise _lib.SvtError(f"{name}: parameters and gradients must be contiguous fp32 tensors of equal size on one device")
+            state = self.state[p]
+            if len(state) == 0:
+                state["step"] = torch.tensor(0.0, dtype=torch.float32)
+                state["exp_avg"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
+                state["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
+                if ams:
+                    state["max_exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
+            m, v, x = state["exp_avg"], state["exp_avg_sq"], state["max_exp_avg_sq"] if ams else None
+            was = seen.get(p)
+            if was is None or was[0] is not m or was[1] is not v or was[2] is not x:
+                for t in (m, v) + ((x,) if ams else ()):
+                    if t.dtype is not f32 or not t.is_contiguous() or t.device != dev or t.numel() != p.numel():
+                        raise _lib.SvtError(f"{name}: the state of a parameter must be contiguous fp32 tensors of its size on its device")
+                seen[p] = (m, v, x)
+            params.append(p)
+            grads.append(g)
+            avgs.append(m)
+            sqs.append(v)
+            if ams:
+                maxs.append(x)
+            steps.append(state["step"])
+        return params, grads, avgs, sqs, maxs, steps
+
+    def _advance(self, steps):
+        """``step += 1`` of every 0-d fp32 step tensor and its new value as a Python float.  A CPU step tensor is written through a numpy
+        view kept by identity: 400 tensor operations a step cost more host time than the kernels take."""
+        views, out = self._step_views, []
+        for st in steps:
+            v = views.get(id(st))
+            if v is None or v[0] is not st:
+                if st.device.type != "cpu" or st.dtype is not torch.float32:   # a state loaded from a fused / capturable torch optimizer
+                    st += 1
+                    out.append(float(st))
+                    continue
+                v = views[id(st)] = (st, st.numpy())
+            k = float(v[1]) + 1.0
+            v[1][()] = k
+            out.append(k)
+        return out
+
+    def load_state_dict(self, state_dict):
+        super().load_state_dict(state_dict)
+        self._seen.clear()
+        self._step_views.clear()
+
+    @torch.no_grad()
+    def step(self, closure=None, max_norm: float = 0.0, total_norm: Optional[torch.Tensor] = None):
+        """One Adam update.  ``max_norm > 0`` (extension) first clips the gradients of ALL parameters of the optimizer by their global
+        norm as ``clip_grad_norm_`` does, in the same kernel call (one param group, any number of tensors).  Parameters whose ``grad``
+        is None are skipped and keep their ``step``; the bias corrections are therefore formed per parameter, in double, as torch's
+        single-tensor path forms them."""
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        if max_norm > 0 and len(self.param_groups) != 1:
+            raise NotImplementedError(f"{type(self).__name__}.step(max_norm=...): one param group only")
+        for group in self.param_groups:
+            params, grads, avgs, sqs, maxs, steps = self._group_tensors(group)
+            if not params:
+                continue
+            beta1, beta2 = (float(b) for b in group["betas"])
+            lr = float(group["lr"])
+            ks = self._advance(steps)
+            bias = {k: (lr / (1 - beta1 ** k), (1 - beta2 ** k) ** 0.5) for k in set(ks)}
+            dev = params[0].device
+            clip_adam_step(params, grads, avgs, sqs, maxs if group["amsgrad"] else None, [bias[k][0] for k in ks], [bias[k][1] for k in ks],
+                           lr, beta1, beta2, group["eps"], group["weight_decay"], group["maximize"], group["decoupled_weight_decay"],
+                           max_norm, total_norm, workspace=lambda q: self._scratch(q, dev), validate=False)
+        return loss
+
+
+class AdamW(Adam):
+    """``torch.optim.AdamW``: ``Adam`` with ``decoupled_weight_decay=True`` and torch's default ``weight_decay=1e-2``."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, amsgrad=False, *, maximize=False, foreach=None,
+                 capturable=False, differentiable=False, fused=None):
+        super().__init__(params, lr, betas, eps, weight_decay, amsgrad, foreach=foreach, maximize=maximize, capturable=capturable,
+                         differentiable=differentiable, fused=fused, decoupled_weight_decay=True)
+
+    def __setstate__(self, state):
+        super().__setstate__(state)
+        for group in self.param_groups:
+            group["decoupled_weight_decay"] = True
+
+
 class LinearProbe:
     """``AMT.fit_batch`` of the linear-probe stage with the encoder frozen (``train_audio_ssl.py:28-76`` + ``Brain.fit_batch`` /
     ``check_gradients``, ``speechbrain/core.py:850-923``).  ``modules`` is the recipe's mapping (``wav2vec2`` + ``model``, as for
@@ -262,7 +493,7 @@ class LinearProbe:
     ``head(...)`` or fused tail uploads them).  A non-finite loss skips the step (gradients set to None, parameters untouched); the
     ``nonfinite_patience + 1``-th skip since ``on_epoch_start()`` raises ``ValueError``, as ``check_gradients`` does."""
 
-    def __init__(self, modules, optimizer: Optional[Adadelta] = None, lr: float = 3e-4, rho: float = 0.95, eps: float = 1e-8,
+    def __init__(self, modules, optimizer: Optional[torch.optim.Optimizer] = None, lr: float = 3e-4, rho: float = 0.95, eps: float = 1e-8,
                  onset_positive_weight: float = 15.0, pitch_octave_num: int = 4, pitch_class_num: int = 12, max_grad_norm: float = 5.0,
                  nonfinite_patience: int = 3, allowed_len_diff: int = 3, label_smoothing: float = 0.0):
         self.amt = AMTForward(modules, pitch_octave_num=pitch_octave_num, pitch_class_num=pitch_class_num)
@@ -276,8 +507,8 @@ class LinearProbe:
         self.label_smoothing = float(label_smoothing)
         if optimizer is None:
             optimizer = Adadelta(self.head.parameters(), lr=lr, rho=rho, eps=eps)
-        if not isinstance(optimizer, Adadelta):
-            raise TypeError("LinearProbe needs svt_speechbrain_amd.training.Adadelta (the clip is fused into its kernel)")
+        if not isinstance(optimizer, (Adadelta, Adam)):
+            raise TypeError("LinearProbe needs svt_speechbrain_amd.training.Adadelta, Adam or AdamW (the clip is fused into their kernels)")
         self.optimizer = optimizer
         self.nonfinite_count = 0
         self.last_terms: Dict[str, float] = {}
@@ -432,7 +663,7 @@ class FusionTrainer:
     ``fusion(a, v)`` uploads nothing through the host.  A non-finite loss skips the step (gradients set to None, parameters
     untouched); the ``nonfinite_patience + 1``-th skip since ``on_epoch_start()`` raises ``ValueError``."""
 
-    def __init__(self, modules, optimizer: Optional[Adadelta] = None, lr: float = 3e-4, rho: float = 0.95, eps: float = 1e-8,
+    def __init__(self, modules, optimizer: Optional[torch.optim.Optimizer] = None, lr: float = 3e-4, rho: float = 0.95, eps: float = 1e-8,
                  onset_positive_weight: float = 15.0, pitch_octave_num: int = 4, pitch_class_num: int = 12, max_grad_norm: float = 5.0,
                  nonfinite_patience: int = 3, allowed_len_diff: int = 3, label_smoothing: float = 0.0):
         from .fusion import FusionRCA
@@ -459,8 +690,8 @@ class FusionTrainer:
         self.label_smoothing = float(label_smoothing)
         if optimizer is None:
             optimizer = Adadelta(list(self.fusion.parameters()) + list(self.head.parameters()), lr=lr, rho=rho, eps=eps)
-        if not isinstance(optimizer, Adadelta):
-            raise TypeError("FusionTrainer needs svt_speechbrain_amd.training.Adadelta (the clip is fused into its kernel)")
+        if not isinstance(optimizer, (Adadelta, Adam)):
+            raise TypeError("FusionTrainer needs svt_speechbrain_amd.training.Adadelta, Adam or AdamW (the clip is fused into their kernels)")
         self.optimizer = optimizer
         self.nonfinite_count = 0
         self.last_terms: Dict[str, float] = {}
