@@ -152,8 +152,13 @@ int svt_encoder_set_spec_augment(svt_encoder* enc, const uint8_t* time_mask_dev,
  * (sites 0 and 1: layer = 0).  No parity with the masks torch's device generator would draw is claimed: those depend on torch's launch
  * geometry.  Where the residual stream is stored twice (an fp32 copy beside the operand copy) both copies receive the same mask; the
  * bf16 (hi, lo) stream has its value float(hi) + float(lo) scaled or zeroed and is cut again (hi' = T(o), lo' = T(o - hi')).
- * With attention_dropout > 0 the attention takes the score-matrix path for every geometry (the fused kernels have no mask), whose
- * score and probability buffers svt_encoder_workspace_bytes counts ONLY while such a state is set: set the state BEFORE the size query.
+ * With attention_dropout > 0 the attention takes the score-matrix path for every geometry by default, whose score and probability
+ * buffers svt_encoder_workspace_bytes counts ONLY while such a state is set: set the state BEFORE the size query.  fused_attention != 0
+ * opts in to the fused attention with the mask inside (csrc/attention_drop.hip, flash_attn_drop_kernel): where the plain forward runs a
+ * fused 16-bit kernel (SVT_PREC_BF16, head size 64 or 128, no position bias) the masked forward then runs its masked form -- the same
+ * mask bit for bit, the row sum over all keys, the scale folded into the final division -- and the workspace is the plain forward's (no
+ * score or probability buffers); every other geometry and precision runs the score-matrix path exactly as with 0.  The default stays 0
+ * so that a forward recorded at a (seed, step) replays bit for bit: the two forms round the probabilities in different places.
  * With hidden_dropout > 0 FFN-2 takes its un-split form.  skip_mask: bit l set = layer l is skipped and launches nothing (HF's
  * layerdrop; the caller draws -- torch.rand([]) < layerdrop per layer, in layer order); `layerdrop` itself is only recorded.
  * The state is sticky on the handle; NULL clears it, and the forward is then the plain one: no launch added, no kernel changed.
@@ -161,7 +166,9 @@ int svt_encoder_set_spec_augment(svt_encoder* enc, const uint8_t* time_mask_dev,
  * rate above 0 in a split-operand precision (SVT_PREC_BF16X3 / SVT_PREC_FP16X3 serve layerdrop only: their activations travel as
  * pair rows, which these kernels do not read), attention_dropout > 0 with a relative position bias (WavLM: the reference runs torch's
  * fused multi-head attention there, which offers no seam to pin a mask against), layer 0 of such an encoder skipped while a later layer runs (the
- * reference cannot: only layer 0 holds the position embedding). */
+ * reference cannot: only layer 0 holds the position embedding).
+ * struct_size: the size of this structure, or that of its form without fused_attention (the first 64 bytes: callers built before the
+ * field existed), which means fused_attention = 0; every other size is refused. */
 typedef struct svt_dropout {
   int32_t struct_size;
   uint32_t step;
@@ -172,6 +179,8 @@ typedef struct svt_dropout {
   double layerdrop;
   uint64_t seed;
   uint64_t skip_mask;
+  int32_t fused_attention;
+  int32_t reserved;   /* padding; ignored */
 } svt_dropout;
 int svt_encoder_set_dropout(svt_encoder* enc, const svt_dropout* state);
 /* copy one parameter by its HF state-dict key (without the wrapper's "model." prefix); both weight-norm
@@ -776,6 +785,36 @@ int svt_debug_attention(int32_t precision, const void* q, const void* k, const v
 int svt_debug_attention_bias(const void* q, const void* k, const void* v, void* o, int32_t batch, int32_t t, int32_t heads, int64_t ldq,
                              int64_t ldkv, int64_t ldo, float scale, const float* gate_dev, const float* pos_bias_dev, int device,
                              void* stream);
+/* The fused attention with the dropout mask inside (csrc/attention_drop.hip), ONE launch of launch_flash_attention_dropout on caller
+ * buffers: o = (keep * float(1 / (1 - p)) * softmax(scale q k^T)) v in HF's eager order (softmax -> dropout -> . v; the row sum runs
+ * over all keys), operands and strides as for svt_debug_attention (16-bit q / k / v / o of the build's operand type).  Element
+ * (b, h, i, j) of the probabilities has the logical index e0 + ((b*heads + h)*t + i)*t + j and is kept by svt_dropout's rule for site 2
+ * of `layer` at (seed, step); e0 lets a small case reach q_hi != 0 and every alignment of the four-word groups.  precision must be
+ * SVT_PREC_BF16 and head_dim 64 or 128, p in [0, 1): anything else is refused (SVT_ERR_INVALID) and nothing is launched.
+ * svt_debug_set(38, 0) says which kernel ran.  struct_size = the size of the structure.  tests/test_gpu_attention_dropout.py */
+typedef struct svt_debug_attention_dropout_desc {
+  int32_t struct_size;
+  int32_t precision;
+  const void* q;
+  const void* k;
+  const void* v;
+  void* o;
+  int64_t ldq;
+  int64_t ldkv;
+  int64_t ldo;
+  int32_t batch;
+  int32_t t;
+  int32_t heads;
+  int32_t head_dim;
+  float scale;
+  uint32_t step;
+  double p;
+  uint64_t seed;
+  int32_t layer;
+  int32_t reserved;
+  uint64_t e0;
+} svt_debug_attention_dropout_desc;
+int svt_debug_attention_dropout(const svt_debug_attention_dropout_desc* d, int device, void* stream);
 /* The score-matrix attention alone (tests/test_gpu_attention_scores.py): what every attention outside the fused kernels' reach runs --
  * the fp32 parity mode, 16-bit head sizes other than 64 / 128, WavLM's biased attention at head size 128 or 2 t - 1 > 8192, WavLM in the
  * split-operand modes.  Two batched products (scale q k^T into fp32 scores with rows padded to a multiple of 8 keys, P V) around the
@@ -832,7 +871,9 @@ int svt_debug_rca_attn_bwd(int32_t precision, const void* qkv, const void* qc, c
  * this process chose (value ignored; 0 = none yet): 1 = flash_attn_kernel<64>, 2 = flash_attn_kernel<128>, 3 = flash_attn_stag_kernel<64>
  * (head_dim 64, "wide" launches), 4 = flash_attn_kernel<64, true> (position bias), 5 = flash_attn_kernel<64, true, 8> (position bias,
  * wide), 6 = flash_attn_x3_kernel<64, .>, 7 = flash_attn_x3_kernel<128, .>, 8 = flash_attn_x3_stag_kernel<.> (split-operand modes;
- * tests/test_gpu_attention.py asserts the id of every case), 39 = query: svt_debug_set(39, 0) returns which kernel the last dense product of this
+ * tests/test_gpu_attention.py asserts the id of every case), 9 = flash_attn_drop_kernel<64, 4>, 10 = flash_attn_drop_kernel<128, 4>
+ * (the dropout mask inside; tests/test_gpu_attention_dropout.py), 11 = not assigned (kept for an eight-wave flash_attn_drop_kernel<64, 8>,
+ * which is not built: DESIGN.md section 4.51), 39 = query: svt_debug_set(39, 0) returns which kernel the last dense product of this
  * process ran on (value ignored; 0 = none yet) as 1000 * family + tile rows: family 1 = gemm_skinny_kernel (32 / 64), 2 = the register-staged
  * gemm_kernel (128, or 256 for its 256 x 64 form; + 10000 for a split-operand instantiation), 3 = gemm_pp8_kernel (64 / 128 / 192 /
  * 256), 4 = gemm_pers_kernel, 5 = gemm_pps_kernel, 6 = gemm_p1w_kernel, 7 = gemm_x3s_kernel (256; 192 names its 192-column form),

@@ -95,12 +95,29 @@ class LayerNormDescC(C.Structure):
 
 
 class DropoutC(C.Structure):
-    """svt_dropout: the training-mode state of svt_encoder_set_dropout -- five rates, (seed, step) of the mask function, skipped layers."""
+    """svt_dropout: the training-mode state of svt_encoder_set_dropout -- five rates, (seed, step) of the mask function, skipped layers,
+    and the opt-in to the fused attention with the mask inside (fused_attention; the structure without its last 8 bytes is accepted
+    and means 0)."""
     _fields_ = [
         ("struct_size", C.c_int32), ("step", C.c_uint32),
         ("feat_proj_dropout", C.c_double), ("hidden_dropout", C.c_double), ("attention_dropout", C.c_double),
         ("activation_dropout", C.c_double), ("layerdrop", C.c_double),
         ("seed", C.c_uint64), ("skip_mask", C.c_uint64),
+        ("fused_attention", C.c_int32), ("reserved", C.c_int32),
+    ]
+
+
+class AttentionDropoutDescC(C.Structure):
+    """svt_debug_attention_dropout_desc: one launch of the fused attention with the dropout mask inside (svt_debug_attention_dropout)."""
+    _fields_ = [
+        ("struct_size", C.c_int32), ("precision", C.c_int32),
+        ("q", C.c_void_p), ("k", C.c_void_p), ("v", C.c_void_p), ("o", C.c_void_p),
+        ("ldq", C.c_int64), ("ldkv", C.c_int64), ("ldo", C.c_int64),
+        ("batch", C.c_int32), ("t", C.c_int32), ("heads", C.c_int32), ("head_dim", C.c_int32),
+        ("scale", C.c_float), ("step", C.c_uint32),
+        ("p", C.c_double), ("seed", C.c_uint64),
+        ("layer", C.c_int32), ("reserved", C.c_int32),
+        ("e0", C.c_uint64),
     ]
 
 
@@ -208,6 +225,7 @@ SYMBOLS = {
     "svt_encoder_set_spec_augment": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32]),
     "svt_encoder_set_dropout": (C.c_int, [_P, C.POINTER(DropoutC)]),
     "svt_debug_dropout": (C.c_int, [C.POINTER(DropoutDescC), C.c_int, _P]),
+    "svt_debug_attention_dropout": (C.c_int, [C.POINTER(AttentionDropoutDescC), C.c_int, _P]),
     "svt_wav_parse": (C.c_int, [_P, C.c_int64, C.c_int64, C.POINTER(WavInfoC), _I64P]),
     "svt_wav_header": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int64, _P, C.c_int64, _I64P]),
     "svt_pcm_decode": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int64, _P, C.c_int64, C.c_int32, C.c_int, _P]),

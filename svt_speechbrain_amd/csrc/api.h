@@ -75,13 +75,14 @@ static inline int storage_prec(int precision) { return precision >= 2 ? 0 : prec
 
 // out[b,t,h*dh+d] = softmax(scale * q k^T) v (api.hip): the fused kernels where they apply, else the materialised scores.
 // pdrop (training-mode attention dropout, site 2): the materialised scores for EVERY geometry, with the mask on the probabilities
-// (launch_softmax_dropout; element ((b*H + h)*T + i)*T + j); null: the plain path
+// (launch_softmax_dropout; element ((b*H + h)*T + i)*T + j); null: the plain path.  fused_drop (svt_dropout.fused_attention): with
+// pdrop, a geometry the plain fused 16-bit kernels serve runs their masked form instead (launch_flash_attention_dropout), the rest as before
 bool use_flash(int prec, int dh, bool bias = false, int64_t T = 0);
 int attn_tp(int prec, int dh, int T, bool bias = false);
 int attention_scores_path(int prec, const void* Q, long ldq, const void* K, const void* V, long ldkv, int B,
                           int T, int H, int dh, float scale, const AttnBufs& ab, bool vt_ready, void* out,
                           long ldo, hipStream_t s, const float* gate = nullptr, const float* relpb = nullptr,
-                          int gp = -1, int o_pairs = 0, const DropSpec* pdrop = nullptr);
+                          int gp = -1, int o_pairs = 0, const DropSpec* pdrop = nullptr, bool fused_drop = false);
 
 // a gfx950 device of this index exists; it becomes the current device
 int check_device(int device);

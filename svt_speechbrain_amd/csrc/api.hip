@@ -214,7 +214,8 @@ int attn_tp(int prec, int dh, int T, bool bias) {
 
 int attention_scores_path(int prec, const void* Q, long ldq, const void* K, const void* V, long ldkv, int B,
                           int T, int H, int dh, float scale, const AttnBufs& ab, bool vt_ready, void* out,
-                          long ldo, hipStream_t s, const float* gate, const float* relpb, int gp, int o_pairs, const DropSpec* pdrop) {
+                          long ldo, hipStream_t s, const float* gate, const float* relpb, int gp, int o_pairs, const DropSpec* pdrop,
+                          bool fused_drop) {
   if (gp < 0) gp = prec;
   if (gp >= 2 && !pdrop && !gate && flash_attention_x3_ok(dh) && ab.pl_qkv && ldkv == 3L * H * dh &&
       (const float*)V == (const float*)K + (long)H * dh) {
@@ -243,6 +244,9 @@ int attention_scores_path(int prec, const void* Q, long ldq, const void* K, cons
     return launch_flash_attention(Q, ldq, (long)T * ldq, K, V, ldkv, (long)T * ldkv, out, ldo, (long)T * ldo, B, T, H, dh,
                                   scale, s, gate, gate ? relpb : nullptr);
   }
+  if (pdrop && fused_drop && !gate && use_flash(prec, dh, /*bias*/ false, T))
+    return launch_flash_attention_dropout(Q, ldq, (long)T * ldq, K, V, ldkv, (long)T * ldkv, out, ldo, (long)T * ldo, B, T, H, dh, scale,
+                                          0, *pdrop, s);
   const int Tp = round_up_int(T, 8);
   GemmArgs g;
   g.A = Q; g.W = K; g.C = ab.S;
@@ -609,6 +613,25 @@ int svt_debug_attention(int32_t precision, const void* q, const void* k, const v
   }
   if (launch_flash_attention(q, ldq, (long)t * ldq, k, v, ldkv, (long)t * ldkv, o, ldo, (long)t * ldo, batch, t, heads,
                              head_dim, scale, (hipStream_t)stream)) return SVT_ERR_INVALID;
+  return SVT_OK;
+}
+
+int svt_debug_attention_dropout(const svt_debug_attention_dropout_desc* d, int device, void* stream) {
+  auto refuse = [](const char* why) { set_error(std::string("svt_debug_attention_dropout: ") + why); return SVT_ERR_INVALID; };
+  if (!d) return refuse("null descriptor");
+  if (d->struct_size != (int32_t)sizeof(svt_debug_attention_dropout_desc)) return refuse("struct_size");
+  if (!d->q || !d->k || !d->v || !d->o) return refuse("null argument");
+  if (d->batch < 1 || d->t < 1 || d->heads < 1) return refuse("batch, t and heads must be positive");
+  if (!use_flash(d->precision, d->head_dim, false, d->t))
+    return refuse("the fused kernel serves precision SVT_PREC_BF16 (the build's 16-bit operand type) at head_dim 64 / 128 only");
+  if (!(d->p >= 0.0 && d->p < 1.0)) return refuse("p must lie in [0, 1)");
+  if (d->layer < 0 || d->layer > 0xFFFFFF) return refuse("layer");
+  if (int r = check_device(device)) return r;
+  SVT_HIP(hipSetDevice(device));
+  const DropSpec spec = make_drop_spec(d->p, d->seed, d->step, 2, d->layer);
+  if (launch_flash_attention_dropout(d->q, d->ldq, (long)d->t * d->ldq, d->k, d->v, d->ldkv, (long)d->t * d->ldkv, d->o, d->ldo,
+                                     (long)d->t * d->ldo, d->batch, d->t, d->heads, d->head_dim, d->scale, d->e0, spec,
+                                     (hipStream_t)stream)) return SVT_ERR_INVALID;
   return SVT_OK;
 }
 

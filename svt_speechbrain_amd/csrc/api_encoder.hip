@@ -310,7 +310,9 @@ int svt_encoder_set_dropout(svt_encoder* e, const svt_dropout* st) {
   auto refuse = [](const std::string& why) { set_error("svt_encoder_set_dropout: " + why); return SVT_ERR_INVALID; };
   if (!e) return refuse("null encoder");
   if (!st) { e->drop_on = false; e->drop = svt_dropout{}; return SVT_OK; }
-  if (st->struct_size != (int32_t)sizeof(svt_dropout)) return refuse("struct_size");
+  // the structure as it was before fused_attention was appended is accepted and means 0
+  const bool old_size = st->struct_size == (int32_t)offsetof(svt_dropout, fused_attention);
+  if (!old_size && st->struct_size != (int32_t)sizeof(svt_dropout)) return refuse("struct_size");
   const svt_encoder_config& c = e->cfg;
   const double rates[5] = {st->feat_proj_dropout, st->hidden_dropout, st->attention_dropout, st->activation_dropout, st->layerdrop};
   for (double r : rates)
@@ -329,7 +331,9 @@ int svt_encoder_set_dropout(svt_encoder* e, const svt_dropout* st) {
   if ((st->skip_mask & 1) && c.rel_pos_buckets > 0 && (st->skip_mask & all_layers) != all_layers)
     return refuse("layer 0 of an encoder with a relative position bias (WavLM) cannot be skipped: only that layer holds the position "
                   "embedding, and the reference fails in the next layer");
-  e->drop = *st;
+  e->drop = svt_dropout{};
+  memcpy(&e->drop, st, (size_t)st->struct_size);
+  e->drop.struct_size = (int32_t)sizeof(svt_dropout);
   e->drop_on = true;
   return SVT_OK;
 }
@@ -407,7 +411,8 @@ struct EncPlan {
   bool pos_multi = false;  // this batch has enough rows for the multi-frame form
   bool hilo = false;       // post-LN encoder with the residual stream as a bf16 (hi, lo) pair
   bool ksplit_ws = false;  // few enough rows for the K-split FFN-2: its partial products get workspace
-  bool attn_drop = false;  // training mode with attention_dropout > 0: the score-matrix attention for every geometry
+  bool attn_drop = false;  // training mode with attention_dropout > 0: the score-matrix attention for every geometry, unless ...
+  bool attn_fused_drop = false;  // ... svt_dropout.fused_attention opted in and the plain forward runs a fused 16-bit kernel: its masked form
 };
 
 // false: the waveform is shorter than the receptive field
@@ -424,9 +429,10 @@ bool plan_encoder(const svt_encoder* e, int B, int64_t L, EncPlan* out) {
   p.sp = storage_prec(c.precision); p.gp = c.precision; p.reduced = reduced_mode(c);
   p.rel = c.rel_pos_buckets > 0;
   p.attn_drop = e->drop_on && e->drop.attention_dropout > 0;
-  p.flash = !p.attn_drop && use_flash(p.sp, p.dh, p.rel, p.T);
+  p.attn_fused_drop = p.attn_drop && e->drop.fused_attention != 0 && !p.rel && use_flash(p.sp, p.dh, /*bias*/ false, p.T);
+  p.flash = (!p.attn_drop || p.attn_fused_drop) && use_flash(p.sp, p.dh, p.rel, p.T);
   p.planes = p.gp >= 2 && flash_attention_x3_ok(p.dh) && !p.rel;
-  p.attn_Tp = p.attn_drop ? round_up_int((int)p.T, 8) : attn_tp(p.sp, p.dh, (int)p.T, p.rel);
+  p.attn_Tp = p.attn_drop && !p.attn_fused_drop ? round_up_int((int)p.T, 8) : attn_tp(p.sp, p.dh, (int)p.T, p.rel);
   p.Pf = e->pos_P;
   p.pos_Tq = p.Pf ? (p.T + p.Pf - 1) / p.Pf : 0;
   p.pos_Tp = p.Pf ? p.pos_Tq * p.Pf + c.pos_conv_kernel : p.T + c.pos_conv_kernel;
@@ -901,7 +907,7 @@ int attention_block(const EncRun& x, const EncLayerW& Lw, const LayerForm& f, in
   if (int r = attention_scores_path(p.sp, w.qkv, 3L * D, (const char*)w.qkv + (size_t)D * esize(p.sp),
                                     (const char*)w.qkv + (size_t)2 * D * esize(p.sp), 3L * D, p.B, (int)p.T, p.H, p.dh,
                                     1.0f / std::sqrt((float)p.dh), w.ab, p.planes, w.attn_o, D, x.s, gate, w.relpb, p.gp, x.pk_enc ? 1 : 0,
-                                    p.attn_drop ? &ad : nullptr)) return r;
+                                    p.attn_drop ? &ad : nullptr, p.attn_fused_drop)) return r;
   // (rounds 1-2 fused this projection with the residual add and the LayerNorm in one row-complete kernel, 44 us against 29 + 23; with
   //  the projection on gemm_pps_kernel the pair costs 20.6 + 23.9 us and the fused kernel -- every workgroup streaming all of W,
   //  0.16 of the matrix pipe -- is gone: C2 6 093-6 110 against 6 066-6 074 clips/s on one box)

@@ -228,6 +228,56 @@ __device__ __forceinline__ void attn_block_map(int nqb, int& bh, int& qblk) {
         }                                                                                                                     \
   }
 
+// ---- training-mode dropout on the probabilities (attention_drop.hip; the mask function: philox.h, which the kernel file includes) ----
+// Element (b, h, i, j) of the (B, H, T, T) probabilities has the LOGICAL index e = E0 + ((b*H + h)*T + i)*T + j and is kept iff word e & 3
+// of its four-element group e >> 2 reaches the threshold.  A tile's 64 keys of one query are 64 consecutive elements: 16 groups when the
+// row's first element is a multiple of 4, else 17.  Lanes l and l ^ 32 hold the same query (runs of four keys at 8k and 8k + 4), so the
+// pair splits the groups -- lanes 0-31 compute groups 0..7 of the tile, lanes 32-63 groups 8..16 -- turns each word into one keep bit and
+// exchanges the bits, not the words: two half exchanges (v_permlane32_swap: groups 0..15, then group 16) per tile give both lanes the
+// row's 68 bits, of which a lane reads the 60 from its first key on.  Nine Philox
+// calls per lane and tile at any alignment (a naive lane needs two calls per run: 16), eight when every row of the wave is aligned.
+//
+// Declares the lane's constants: drow = index of (b, h, i = q0 + (lane & 31), key 0); dg0 = the first group this lane computes in tile 0;
+// dsh = the bit of the lane's first key in the row's bits (alignment of the row + 4 for the upper lane); dninth = some row of the wave
+// is unaligned (wave-uniform).  Rows past T get indices of their own that nobody reads.
+#define SVT_ATTN_DROP_ROW(E0)                                                                                                 \
+  const uint64_t drow = (E0) + ((uint64_t)((long)b * H + h) * (uint64_t)T + (uint64_t)(q0 + (lane & 31))) * (uint64_t)T;      \
+  const uint64_t dg0 = (drow >> 2) + (uint64_t)(8 * hh);                                                                      \
+  const unsigned dsh = (unsigned)(drow & 3) + 4u * (unsigned)hh;                                                              \
+  const bool dninth = __any((int)(drow & 3) != 0);
+
+// Zeroes the dropped probabilities of tile TILE in s (after the row sum took them, before P is cut to 16 bits); D: the DropSpec.
+// Bit n of (dw0, dw1) is the keep bit of the lane's key kb*32 + 8*(r>>2) + (r&3) with n = that number: the key map of SVT_ATTN_SOFTMAX_HEAD
+// less the lane's 4*hh, which dsh holds.  Keys >= T have p = 0 already; their bits belong to other rows and change nothing.
+#define SVT_ATTN_DROP(TILE, D)                                                                                                \
+  {                                                                                                                           \
+    const uint64_t dg = dg0 + (uint64_t)(TILE) * 16;                                                                          \
+    unsigned mlo = 0, mhi = 0;                                                                                                \
+    _Pragma("unroll") for (int cc = 0; cc < 8; ++cc) {                                                                        \
+      const Philox4 pw = drop_words((D), dg + cc);                                                                            \
+      _Pragma("unroll") for (int k = 0; k < 4; ++k) mlo |= (unsigned)(pw.w[k] >= (D).thr) << (4 * cc + k);                    \
+    }                                                                                                                         \
+    if (dninth) {  /* wave-uniform: group 16 of the row, which an unaligned row's last keys reach (lanes 32-63; 0-31: unread) */ \
+      const Philox4 pw = drop_words((D), dg + 8);                                                                             \
+      _Pragma("unroll") for (int k = 0; k < 4; ++k) mhi |= (unsigned)(pw.w[k] >= (D).thr) << k;                               \
+    }                                                                                                                         \
+    /* swap(x, x): element 0 = the lower lane's x in both lanes of a pair, element 1 = the upper lane's */                    \
+    const auto x0 = __builtin_amdgcn_permlane32_swap(mlo, mlo, false, false);                                                 \
+    const auto x1 = __builtin_amdgcn_permlane32_swap(mhi, mhi, false, false);                                                 \
+    const unsigned dw0 = __builtin_amdgcn_alignbit(x0[1], x0[0], dsh);   /* bits dsh .. dsh + 31 of the row's 68 */           \
+    const unsigned dw1 = __builtin_amdgcn_alignbit(x1[1], x0[1], dsh);   /* bits dsh + 32 .. dsh + 63 */                      \
+    _Pragma("unroll") for (int kb = 0; kb < 2; ++kb)                                                                          \
+      _Pragma("unroll") for (int r = 0; r < 16; ++r) {                                                                        \
+        const int bit = 8 * (r >> 2) + (r & 3);                                                                               \
+        /* v_bfe_i32: all ones or zero (hipcc turns the C form and the sbfe builtin into and + compare + select); the pair in ONE asm   \
+           so that no 32 extracted masks stay live beside s: apart, hipcc hoists them all and the kernel takes 162 VGPRs for 128 */   \
+        const float pv = s[kb][r];   /* a copy: __builtin_bit_cast on the vector element itself reads element 0 (hipcc 7.2) */ \
+        float pk;                                                                                                             \
+        asm("v_bfe_i32 %0, %1, %2, 1\n\tv_and_b32 %0, %0, %3" : "=&v"(pk) : "v"(kb ? dw1 : dw0), "n"(bit), "v"(pv));           \
+        s[kb][r] = pk;                                                                                                        \
+      }                                                                                                                       \
+  }
+
 // ---- epilogues: O[q][d] = o * inv (inv = 1 / l) to the lane's row `op`; lane (q = lane&31, hh) holds d = db*32 + (r&3) + 8*(r>>2) + 4*hh
 
 // 16-bit output.  A lane holds 4 consecutive d per (db, g) and its partner lane ^ 32 (same query) the other 4 of the same 8: a half

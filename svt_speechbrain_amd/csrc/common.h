@@ -342,7 +342,7 @@ extern int g_gemm_kernel_id;     // key 39 (query): 1000 * family + tile rows of
 extern int g_ln_two_rows;  // (hi, lo) LayerNorm: half a wave per row, 16-byte accesses (1, default) or a wave per row (0)
 extern int g_ln_kernel_id;  // key 40 (query): which LayerNorm kernel and instantiation the last launch chose (layernorm.hip)
 extern int g_flash_wide;  // fused attention: 8-wave (256-query) workgroups for head_dim 64 (1, default) or 4-wave ones (0)
-extern int g_flash_kernel_id;  // fused attention: id of the kernel the last launch chose (attention_bf16.hip; svt_debug_set key 38)
+extern int g_flash_kernel_id;  // fused attention: id of the kernel the last launch chose (attention_bf16.hip, attention_x3.hip, attention_drop.hip; svt_debug_set key 38)
 extern int g_ffn2_ksplit;   // svt_debug_set key 36 (api_encoder.hip): FFN-2 of a small batch as a K-split small GEMM + summing LayerNorm
 // switches of the host entry points, defined beside their users; hidden like the helpers of api.h (not part of the exported symbols)
 #pragma GCC visibility push(hidden)
@@ -550,6 +550,12 @@ DropSpec make_drop_spec(double p, uint64_t seed, uint32_t step, int site, int la
 int launch_dropout_rows(int kind, void* x, int64_t n, uint64_t e0, const DropSpec& d, hipStream_t s);
 int launch_dropout_hilo(bf16_t* xh, bf16_t* xl, int64_t n, uint64_t e0, const DropSpec& d, hipStream_t s);
 int launch_softmax_dropout(int prec, const float* S, int64_t rows, int T, int Tp, void* P, uint64_t e0, const DropSpec& d, hipStream_t s);
+// ---- attention_drop.hip ----
+// launch_flash_attention (16-bit operands, head_dim 64 / 128, no bias) with the mask of site 2 inside: element (b, h, i, j) of the
+// probabilities is e0 + ((b*H + h)*T + i)*T + j; softmax -> dropout -> P V, no score matrix
+int launch_flash_attention_dropout(const void* Q, long ldq, long q_bstride, const void* K, const void* V, long ldk, long k_bstride,
+                                   void* O, long ldo, long o_bstride, int B, int T, int H, int dh, float scale, uint64_t e0,
+                                   const DropSpec& d, hipStream_t s);
 extern int g_dropout_kernel_id;   // key 44 (query): which dropout kernel the last launch chose (dropout.hip; include/svt_mi355.h lists the ids)
 // PCM <-> fp32 on the bytes of a wav file (pcm.hip): interleaved little-endian frames at any byte address <-> planar fp32 rows (4-byte
 // aligned, pitch ld >= frames); format = svt_pcm_format (encode: S16 or F32); downmix: 2 channels -> the one row 0.5 * (l + r).  One launch

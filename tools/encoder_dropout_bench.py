@@ -1,7 +1,9 @@
 """The encoder in training mode: what the checkpoint's dropouts and layerdrop cost on top of a plain forward.
 
     python tools/encoder_dropout_bench.py [--out profiles/encoder_dropout.txt]
-    rocprofv3 --kernel-trace --stats -d DIR_N -- python tools/encoder_dropout_bench.py --count-forwards N      (N = 1 and N = 3)
+    python tools/encoder_dropout_bench.py --precisions bf16,fp16 --out profiles/encoder_dropout_fused.txt      (the fused masked attention)
+    rocprofv3 --kernel-trace --stats --output-format csv -d DIR_N -- python tools/encoder_dropout_bench.py --count-forwards N   (N = 1, 3;
+                                                          --count-parse reads the csv statistics, not the rocpd database)
     python tools/encoder_dropout_bench.py --count-parse DIR_1 DIR_3 [--out ...]                                 (appends the launch table)
 
 wav2vec2-base at 8 x 5 s (the recipe's training batch) and 32 x 10 s, bf16 and fp32.  One encoder per precision; the rates are fields
@@ -15,6 +17,8 @@ forwards, median of the rounds).  Layerdrop is held off (skip_layers all False) 
     attention alone  site 2, which takes the score-matrix attention
     attention ~ 0    attention_dropout 2^-33: threshold 0, nothing dropped -- what FORCING the score-matrix path costs by itself
     one layer fewer  HF defaults with the last layer skipped: what a skipped layer saves
+    ..., fused       HF defaults / attention alone with fused_attention_dropout=True: the mask inside the fused attention kernel
+                     (csrc/attention_drop.hip) in place of the score-matrix path; in fp32 the flag changes nothing
 
 The host cost of the draws is taken by the host clock around draw_layerdrop + torch.cuda.initial_seed().  No assertion on the timings:
 the tool reports."""
@@ -43,6 +47,8 @@ VARIANTS = [
     ("attention alone", dict(attention_dropout=0.1), None),
     ("attention ~ 0 (score path forced)", dict(attention_dropout=2.0 ** -33), None),
     ("HF defaults, last layer skipped", dict(hidden_dropout=0.1, attention_dropout=0.1, activation_dropout=0.1), "last"),
+    ("HF defaults, fused attention", dict(hidden_dropout=0.1, attention_dropout=0.1, activation_dropout=0.1), "fused"),
+    ("attention alone, fused attention", dict(attention_dropout=0.1), "fused"),
 ]
 
 
@@ -86,6 +92,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--precisions", default="bf16,fp32", help="comma-separated precisions of the timed encoders")
     ap.add_argument("--count-forwards", type=int, default=0)
     ap.add_argument("--count-parse", nargs=2, default=None)
     args = ap.parse_args()
@@ -129,7 +136,7 @@ def main():
     layers = cfg.num_hidden_layers
     none = (False,) * layers
     last = (False,) * (layers - 1) + (True,)
-    for prec in ("bf16", "fp32"):
+    for prec in args.precisions.split(","):
         enc = S.HuggingFaceWav2Vec2("wav2vec2-base", None, config=cfg, precision=prec, seed=3, freeze=False).to(DEV)
         for B, secs in ((8, 5), (32, 10)):
             L = secs * 16000
@@ -143,11 +150,12 @@ def main():
                 def run():
                     enc.train()
                     enc.config = dataclasses.replace(cfg, **dict(ZERO, **rates))
-                    return enc(wav, dropout_seed=1234, dropout_step=0, skip_layers=last if skip else none)
+                    enc.fused_attention_dropout = skip == "fused"
+                    return enc(wav, dropout_seed=1234, dropout_step=0, skip_layers=last if skip == "last" else none)
                 return run
 
             fns = [plain] + [variant(r, s) for _, r, s in VARIANTS]
-            iters = (10 if B == 8 else 4) if prec == "bf16" else (4 if B == 8 else 2)
+            iters = (10 if B == 8 else 4) if prec != "fp32" else (4 if B == 8 else 2)
             with torch.no_grad():
                 for fn in fns:
                     for _ in range(2):
@@ -155,10 +163,11 @@ def main():
                 torch.cuda.synchronize()
                 t, spread = time_rounds(fns, iters, args.rounds)
             enc.config = cfg
+            enc.fused_attention_dropout = False
             say(f"encoder forward, wav2vec2-base, {prec}, {B} x {secs} s ({B * cfg.frames(L)} rows), us per forward (median of {args.rounds} rounds of {iters}):")
             say(f"    {'plain (eval mode)':36s} {t[0]:10.1f}   (rounds {spread[0][0]:.1f} .. {spread[0][1]:.1f})")
             for k, (name, rates, skip) in enumerate(VARIANTS, start=1):
-                n = added_launches(rates, layers, 1 if skip else 0)
+                n = added_launches(rates, layers, 1 if skip == "last" else 0)
                 extra = t[k] - t[0]
                 per = f"; {n} dropout launches outside the attention: {extra / n:6.1f} us each" if n and "attention_dropout" not in rates else ""
                 say(f"    {name:36s} {t[k]:10.1f}   (rounds {spread[k][0]:.1f} .. {spread[k][1]:.1f})   {extra:+9.1f} us  {100 * (t[k] / t[0] - 1):+6.2f} %{per}")

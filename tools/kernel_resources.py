@@ -1,7 +1,9 @@
-"""usage: python tools/kernel_resources.py file.hip -> per kernel: VGPRs, scratch bytes/lane, occupancy, spills"""
+"""usage: python tools/kernel_resources.py file.hip [extra hipcc flags] -> per kernel: VGPRs, scratch bytes/lane, occupancy, spills
+The attention objects are built with extra flags (csrc/Makefile, EXTRA): report on the shipped code object with
+    python tools/kernel_resources.py svt_speechbrain_amd/csrc/attention_drop.hip -mllvm -amdgpu-mfma-vgpr-form -fno-honor-nans [-DSVT_OPERAND_F16]"""
 import re, subprocess, sys
 out = subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-ffp-contract=fast", "-fPIC", "-std=c++17", "-c",
-                      sys.argv[1], "-o", "/dev/null", "-Rpass-analysis=kernel-resource-usage"], capture_output=True, text=True).stderr
+                      sys.argv[1], "-o", "/dev/null", "-Rpass-analysis=kernel-resource-usage"] + sys.argv[2:], capture_output=True, text=True).stderr
 name, d = None, {}
 keys = {"VGPRs": "vgpr", "ScratchSize [bytes/lane]": "scratch", "Occupancy [waves/SIMD]": "occ", "VGPRs Spill": "spill"}
 for l in out.splitlines():
