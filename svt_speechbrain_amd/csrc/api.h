@@ -1,5 +1,5 @@
 // Host-side pieces shared by the C-ABI translation units (api.hip and api_*.hip): device buffers, workspace carving, uploads,
-// the attention score path and the argument checks every entry point family uses.  Included by the api*.hip files only.
+// the attention launcher's arguments (attention.hip) and the argument checks every entry point family uses.  Included by the api*.hip files only.
 #pragma once
 #include "common.h"
 #include "host.h"
@@ -73,16 +73,24 @@ static inline size_t esize(int prec) { return prec ? 2 : 4; }
 // launch_gemm(gp = precision) cuts the fp32 operands into 16-bit pieces on their way into LDS (gemm.hip).
 static inline int storage_prec(int precision) { return precision >= 2 ? 0 : precision; }
 
-// out[b,t,h*dh+d] = softmax(scale * q k^T) v (api.hip): the fused kernels where they apply, else the materialised scores.
-// pdrop (training-mode attention dropout, site 2): the materialised scores for EVERY geometry, with the mask on the probabilities
-// (launch_softmax_dropout; element ((b*H + h)*T + i)*T + j); null: the plain path.  fused_drop (svt_dropout.fused_attention): with
-// pdrop, a geometry the plain fused 16-bit kernels serve runs their masked form instead (launch_flash_attention_dropout), the rest as before
-bool use_flash(int prec, int dh, bool bias = false, int64_t T = 0);
-int attn_tp(int prec, int dh, int T, bool bias = false);
-int attention_scores_path(int prec, const void* Q, long ldq, const void* K, const void* V, long ldkv, int B,
-                          int T, int H, int dh, float scale, const AttnBufs& ab, bool vt_ready, void* out,
-                          long ldo, hipStream_t s, const float* gate = nullptr, const float* relpb = nullptr,
-                          int gp = -1, int o_pairs = 0, const DropSpec* pdrop = nullptr, bool fused_drop = false);
+// One attention (attention.hip): out[b,t,h*dh+d] = softmax(scale q k^T [+ gated bias]) v; q rows at Q + (b*T+t)*ldq + h*dh, likewise
+// K and V (ldkv).  plan_attention (host.h) chooses among the fused kernels and the materialised scores.
+struct AttnArgs {
+  int prec = 0, gp = -1;     // storage type; product engine (-1: prec)
+  const void *Q = nullptr, *K = nullptr, *V = nullptr; long ldq = 0, ldkv = 0;
+  void* out = nullptr; long ldo = 0; int o_pairs = 0;   // o_pairs: out written as pair rows (the fused split path only)
+  int B = 0, T = 0, H = 0, dh = 0; float scale = 1.f;
+  const float *gate = nullptr, *relpb = nullptr;        // WavLM: gate (B,H,T), bias table (H, 2T-1); both or neither
+  // training-mode attention dropout (site 2): the mask on the probabilities, element ((b*H + h)*T + i)*T + j; null: the plain paths.
+  // fused_drop (svt_dropout.fused_attention): a geometry the plain fused 16-bit kernels serve runs their masked form, the rest the scores
+  const DropSpec* drop = nullptr; bool fused_drop = false;
+  bool kv_ready = false;     // the K/V side (V^T, or the planes) was prepared by an earlier call on the same k, v
+};
+AttnGeom attn_geom(const AttnArgs& a);   // the ONE place that infers packed_kv / q_packed from addresses and strides
+// refuses (set_error, nothing launched) when a buffer the plan needs is null in `ab`
+int launch_attention(const AttnArgs& a, const AttnBufs& ab, hipStream_t s);
+// the buffers `plan` names, in the order S, P, Vt, pl_qkv, pl_q; the rest null.  es: esize of the storage type
+AttnBufs carve_attention(Carver& cv, const AttnPlan& plan, size_t B, size_t H, size_t T, size_t dh, size_t es);
 
 // a gfx950 device of this index exists; it becomes the current device
 int check_device(int device);

@@ -200,83 +200,6 @@ int begin_upload(bool& uploaded) {
   return SVT_OK;
 }
 
-// ---------------------------------------------------------------- attention (materialised scores)
-// out[b,t,h*dh+d] = softmax(scale * q k^T) v ; q rows at Q + (b*T+t)*ldq + h*dh, likewise K (ldkv), V (ldkv)
-// fused attention: bf16, head_dim 64 / 128; its relative-position-bias variant (WavLM) exists for head_dim 64 with the
-// (2T-1)-entry table of a head in LDS -- other WavLM geometries take the score-matrix path
-bool use_flash(int prec, int dh, bool bias, int64_t T) {
-  if (!(prec == 1 && (dh == 64 || dh == 128))) return false;
-  return !bias || (dh == 64 && 2 * T - 1 <= 8192);
-}
-int attn_tp(int prec, int dh, int T, bool bias) {
-  return use_flash(prec, dh, bias, T) ? round_up_int(T, 64) : round_up_int(T, 8);
-}
-
-int attention_scores_path(int prec, const void* Q, long ldq, const void* K, const void* V, long ldkv, int B,
-                          int T, int H, int dh, float scale, const AttnBufs& ab, bool vt_ready, void* out,
-                          long ldo, hipStream_t s, const float* gate, const float* relpb, int gp, int o_pairs, const DropSpec* pdrop,
-                          bool fused_drop) {
-  if (gp < 0) gp = prec;
-  if (gp >= 2 && !pdrop && !gate && flash_attention_x3_ok(dh) && ab.pl_qkv && ldkv == 3L * H * dh &&
-      (const float*)V == (const float*)K + (long)H * dh) {
-    // split-operand fused attention: cut the fp32 projections into 16-bit planes once, then three MFMAs per product
-    // (attention_x3.hip flash_attn_x3_kernel) -- no (B, H, T, T) score tensor
-    const long D = (long)H * dh, rows = (long)B * T;
-    const float* kv0 = (const float*)K - D;                     // start of the packed (rows, 3D) projection
-    const long pl3 = rows * 3 * D;
-    unsigned short* p3 = (unsigned short*)ab.pl_qkv;
-    if (!vt_ready)
-      if (int r = launch_split_planes(gp, kv0, 3 * D, rows, (int)(3 * D), p3, 3 * D, pl3, s)) return r;
-    const unsigned short* qp;
-    long qld, qpl;
-    if ((const float*)Q == kv0 && ldq == 3 * D) { qp = p3; qld = 3 * D; qpl = pl3; }
-    else {
-      if (!ab.pl_q) { set_error("attention: no workspace for the query planes"); return -1; }
-      if (int r = launch_split_planes(gp, (const float*)Q, ldq, rows, (int)D, ab.pl_q, D, rows * D, s)) return r;
-      qp = (const unsigned short*)ab.pl_q; qld = D; qpl = rows * D;
-    }
-    return launch_flash_attention_x3(gp, qp, qld, (long)T * qld, qpl, p3 + D, p3 + 2 * D, 3 * D, (long)T * 3 * D, pl3, (float*)out, ldo,
-                                     (long)T * ldo, B, T, H, dh, scale, s, o_pairs);
-  }
-  if (o_pairs) { set_error("attention: pair-row output is served by the fused split attention only"); return -1; }
-  if (!pdrop && use_flash(prec, dh, gate != nullptr, T)) {
-    (void)vt_ready;
-    return launch_flash_attention(Q, ldq, (long)T * ldq, K, V, ldkv, (long)T * ldkv, out, ldo, (long)T * ldo, B, T, H, dh,
-                                  scale, s, gate, gate ? relpb : nullptr);
-  }
-  if (pdrop && fused_drop && !gate && use_flash(prec, dh, /*bias*/ false, T))
-    return launch_flash_attention_dropout(Q, ldq, (long)T * ldq, K, V, ldkv, (long)T * ldkv, out, ldo, (long)T * ldo, B, T, H, dh, scale,
-                                          0, *pdrop, s);
-  const int Tp = round_up_int(T, 8);
-  GemmArgs g;
-  g.A = Q; g.W = K; g.C = ab.S;
-  g.M = T; g.N = T; g.K = dh;
-  g.a_rpb = T; g.a_bstride = 0; g.a_rstride = ldq;
-  g.ldw = ldkv; g.ldc = Tp;
-  g.nz = B * H; g.nz2 = H;
-  g.a_z1 = (long)T * ldq; g.a_z2 = dh;
-  g.w_z1 = (long)T * ldkv; g.w_z2 = dh;
-  g.c_z1 = (long)H * T * Tp; g.c_z2 = (long)T * Tp;
-  g.alpha = scale; g.out_f32 = 1;
-  if (int r = launch_gemm(gp, g, s)) return r;
-  if (gate)
-    if (int r = launch_scores_add_relbias(ab.S, (int64_t)B * H, H, T, Tp, gate, relpb, s)) return r;
-  if (pdrop) { if (int r = launch_softmax_dropout(prec, ab.S, (int64_t)B * H * T, T, Tp, ab.P, 0, *pdrop, s)) return r; }
-  else if (int r = launch_softmax_rows(prec, ab.S, (int64_t)B * H * T, T, Tp, ab.P, s)) return r;
-  if (!vt_ready)
-    if (int r = launch_transpose_v(prec, V, B, T, H, dh, ldkv, 0, Tp, ab.Vt, s)) return r;
-  GemmArgs o;
-  o.A = ab.P; o.W = ab.Vt; o.C = out;
-  o.M = T; o.N = dh; o.K = Tp;
-  o.a_rpb = T; o.a_rstride = Tp;
-  o.ldw = Tp; o.ldc = ldo;
-  o.nz = B * H; o.nz2 = H;
-  o.a_z1 = (long)H * T * Tp; o.a_z2 = (long)T * Tp;
-  o.w_z1 = (long)H * dh * Tp; o.w_z2 = (long)dh * Tp;
-  o.c_z1 = (long)T * ldo; o.c_z2 = dh;
-  return launch_gemm(gp, o, s);
-}
-
 int check_device(int device) {
   int n = 0;
   if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) { set_error("no HIP device visible: the MI355X path cannot run (there is no CPU fallback)"); return SVT_ERR_NO_DEVICE; }
@@ -598,17 +521,17 @@ int svt_debug_attention(int32_t precision, const void* q, const void* k, const v
   SVT_HIP(hipSetDevice(device));
   if (precision >= 2) {
     // q / k / v: fp32 slices of ONE packed (batch * t, 3 * heads * head_dim) projection; o: fp32
-    const long D = (long)heads * head_dim, rows = (long)batch * t;
-    if ((const float*)k != (const float*)q + D || (const float*)v != (const float*)q + 2 * D || ldq != 3 * D || ldkv != 3 * D) {
+    AttnArgs a;
+    a.gp = precision; a.Q = q; a.K = k; a.V = v; a.ldq = ldq; a.ldkv = ldkv; a.out = o; a.ldo = ldo;
+    a.B = batch; a.T = t; a.H = heads; a.dh = head_dim; a.scale = scale;
+    const AttnPlan plan = plan_attention(attn_geom(a));
+    if (plan.path != ATTN_FUSED_X3 || plan.planes_q) {
       set_error("svt_debug_attention: the split-operand kernel is exposed for a packed q|k|v projection"); return SVT_ERR_INVALID; }
-    void* planes = nullptr;
-    if (int r = dev_alloc(&planes, (size_t)rows * 3 * D * 4)) return r;
-    AttnBufs ab{};
-    ab.pl_qkv = planes;
-    const int rc = attention_scores_path(0, q, ldq, k, v, ldkv, batch, t, heads, head_dim, scale, ab, false, o, ldo, (hipStream_t)stream,
-                                         nullptr, nullptr, precision);
+    AttnBufs ab{};   // the plan needs the planes of the packed projection and nothing else
+    if (int r = dev_alloc(&ab.pl_qkv, (size_t)batch * t * 3 * heads * head_dim * 4)) return r;
+    const int rc = launch_attention(a, ab, (hipStream_t)stream);
     (void)hipStreamSynchronize((hipStream_t)stream);
-    dev_free(planes);
+    dev_free(ab.pl_qkv);
     return rc ? SVT_ERR_INVALID : SVT_OK;
   }
   if (launch_flash_attention(q, ldq, (long)t * ldq, k, v, ldkv, (long)t * ldkv, o, ldo, (long)t * ldo, batch, t, heads,
@@ -622,7 +545,9 @@ int svt_debug_attention_dropout(const svt_debug_attention_dropout_desc* d, int d
   if (d->struct_size != (int32_t)sizeof(svt_debug_attention_dropout_desc)) return refuse("struct_size");
   if (!d->q || !d->k || !d->v || !d->o) return refuse("null argument");
   if (d->batch < 1 || d->t < 1 || d->heads < 1) return refuse("batch, t and heads must be positive");
-  if (!use_flash(d->precision, d->head_dim, false, d->t))
+  AttnGeom g;
+  g.prec = g.gp = d->precision; g.dh = d->head_dim; g.T = d->t; g.drop = g.fused_drop = true;
+  if (plan_attention(g).path != ATTN_FUSED16_DROP)
     return refuse("the fused kernel serves precision SVT_PREC_BF16 (the build's 16-bit operand type) at head_dim 64 / 128 only");
   if (!(d->p >= 0.0 && d->p < 1.0)) return refuse("p must lie in [0, 1)");
   if (d->layer < 0 || d->layer > 0xFFFFFF) return refuse("layer");
@@ -654,13 +579,17 @@ int svt_debug_attention_scores(int32_t precision, const void* q, const void* k, 
   if (!valid_precision(precision)) { set_error("svt_debug_attention_scores: precision"); return SVT_ERR_INVALID; }
   if (batch < 1 || t < 1 || heads < 1 || head_dim < 1) { set_error("svt_debug_attention_scores: batch, t, heads and head_dim must be positive"); return SVT_ERR_INVALID; }
   if (!gate_dev != !pos_bias_dev) { set_error("svt_debug_attention_scores: gate and pos_bias come together"); return SVT_ERR_INVALID; }
-  if (use_flash(precision, head_dim, gate_dev != nullptr, t)) {
+  const int prec = storage_prec(precision);
+  AttnArgs a;
+  a.prec = prec; a.gp = precision; a.Q = q; a.K = k; a.V = v; a.ldq = ldq; a.ldkv = ldkv; a.out = o; a.ldo = ldo;
+  a.B = batch; a.T = t; a.H = heads; a.dh = head_dim; a.scale = scale; a.gate = gate_dev; a.relpb = pos_bias_dev;
+  const AttnPlan plan = plan_attention(attn_geom(a));
+  if (plan.path != ATTN_SCORES) {
     set_error("svt_debug_attention_scores: this geometry runs the fused kernel (svt_debug_attention / svt_debug_attention_bias)"); return SVT_ERR_INVALID; }
   if (int r = check_device(device)) return r;
   SVT_HIP(hipSetDevice(device));
   hipStream_t s = (hipStream_t)stream;
-  const int prec = storage_prec(precision);
-  const int Tp = attn_tp(precision, head_dim, t, gate_dev != nullptr);
+  const int Tp = plan.Tp;
   const size_t bh = (size_t)batch * heads;
   const size_t bytes[3] = {bh * t * Tp * 4, bh * t * Tp * esize(prec), bh * head_dim * Tp * esize(prec)};
   void* buf[3] = {nullptr, nullptr, nullptr};
@@ -672,8 +601,7 @@ int svt_debug_attention_scores(int32_t precision, const void* q, const void* k, 
   if (!rc) {
     AttnBufs ab{};
     ab.S = (float*)buf[0]; ab.P = buf[1]; ab.Vt = buf[2];
-    rc = attention_scores_path(prec, q, ldq, k, v, ldkv, batch, t, heads, head_dim, scale, ab, false, o, ldo, s, gate_dev, pos_bias_dev,
-                               precision) ? SVT_ERR_INVALID : SVT_OK;
+    rc = launch_attention(a, ab, s) ? SVT_ERR_INVALID : SVT_OK;
   }
   (void)hipStreamSynchronize(s);
   for (int i = 0; i < 3; ++i) dev_free(buf[i]);

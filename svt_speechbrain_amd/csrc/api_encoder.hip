@@ -2,7 +2,7 @@
 // carving and the launch sequence of a forward, with or without the fused frame-head tail.  Host code only: no allocation and no
 // synchronisation inside a forward call.
 //   finalize: finalize_conv_stack -> finalize_projection -> finalize_pos_conv(_stack) -> encoder LayerNorm -> finalize_layer
-//   forward:  plan_encoder -> carve_encoder -> input_statistics -> choose_pair_rows -> conv_layer0 -> conv_stack -> feature_projection
+//   forward:  plan_encoder (plan_attention) -> carve_encoder -> input_statistics -> choose_pair_rows -> conv_layer0 -> conv_stack -> feature_projection
 //             [-> spec_augment] -> positional_conv -> encoder_layers (post_ln_layers / pre_ln_layers) -> forward_tail
 //   training mode (svt_encoder_set_dropout): drop_rows / launch_dropout_hilo / the softmax form at the six sites of the header, skipped layers launch nothing
 #include "../../include/svt_mi355.h"
@@ -402,17 +402,16 @@ struct EncPlan {
   int gp = 0;              // engine of the dense products (launch_gemm)
   bool reduced = false;    // reduced_mode()
   bool rel = false;        // WavLM relative position bias
-  bool flash = false;      // fused 16-bit attention: no score matrix
-  bool planes = false;     // fused split attention: no score matrix, the QKV projection's epilogue writes the (hi, lo) planes it reads
-  int attn_Tp = 0;         // padded key length of the score / V^T buffers
+  AttnPlan attn;           // the layers' attention: its path and the buffers it needs (plan_attention); on ATTN_FUSED_X3 the QKV
+                           // projection's epilogue writes the (hi, lo) planes the kernel reads
   int Pf = 0;              // frames per row of the multi-frame positional conv the encoder holds (0: none)
   int64_t pos_Tq = 0;      // ... its GEMM rows per clip
   int64_t pos_Tp = 0;      // frames per clip the gathered positional-conv input is carved for: pos_Tq * Pf + kernel (multi-frame), else T + kernel
   bool pos_multi = false;  // this batch has enough rows for the multi-frame form
   bool hilo = false;       // post-LN encoder with the residual stream as a bf16 (hi, lo) pair
   bool ksplit_ws = false;  // few enough rows for the K-split FFN-2: its partial products get workspace
-  bool attn_drop = false;  // training mode with attention_dropout > 0: the score-matrix attention for every geometry, unless ...
-  bool attn_fused_drop = false;  // ... svt_dropout.fused_attention opted in and the plain forward runs a fused 16-bit kernel: its masked form
+  bool attn_drop = false;  // training mode with attention_dropout > 0: the score-matrix attention for every geometry, unless
+                           // svt_dropout.fused_attention opted in and the plain forward runs a fused 16-bit kernel: its masked form
 };
 
 // false: the waveform is shorter than the receptive field
@@ -429,10 +428,11 @@ bool plan_encoder(const svt_encoder* e, int B, int64_t L, EncPlan* out) {
   p.sp = storage_prec(c.precision); p.gp = c.precision; p.reduced = reduced_mode(c);
   p.rel = c.rel_pos_buckets > 0;
   p.attn_drop = e->drop_on && e->drop.attention_dropout > 0;
-  p.attn_fused_drop = p.attn_drop && e->drop.fused_attention != 0 && !p.rel && use_flash(p.sp, p.dh, /*bias*/ false, p.T);
-  p.flash = (!p.attn_drop || p.attn_fused_drop) && use_flash(p.sp, p.dh, p.rel, p.T);
-  p.planes = p.gp >= 2 && flash_attention_x3_ok(p.dh) && !p.rel;
-  p.attn_Tp = p.attn_drop && !p.attn_fused_drop ? round_up_int((int)p.T, 8) : attn_tp(p.sp, p.dh, (int)p.T, p.rel);
+  AttnGeom ag;   // attention_block's call: q | k | v are the columns of one (rows, 3D) projection
+  ag.prec = p.sp; ag.gp = p.gp; ag.dh = p.dh; ag.T = p.T; ag.bias = p.rel;
+  ag.drop = p.attn_drop; ag.fused_drop = e->drop.fused_attention != 0;
+  ag.packed_kv = ag.q_packed = true;
+  p.attn = plan_attention(ag);
   p.Pf = e->pos_P;
   p.pos_Tq = p.Pf ? (p.T + p.Pf - 1) / p.Pf : 0;
   p.pos_Tp = p.Pf ? p.pos_Tq * p.Pf + c.pos_conv_kernel : p.T + c.pos_conv_kernel;
@@ -509,11 +509,8 @@ EncWs carve_encoder(const svt_encoder* e, const EncPlan& p, void* base) {
   w.posg = cv.take(B * p.pos_Tp * D * es);
   w.posy = p.Pf ? cv.take(B * p.pos_Tq * p.Pf * D * es) : nullptr;
   w.qkv = cv.take(rows * 3 * D * es);
-  const bool scores = !(p.flash || p.planes);
-  w.ab.S = scores ? (float*)cv.take(B * H * T * p.attn_Tp * 4) : nullptr;
-  w.ab.P = scores ? cv.take(B * H * T * p.attn_Tp * es) : nullptr;
-  w.ab.Vt = cv.take(B * H * p.dh * p.attn_Tp * es);
-  w.ab.pl_qkv = p.planes ? cv.take(rows * 3 * D * 4) : nullptr;
+  // (kept on purpose: V^T is carved on the fused paths too, where nothing reads it -- attn_workspace_plan)
+  w.ab = carve_attention(cv, attn_workspace_plan(p.attn, false), B, H, T, (size_t)p.dh, es);
   w.attn_o = cv.take(rows * D * es);
   w.ffn = cv.take(rows * p.F * es);
   w.gate = p.rel ? (float*)cv.take(B * H * T * 4) : nullptr;
@@ -688,7 +685,7 @@ void choose_pair_rows(EncRun& x) {
   x.pk_front = front ? pk_mode : 0;
   // encoder layers on pair rows: the layer input (LayerNorm output), the attention output and the FFN intermediate are written as
   // pair rows by their producers; the residual stream stays fp32 beside them (w.xF)
-  const bool enc = pk_mode != 0 && p.planes && c.num_layers > 0 && (D == 512 || D == 768 || D == 1024) && p.dh % 32 == 0 &&
+  const bool enc = pk_mode != 0 && p.attn.path == ATTN_FUSED_X3 && c.num_layers > 0 && (D == 512 || D == 768 || D == 1024) && p.dh % 32 == 0 &&
                    x3q_fits(w.xb, rows, 3 * D, D, rows, 0, D, e->layers[0].wqkv.p, 0, 3 * D) &&
                    x3q_fits(w.attn_o, rows, D, D, rows, 0, D, e->layers[0].wo.p, 0, D) &&
                    x3q_fits(w.xb, rows, F, D, rows, 0, D, e->layers[0].w1.p, 1, F) &&
@@ -894,7 +891,8 @@ int attention_block(const EncRun& x, const EncLayerW& Lw, const LayerForm& f, in
   const EncWs& w = x.w;
   const int D = p.D;
   // split-operand modes with the fused attention: the QKV projection's epilogue writes the planes the attention reads
-  if (int r = rows_gemm(x, w.xb, D, Lw.wqkv, Lw.bqkv, 3 * D, w.qkv, 0, ACT_NONE, p.planes ? (unsigned short*)w.ab.pl_qkv : nullptr)) return r;
+  const bool x3 = p.attn.path == ATTN_FUSED_X3;
+  if (int r = rows_gemm(x, w.xb, D, Lw.wqkv, Lw.bqkv, 3 * D, w.qkv, 0, ACT_NONE, x3 ? (unsigned short*)w.ab.pl_qkv : nullptr)) return r;
   const float* gate = nullptr;
   if (p.rel) {
     // WavLM: the gate of the relative position bias is a function of the attention INPUT (w.xb, operand type)
@@ -904,10 +902,16 @@ int attention_block(const EncRun& x, const EncLayerW& Lw, const LayerForm& f, in
   }
   DropSpec ad;   // site 2
   if (p.attn_drop) ad = make_drop_spec(x.drop->attention_dropout, x.drop->seed, x.drop->step, 2, l);
-  if (int r = attention_scores_path(p.sp, w.qkv, 3L * D, (const char*)w.qkv + (size_t)D * esize(p.sp),
-                                    (const char*)w.qkv + (size_t)2 * D * esize(p.sp), 3L * D, p.B, (int)p.T, p.H, p.dh,
-                                    1.0f / std::sqrt((float)p.dh), w.ab, p.planes, w.attn_o, D, x.s, gate, w.relpb, p.gp, x.pk_enc ? 1 : 0,
-                                    p.attn_drop ? &ad : nullptr, p.attn_fused_drop)) return r;
+  AttnArgs a;
+  a.prec = p.sp; a.gp = p.gp;
+  a.Q = w.qkv; a.K = (const char*)w.qkv + (size_t)D * esize(p.sp); a.V = (const char*)w.qkv + (size_t)2 * D * esize(p.sp);
+  a.ldq = a.ldkv = 3L * D;
+  a.out = w.attn_o; a.ldo = D; a.o_pairs = x.pk_enc ? 1 : 0;
+  a.B = p.B; a.T = (int)p.T; a.H = p.H; a.dh = p.dh; a.scale = 1.0f / std::sqrt((float)p.dh);
+  a.gate = gate; a.relpb = w.relpb;
+  a.drop = p.attn_drop ? &ad : nullptr; a.fused_drop = x.e->drop.fused_attention != 0;
+  a.kv_ready = x3;   // the planes are there already
+  if (int r = launch_attention(a, w.ab, x.s)) return r;
   // (rounds 1-2 fused this projection with the residual add and the LayerNorm in one row-complete kernel, 44 us against 29 + 23; with
   //  the projection on gemm_pps_kernel the pair costs 20.6 + 23.9 us and the fused kernel -- every workgroup streaming all of W,
   //  0.16 of the matrix pipe -- is gone: C2 6 093-6 110 against 6 066-6 074 clips/s on one box)

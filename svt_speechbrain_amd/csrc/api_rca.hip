@@ -45,21 +45,18 @@ RcaWs carve_rca(const svt_rca* r, int B, int T, void* base) {
   Carver cv(base);
   RcaWs w;
   const size_t es = esize(r->prec), rows = (size_t)B * T, D = r->D;
-  const int dh = r->D / r->H, Tp = attn_tp(r->prec, dh, T);
-  const bool flash = use_flash(r->prec, dh);
+  const int dh = r->D / r->H;
   w.s1F = (float*)cv.take(rows * D * 4);
   w.s2F = (float*)cv.take(rows * D * 4);
   w.s1T = r->prec ? cv.take(rows * D * es) : (void*)w.s1F;
   w.s2T = r->prec ? cv.take(rows * D * es) : (void*)w.s2F;
   w.qkv = cv.take(rows * 3 * D * es);
   w.qc = cv.take(rows * D * es);
-  w.ab.S = flash ? nullptr : (float*)cv.take((size_t)B * r->H * T * Tp * 4);
-  w.ab.P = flash ? nullptr : cv.take((size_t)B * r->H * T * Tp * es);
-  w.ab.Vt = cv.take((size_t)B * r->H * dh * Tp * es);
-  if (r->gp >= 2 && flash_attention_x3_ok(dh)) {
-    w.ab.pl_qkv = cv.take(rows * 3 * D * 4);
-    w.ab.pl_q = cv.take(rows * D * 4);
-  }
+  // one set of buffers serves both attentions of a layer: k | v packed in both, the cross query in a buffer of its own
+  // (kept on purpose: V^T on the fused paths, S and P in the split modes, which nothing reads -- attn_workspace_plan)
+  AttnGeom ag;
+  ag.prec = r->prec; ag.gp = r->gp; ag.dh = dh; ag.T = T; ag.packed_kv = true;
+  w.ab = carve_attention(cv, attn_workspace_plan(plan_attention(ag), true), B, r->H, T, dh, es);
   w.att_s = cv.take(rows * D * es);
   w.att_c = cv.take(rows * D * es);
   w.blend = cv.take(rows * D * es);
@@ -177,8 +174,12 @@ int rca_forward_run(svt_rca* r, const float* audio, int T1, const float* video, 
     if (int rc = gemm_rows(qT, D, L.win.p, L.bin.as<float>(), D, qc, 0, ACT_NONE, nullptr)) return rc;
     const char* kp = (const char*)qkv + (size_t)D * es;
     const char* vp = (const char*)qkv + (size_t)2 * D * es;
-    if (int rc = attention_scores_path(prec, qkv, 3L * D, kp, vp, 3L * D, B, T, H, dh, scale, w.ab, false, att_s, D, s, nullptr, nullptr, r->gp)) return rc;
-    if (int rc = attention_scores_path(prec, qc, D, kp, vp, 3L * D, B, T, H, dh, scale, w.ab, true, att_c, D, s, nullptr, nullptr, r->gp)) return rc;
+    AttnArgs a;
+    a.prec = prec; a.gp = r->gp; a.Q = qkv; a.K = kp; a.V = vp; a.ldq = a.ldkv = 3L * D; a.out = att_s; a.ldo = D;
+    a.B = B; a.T = T; a.H = H; a.dh = dh; a.scale = scale;
+    if (int rc = launch_attention(a, w.ab, s)) return rc;
+    a.Q = qc; a.ldq = D; a.out = att_c; a.kv_ready = true;   // cross attention: the same k, v
+    if (int rc = launch_attention(a, w.ab, s)) return rc;
     // out_proj is linear: alpha*Wo(a_s) + (1-alpha)*Wo(a_c) + bo = Wo(alpha*a_s + (1-alpha)*a_c) + bo
     if (int rc = launch_axpby(prec, att_s, att_c, r->alpha, 1.f - r->alpha, blend, rows * D, s)) return rc;
     if (int rc = gemm_rows(blend, D, L.wo.p, L.bo.as<float>(), D, pre1, 1, ACT_NONE, nullptr)) return rc;

@@ -474,7 +474,7 @@ int launch_scores_add_relbias(float* S, int64_t BH, int H, int T, int Tp, const 
 int launch_clock_stamp(long long* out16, hipStream_t s);
 
 // ---- attention_bf16.hip ----
-// fused attention (bf16, head_dim 64/128): Q/K row-major with row strides ldq/ldk and per-clip strides, V^T padded
+// fused attention (16-bit operands, head_dim 64/128), row strides ldq / ldk and per-clip strides in elements; no V^T buffer:
 // Q/K/V row-major (K and V share row / clip strides); V is transposed on the fly by ds_read_b64_tr_b16
 // gate (B,H,T) / pb (H, 2T-1): WavLM's gated relative position bias, or nullptr
 int launch_flash_attention(const void* Q, long ldq, long q_bstride, const void* K, const void* V, long ldk, long k_bstride,

@@ -137,6 +137,31 @@ void posconv_multiframe(const float* w, const float* bias, int G, int cg, int kp
       }
 }
 
+// First match wins.  The fused kernels exist for head sizes 64 / 128; the 16-bit one has WavLM's bias for head
+// size 64 with the (2T-1)-entry table of a head in LDS; the split one reads planes cut from one packed projection and has neither bias
+// nor mask; a mask without the opt-in takes the materialised scores for every geometry.
+AttnPlan plan_attention(const AttnGeom& g) {
+  const bool dh_ok = g.dh == 64 || g.dh == 128;
+  auto pad = [&](int a) { return (int)((g.T + a - 1) / a * a); };
+  AttnPlan p;
+  if (g.gp >= 2 && !g.drop && !g.bias && dh_ok && g.packed_kv) {
+    p.path = ATTN_FUSED_X3; p.Tp = pad(8); p.planes_qkv = true; p.planes_q = !g.q_packed;
+  } else if (!g.drop && g.prec == 1 && dh_ok && (!g.bias || (g.dh == 64 && 2 * g.T - 1 <= 8192))) {
+    p.path = ATTN_FUSED16; p.Tp = pad(64);
+  } else if (g.drop && g.fused_drop && !g.bias && g.prec == 1 && dh_ok) {
+    p.path = ATTN_FUSED16_DROP; p.Tp = pad(64);
+  } else {
+    p.path = ATTN_SCORES; p.Tp = pad(8); p.scores = p.vt = true;
+  }
+  return p;
+}
+
+AttnPlan attn_workspace_plan(AttnPlan p, bool scores_with_planes) {
+  p.vt = true;
+  if (scores_with_planes && p.path == ATTN_FUSED_X3) p.scores = true;
+  return p;
+}
+
 }  // namespace svt
 
 using namespace svt;

@@ -47,6 +47,37 @@ void gate_rowsum_fold(const float* w, const float* b, int dh, std::vector<float>
 // (kp+Pf-1)*cg -- row j*cg+co of a group holds filter co shifted by j taps, zero elsewhere -- and bP (G x Pf*cg) repeats the bias
 void posconv_multiframe(const float* w, const float* bias, int G, int cg, int kp, int Pf, std::vector<float>* wP, std::vector<float>* bP);
 
+// ---- attention planner: which of the four attention paths a geometry takes and which workspace buffers that path needs.  A function of
+// numbers and flags only (no pointer, no global): the workspace carves, the launcher (attention.hip launch_attention) and the debug hooks
+// all read ONE AttnPlan, so a carve can never disagree with the launch behind it (`make san` runs its expectation table) ----
+enum AttnPath {
+  ATTN_FUSED16,        // fused 16-bit kernels (attention_bf16.hip), with WavLM's gated bias where the kernel has it
+  ATTN_FUSED16_DROP,   // the same with the dropout mask of site 2 inside (attention_drop.hip)
+  ATTN_FUSED_X3,       // split-operand fused kernel on 16-bit (hi, lo) planes (attention_x3.hip)
+  ATTN_SCORES          // materialised scores: two batched products around bias add, softmax (with or without the mask) and V^T
+};
+struct AttnGeom {
+  int prec = 0, gp = 0, dh = 0;   // storage type (0 fp32, 1 16-bit); product engine (svt_precision); head size
+  int64_t T = 0;
+  bool bias = false;              // gated relative position bias (WavLM)
+  bool drop = false;              // a dropout mask on the probabilities ...
+  bool fused_drop = false;        // ... and the caller opted into the masked fused kernel where it serves the geometry
+  bool packed_kv = false;         // k | v are columns D.., 2D.. of ONE fp32 (rows, 3D) projection: the planes are cut from it whole
+  bool q_packed = false;          // ... and q is its columns 0..
+};
+struct AttnPlan {
+  AttnPath path = ATTN_SCORES;
+  int Tp = 0;                  // padded key length the S / P / V^T buffers are carved with
+  bool scores = false;         // needs S and P
+  bool vt = false;             // needs V^T
+  bool planes_qkv = false;     // needs the planes of the packed projection
+  bool planes_q = false;       // needs planes for a query in a buffer of its own
+};
+AttnPlan plan_attention(const AttnGeom& g);
+// The plan a WORKSPACE is carved from: `p` plus two buffers nothing reads, kept because dropping them changes svt_*_workspace_bytes
+// (a follow-up): V^T on the fused paths, and (scores_with_planes: FusionRCA) S and P on the fused split path.
+AttnPlan attn_workspace_plan(AttnPlan p, bool scores_with_planes);
+
 #ifdef SVT_OPERAND_F16
 // the IEEE-half build serves the exact fp32 mode and the 16-bit throughput mode; the split-operand engines live in the bf16 build
 static inline bool valid_precision(int p) { return p == SVT_PREC_FP32 || p == SVT_PREC_BF16; }

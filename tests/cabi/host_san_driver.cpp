@@ -6,6 +6,7 @@
 //   host_san_test fold <op> <out.bin> <dims...> <in.bin...>  -> a re-layout / fold of the finalize step on raw float32 files:
 //       tap_major | tap_minor Co Ci k w;  weight_norm n kp g v;  batch_norm C weight bias mean var -> scale, shift;
 //       gate dh w b -> wab, bab;  multiframe G cg kp Pf w bias -> wP, bP
+//   host_san_test attention                                 -> plan_attention against a hand-written table; prints "attention ok"
 #include "../../svt_speechbrain_amd/csrc/host.h"
 
 #include <cstdio>
@@ -178,10 +179,93 @@ static int run_hostile() {
   return 0;
 }
 
+// plan_attention against a table written by hand from DESIGN.md section 4.2 (literal rows, not a second copy of the rule), and the two
+// composite conditions under which the encoder's and FusionRCA's workspaces hold score buffers
+static int run_attention() {
+  const AttnPath F16 = ATTN_FUSED16, DROP = ATTN_FUSED16_DROP, X3 = ATTN_FUSED_X3, SC = ATTN_SCORES;
+  struct Row { AttnGeom g; AttnPath path; int Tp; bool scores, vt, planes_qkv, planes_q; };
+  //                 prec gp dh   T     bias   drop   fdrop  pkv    qpk       path  Tp    S+P    Vt     pl_qkv pl_q
+  const Row rows[] = {
+      {{1, 1, 64, 100, false, false, false, true, true}, F16, 128, false, false, false, false},       // bf16
+      {{1, 1, 128, 100, false, false, false, true, true}, F16, 128, false, false, false, false},
+      {{1, 1, 48, 100, false, false, false, true, true}, SC, 104, true, true, false, false},
+      {{1, 1, 96, 100, false, false, false, true, true}, SC, 104, true, true, false, false},
+      {{1, 1, 64, 100, false, false, false, false, false}, F16, 128, false, false, false, false},     // the layout does not matter to it
+      {{0, 0, 64, 100, false, false, false, true, true}, SC, 104, true, true, false, false},          // fp32
+      {{1, 1, 64, 4096, true, false, false, true, true}, F16, 4096, false, false, false, false},      // bias: 2T - 1 = 8191 entries fit
+      {{1, 1, 64, 4097, true, false, false, true, true}, SC, 4104, true, true, false, false},         // ... 8193 do not
+      {{1, 1, 128, 100, true, false, false, true, true}, SC, 104, true, true, false, false},
+      {{0, 0, 64, 100, true, false, false, true, true}, SC, 104, true, true, false, false},
+      {{1, 1, 64, 100, false, true, false, true, true}, SC, 104, true, true, false, false},           // a mask without the opt-in
+      {{1, 1, 128, 100, false, true, false, true, true}, SC, 104, true, true, false, false},
+      {{1, 1, 64, 100, false, true, true, true, true}, DROP, 128, false, false, false, false},        // ... with it
+      {{1, 1, 128, 100, false, true, true, true, true}, DROP, 128, false, false, false, false},
+      {{1, 1, 64, 100, true, true, true, true, true}, SC, 104, true, true, false, false},
+      {{0, 0, 64, 100, false, true, true, true, true}, SC, 104, true, true, false, false},
+      {{1, 1, 96, 100, false, true, true, true, true}, SC, 104, true, true, false, false},
+      {{1, 1, 64, 100, false, false, true, true, true}, F16, 128, false, false, false, false},        // the opt-in without a mask: plain
+      {{0, 2, 64, 100, false, false, false, true, true}, X3, 104, false, false, true, false},         // split modes
+      {{0, 3, 64, 100, false, false, false, true, true}, X3, 104, false, false, true, false},
+      {{0, 2, 128, 100, false, false, false, true, true}, X3, 104, false, false, true, false},
+      {{0, 2, 64, 100, false, false, false, true, false}, X3, 104, false, false, true, true},         // a query of its own
+      {{0, 2, 64, 100, false, false, false, false, false}, SC, 104, true, true, false, false},
+      {{0, 2, 64, 100, true, false, false, true, true}, SC, 104, true, true, false, false},
+      {{0, 2, 64, 100, false, true, false, true, true}, SC, 104, true, true, false, false},
+      {{0, 2, 64, 100, false, true, true, true, true}, SC, 104, true, true, false, false},
+      {{0, 2, 32, 100, false, false, false, true, true}, SC, 104, true, true, false, false},
+      {{0, 3, 96, 100, false, false, false, true, true}, SC, 104, true, true, false, false},
+      {{1, 1, 64, 1, false, false, false, true, true}, F16, 64, false, false, false, false},          // the pad: to 64 keys on the fused
+      {{1, 1, 64, 63, false, false, false, true, true}, F16, 64, false, false, false, false},         //   16-bit paths, to 8 elsewhere
+      {{1, 1, 64, 64, false, false, false, true, true}, F16, 64, false, false, false, false},
+      {{1, 1, 64, 65, false, false, false, true, true}, F16, 128, false, false, false, false},
+      {{1, 1, 64, 65, false, true, true, true, true}, DROP, 128, false, false, false, false},
+      {{0, 0, 64, 1, false, false, false, true, true}, SC, 8, true, true, false, false},
+      {{0, 0, 64, 63, false, false, false, true, true}, SC, 64, true, true, false, false},
+      {{0, 0, 64, 64, false, false, false, true, true}, SC, 64, true, true, false, false},
+      {{0, 0, 64, 65, false, false, false, true, true}, SC, 72, true, true, false, false},
+      {{0, 2, 64, 1, false, false, false, true, true}, X3, 8, false, false, true, false},
+      {{0, 2, 64, 63, false, false, false, true, true}, X3, 64, false, false, true, false},
+      {{0, 2, 64, 65, false, false, false, true, true}, X3, 72, false, false, true, false},
+  };
+  int i = 0;
+  for (const Row& r : rows) {
+    const AttnPlan p = plan_attention(r.g);
+    if (p.path != r.path || p.Tp != r.Tp || p.scores != r.scores || p.vt != r.vt || p.planes_qkv != r.planes_qkv || p.planes_q != r.planes_q) {
+      std::fprintf(stderr, "plan_attention row %d: path %d Tp %d S+P %d Vt %d pl_qkv %d pl_q %d\n", i, (int)p.path, p.Tp, (int)p.scores,
+                   (int)p.vt, (int)p.planes_qkv, (int)p.planes_q);
+      return 1;
+    }
+    ++i;
+  }
+  // What the workspaces hold.  V^T is carved for every path.  The encoder has score buffers exactly on the score path; FusionRCA
+  // (scores_with_planes) has them on every path but the fused 16-bit one, the fused split path included.  Nothing else is added.
+  struct Ws { AttnGeom g; bool rca; bool scores, planes_qkv, planes_q; int Tp; };
+  const Ws ws[] = {
+      {{1, 1, 64, 100, false, false, false, true, true}, false, false, false, false, 128},   // encoder
+      {{0, 2, 64, 100, false, false, false, true, true}, false, false, true, false, 104},
+      {{0, 0, 64, 100, false, false, false, true, true}, false, true, false, false, 104},
+      {{1, 1, 64, 100, false, true, false, true, true}, false, true, false, false, 104},
+      {{1, 1, 64, 100, false, true, true, true, true}, false, false, false, false, 128},
+      {{1, 1, 64, 40, false, false, false, true, false}, true, false, false, false, 64},     // FusionRCA
+      {{0, 2, 64, 40, false, false, false, true, false}, true, true, true, true, 40},
+      {{0, 3, 128, 40, false, false, false, true, false}, true, true, true, true, 40},
+      {{0, 2, 32, 40, false, false, false, true, false}, true, true, false, false, 40},
+      {{0, 0, 64, 40, false, false, false, true, false}, true, true, false, false, 40},
+  };
+  for (const Ws& r : ws) {
+    const AttnPlan p = attn_workspace_plan(plan_attention(r.g), r.rca);
+    EXPECT(p.path == plan_attention(r.g).path);
+    EXPECT(p.vt && p.scores == r.scores && p.planes_qkv == r.planes_qkv && p.planes_q == r.planes_q && p.Tp == r.Tp);
+  }
+  std::printf("attention ok\n");
+  return 0;
+}
+
 int main(int argc, char** argv) {
   if (argc >= 2 && !std::strcmp(argv[1], "notes")) return run_notes(argc, argv);
   if (argc >= 2 && !std::strcmp(argv[1], "hostile")) return run_hostile();
   if (argc >= 2 && !std::strcmp(argv[1], "fold")) return run_fold(argc, argv);
-  std::fprintf(stderr, "usage: host_san_test notes <frames.bin> B T onset offset frame_size [capacity] | hostile | fold <op> <out.bin> dims... in.bin...\n");
+  if (argc >= 2 && !std::strcmp(argv[1], "attention")) return run_attention();
+  std::fprintf(stderr, "usage: host_san_test notes <frames.bin> B T onset offset frame_size [capacity] | hostile | attention | fold <op> <out.bin> dims... in.bin...\n");
   return 2;
 }

@@ -172,6 +172,12 @@ def test_hostile_arguments_under_sanitizers(san_bin):
     assert run(san_bin, "hostile").strip() == "hostile ok"
 
 
+def test_attention_planner_table_under_sanitizers(san_bin):
+    """plan_attention (the one place that chooses an attention path and the buffers it needs) against the driver's hand-written table:
+    every path, every edge of a condition, the key pad at T = 1, 63, 64, 65, and what the encoder's and FusionRCA's workspaces hold."""
+    assert run(san_bin, "attention").strip() == "attention ok"
+
+
 def test_reference_frame2note_fixture_under_sanitizers(san_bin, tmp_path, golden):
     for k, c in golden("frame2note").items():
         fr = pack(c["p_on"].numpy(), c["p_off"].numpy(), c["oct"].numpy(), c["pc"].numpy())
