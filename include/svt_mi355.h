@@ -907,8 +907,16 @@ int svt_debug_rca_attn_bwd(int32_t precision, const void* qkv, const void* qc, c
  * case), 44 = query: returns which dropout kernel the last launch of csrc/dropout.hip in this process chose (value ignored; 0 = none
  * yet): 1 = dropout_rows_kernel<float>, 2 = dropout_rows_kernel<16-bit>, 3 = dropout_hilo_kernel, each + 10 for its element-by-element
  * instantiation (e0 % 4 != 0 or a pointer that is not 16-byte aligned); 4 = softmax_dropout_kernel<float>, 5 = <16-bit>
- * (tests/test_gpu_dropout_kernels.py asserts the id of every case).
- * Returns 0 (keys 24, 31: the count; keys 38, 39, 40, 41, 42, 43, 44: the id), SVT_ERR_INVALID for an unknown key or a value a key does not accept (21, 28, 30, 37 above). */
+ * (tests/test_gpu_dropout_kernels.py asserts the id of every case), 45 = query: returns which kernel the last launch of the encoder's
+ * glue chose in this process (value ignored; 0 = none yet; set on the host by every branch of five launchers of csrc/encoder_ops.hip
+ * and by positional_conv of csrc/api_encoder.hip): launch_posconv_gather 11 = posconv_gather_kernel<float>, 12 = posconv_gather_kernel<16-bit>
+ * (element by element), 13 = posconv_gather_bf16x8_kernel (8 channels per thread); launch_posconv_scatter_add 21 =
+ * posconv_scatter_add_kernel<float> (split modes), 22 = <16-bit>; launch_relpos_table 30 = relpos_table_kernel; launch_relpos_gate 41 =
+ * relpos_gate_vec_kernel<float>, 42 = <16-bit>, 43 = relpos_gate_kernel<float> (one thread per head: head sizes whose eighth is no power of
+ * two), 44 = <16-bit>; a whole positional conv 1000 * form + 100 * gather + 10 * scatter with form 1 = plain (one grouped product with the
+ * residual in its epilogue), 2 = multi-frame, 3 = the data2vec stack, gather 1 .. 3 and scatter 0 (none) .. 2 the last digits above; key 39
+ * names the product's kernel (tests/test_gpu_encoder_glue.py asserts the id of every case).
+ * Returns 0 (keys 24, 31: the count; keys 38, 39, 40, 41, 42, 43, 44, 45: the id), SVT_ERR_INVALID for an unknown key or a value a key does not accept (21, 28, 30, 37 above). */
 int svt_debug_set(int key, int value);
 
 /* ---- test hook: ONE step of a finalized lip front-end on caller-supplied device buffers; tests/test_gpu_video_kernels.py ----
@@ -955,6 +963,37 @@ typedef struct svt_debug_video_desc {
   void* out;
 } svt_debug_video_desc;
 int svt_debug_video_step(svt_video* v, const svt_debug_video_desc* d, void* stream);
+
+/* ---- test hook: ONE step of a finalized encoder's glue on caller-supplied device buffers; tests/test_gpu_encoder_glue.py ----
+ * The step runs with the handle's own uploaded weights (the weight-norm fold, the tap-major relayout, the multi-frame weight image, the
+ * BatchNorm fold and the gate's row-sum fold of svt_encoder_finalize are inside the tested unit), through the same functions the forward
+ * calls, with the forward's own choice of form and kernel; the stream is synchronised before the call returns.  `step`:
+ *   1  positional_conv: `x` = h (B, T, D) fp32 -> `out` = h + pos_conv(h) (B, T, D) fp32.  The hook plans (B, n_samples) as a forward
+ *      does and refuses unless the planned frame count is T (features-in mode, num_conv_layers = 0: n_samples = T); it fills the first
+ *      svt_encoder_workspace_bytes(e, B, n_samples) bytes of `workspace` with 0xFF bytes (whatever the step reads without having written
+ *      it is NaN), copies h into the plan's projection output, runs the step and copies its result out.  Which of the three forms ran --
+ *      plain, multi-frame (B * ceil(T / Pf) >= 128 rows in the reduced modes), the data2vec stack -- is the plan's decision.
+ *   2  launch_relpos_table: `out` = pb (heads, 2 T - 1) fp32 from the handle's rel_attn_embed, rel_pos_buckets and rel_pos_max_distance.
+ *   3  launch_relpos_gate of layer `layer`: `x` = u (B T, D) in the handle's storage type (fp32 for an fp32 / split-operand handle, the
+ *      build's 16-bit type otherwise) -> `out` = gate (B, heads, T) fp32.
+ * svt_debug_set(45, 0) afterwards names the kernels, and for step 1 key 39 names the product's.  The hook never forces a form the forward
+ * would not take.  It is NARROWER than the launchers: it refuses (SVT_ERR_INVALID, nothing is launched) a wrong struct_size, a NULL or
+ * unfinalized handle, step outside 1 .. 3, a NULL pointer where the step needs one (out; x for steps 1 and 3; workspace for step 1),
+ * ANY non-NULL pointer that is not 16-byte aligned, B < 1 or T < 1, a layer outside 0 .. num_layers - 1 (step 3), steps 2 and 3 on a
+ * handle without rel_pos_buckets, a plan whose frame count is not T or a workspace_bytes below the plan's (step 1), more than 2^31
+ * elements.  A launcher's own refusal comes back as SVT_ERR_INVALID too.  struct_size = the size of the structure. */
+typedef struct svt_debug_encoder_desc {
+  int32_t struct_size;
+  int32_t step;
+  int32_t B, T;
+  int32_t layer, reserved;
+  int64_t n_samples;
+  const void* x;
+  void* out;
+  void* workspace;
+  uint64_t workspace_bytes;
+} svt_debug_encoder_desc;
+int svt_debug_encoder_step(svt_encoder* e, const svt_debug_encoder_desc* d, void* stream);
 
 /* ---- measurement hook: HIP-event timing of the dominant kernel on the stream it runs on ----
  * When enabled, forward calls bracket every launch of the dense contraction kernel with hipEvents on

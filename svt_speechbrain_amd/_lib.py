@@ -166,6 +166,19 @@ class VideoStepDescC(C.Structure):
     ]
 
 
+class EncoderStepDescC(C.Structure):
+    """svt_debug_encoder_desc: one step of a finalized encoder's glue on caller-supplied device buffers (svt_debug_encoder_step); step 1 .. 3."""
+    _fields_ = [
+        ("struct_size", C.c_int32),
+        ("step", C.c_int32),
+        ("B", C.c_int32), ("T", C.c_int32),
+        ("layer", C.c_int32), ("reserved", C.c_int32),
+        ("n_samples", C.c_int64),
+        ("x", C.c_void_p), ("out", C.c_void_p), ("workspace", C.c_void_p),
+        ("workspace_bytes", C.c_uint64),
+    ]
+
+
 class WavInfoC(C.Structure):
     """svt_wav_info: what svt_wav_parse reads from a RIFF/WAVE header; format is a svt_pcm_format (U8 = 1 .. F64 = 6)."""
     _fields_ = [("format", C.c_int32), ("channels", C.c_int32), ("sample_rate", C.c_int32), ("bits_per_sample", C.c_int32),
@@ -236,6 +249,7 @@ SYMBOLS = {
     "svt_debug_layernorm": (C.c_int, [C.POINTER(LayerNormDescC), C.c_int, _P]),
     "svt_debug_conv0": (C.c_int, [C.POINTER(Conv0DescC), C.c_int, _P]),
     "svt_debug_video_step": (C.c_int, [_P, C.POINTER(VideoStepDescC), _P]),
+    "svt_debug_encoder_step": (C.c_int, [_P, C.POINTER(EncoderStepDescC), _P]),
     "svt_debug_attention_scores": (C.c_int, [C.c_int32, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64,
                                              C.c_int64, C.c_float, _P, _P, C.c_int, _P]),
     "svt_debug_gemm_pairs": (C.c_int, [C.c_int32, _P, C.c_int64, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64,

@@ -817,7 +817,8 @@ GemmArgs posconv_gemm(const EncRun& x, const DevBuf& W, const DevBuf& bias) {
   return g;
 }
 
-// positional conv embedding, w.hF -> w.preF: pre = h + gelu(grouped_conv(h) + b), in one of three forms
+// positional conv embedding, w.hF -> w.preF: pre = h + gelu(grouped_conv(h) + b), in one of three forms.  Leaves svt_debug_set key 45 =
+// 1000 * form (1 plain, 2 multi-frame, 3 stack) + 100 * gather kernel + 10 * scatter kernel (the launchers' own ids less 10 / 20; 0: none)
 int positional_conv(const EncRun& x) {
   const svt_encoder_config& c = x.c;
   const svt_encoder* e = x.e;
@@ -825,12 +826,14 @@ int positional_conv(const EncRun& x) {
   const int prec = x.p.sp, gp = x.p.gp, B = x.p.B, T = (int)x.p.T, D = x.p.D, kp = c.pos_conv_kernel, G = c.pos_conv_groups, cg = D / G;
   const float* bn_sc = c.pos_conv_batch_norm ? e->pos_bn_sc.as<float>() : nullptr;
   const float* bn_sh = c.pos_conv_batch_norm ? e->pos_bn_sh.as<float>() : nullptr;
+  int gather_id = 0;
   if (c.pos_conv_depth > 1) {
     // data2vec-audio: pos = stack of [grouped conv -> LayerNorm(no affine, eps 1e-5) -> GELU]; pre = h + pos
     const float* cur = w.hF;
     float* lnout = w.xF;  // fp32 scratch (rows x D): free until the encoder's first LayerNorm
     for (int i = 0; i < c.pos_conv_depth; ++i) {
       if (int r = launch_posconv_gather(prec, cur, B, T, D, G, kp, T + kp, w.posg, x.s)) return r;
+      gather_id = g_glue_kernel_id - 10;
       GemmArgs g = posconv_gemm(x, e->pos_ws[i], e->pos_bs[i]);
       g.act = ACT_NONE;
       if (int r = launch_gemm(gp, g, x.s)) return r;
@@ -839,12 +842,15 @@ int positional_conv(const EncRun& x) {
       if (int r = launch_layernorm(n, x.s)) return r;
       cur = lnout;
     }
-    return launch_add_f32(w.hF, cur, w.preF, x.p.rows * (int64_t)D, x.s);
+    if (int r = launch_add_f32(w.hF, cur, w.preF, x.p.rows * (int64_t)D, x.s)) return r;
+    g_glue_kernel_id = 3000 + 100 * gather_id;
+    return SVT_OK;
   }
   if (x.p.pos_multi) {
     // multi-frame form (finalize_pos_conv): Pf output frames per GEMM row, 16-bit result scattered back onto h
     const int Pf = x.p.Pf, Tq = (int)x.p.pos_Tq, Tp = (int)x.p.pos_Tp;
     if (int r = launch_posconv_gather(prec, w.hF, B, T, D, G, kp, Tp, w.posg, x.s, bn_sc, bn_sh)) return r;
+    gather_id = g_glue_kernel_id - 10;
     GemmArgs g;
     g.A = w.posg; g.W = e->pos_wP.p; g.C = w.posy; g.bias = e->pos_bP.as<float>();
     g.M = B * Tq; g.N = Pf * cg; g.K = (kp + Pf - 1) * cg;
@@ -854,12 +860,17 @@ int positional_conv(const EncRun& x) {
     g.a_z2 = (long)Tp * cg; g.w_z2 = (long)g.N * g.K; g.c_z2 = (long)B * Tq * g.N; g.bias_z2 = g.N;
     g.act = ACT_GELU; g.out_f32 = 0;
     if (int r = launch_gemm(gp, g, x.s)) return r;
-    return launch_posconv_scatter_add(w.hF, w.posy, B, T, D, G, Pf, Tq, w.preF, x.s, prec ? 0 : 1);
+    if (int r = launch_posconv_scatter_add(w.hF, w.posy, B, T, D, G, Pf, Tq, w.preF, x.s, prec ? 0 : 1)) return r;
+    g_glue_kernel_id = 2000 + 100 * gather_id + 10 * (g_glue_kernel_id - 20);
+    return SVT_OK;
   }
   if (int r = launch_posconv_gather(prec, w.hF, B, T, D, G, kp, T + kp, w.posg, x.s, bn_sc, bn_sh)) return r;
+  gather_id = g_glue_kernel_id - 10;
   GemmArgs g = posconv_gemm(x, e->pos_w, e->pos_b);
   g.resid = w.hF; g.act = ACT_GELU;
-  return launch_gemm(gp, g, x.s);
+  if (int r = launch_gemm(gp, g, x.s)) return r;
+  g_glue_kernel_id = 1000 + 100 * gather_id;
+  return SVT_OK;
 }
 
 // ---- encoder layers.  Every family runs the same five products per layer; they differ in the type the products leave in and in the
@@ -1205,6 +1216,57 @@ int svt_encoder_forward_head(svt_encoder* e, const svt_linear* head, const float
   TailSpec t;
   t.head = head; t.logits = logits; t.frames = frames; t.n_oct = n_octave; t.n_cls = n_class;
   return encoder_forward_impl(e, wav, B, L, t, workspace, workspace_bytes, stream, clips_per_norm_group);
+}
+
+// One step of a finalized encoder on the caller's device buffers (include/svt_mi355.h documents the steps, buffers and refusals)
+int svt_debug_encoder_step(svt_encoder* e, const svt_debug_encoder_desc* d, void* stream) {
+  auto refuse = [](const char* why) { set_error(std::string("svt_debug_encoder_step: ") + why); return (int)SVT_ERR_INVALID; };
+  auto aligned16 = [](auto... p) { return !((... | (uintptr_t)p) & 15); };   // a null pointer passes
+  if (!d || d->struct_size != (int32_t)sizeof(svt_debug_encoder_desc)) return refuse("struct_size");
+  if (!e) return refuse("null handle");
+  if (!e->finalized) return refuse("call svt_encoder_finalize first");
+  const int step = d->step;
+  if (step < 1 || step > 3) return refuse("step is 1 .. 3");
+  if (!aligned16(d->x, d->out, d->workspace)) return refuse("every buffer 16-byte aligned");
+  if (!d->out || (step != 2 && !d->x) || (step == 1 && !d->workspace)) return refuse("null buffer");
+  if (d->B < 1 || d->T < 1) return refuse("B and T must be positive");
+  const svt_encoder_config& c = e->cfg;
+  if (step != 1 && !c.rel_pos_buckets) return refuse("steps 2 and 3 need an encoder with rel_pos_buckets");
+  if (step == 3 && (d->layer < 0 || d->layer >= c.num_layers)) return refuse("layer out of range");
+  if ((int64_t)d->B * d->T > 2147483647LL / (c.hidden_size > 2 * c.num_heads ? c.hidden_size : 2 * c.num_heads))
+    return refuse("too many frames for one call");
+  hipStream_t s = (hipStream_t)stream;
+  const int H = c.num_heads, D = c.hidden_size;
+  int rc = SVT_OK;
+  if (step == 1) {
+    EncPlan plan;
+    if (!plan_encoder(e, d->B, d->n_samples, &plan)) return refuse("n_samples is shorter than the receptive field");
+    if (plan.T != d->T) return refuse("the plan of (B, n_samples) has another frame count than T");
+    const EncWs w = carve_encoder(e, plan, d->workspace);
+    if (w.total > d->workspace_bytes) return refuse("workspace smaller than svt_encoder_workspace_bytes");
+    SVT_HIP(hipSetDevice(e->device));
+    // the whole workspace 0xFF first: whatever the step reads without having written it is NaN
+    if (hipMemsetAsync(d->workspace, 0xFF, w.total, s) != hipSuccess) { set_error("svt_debug_encoder_step: hipMemsetAsync"); rc = SVT_ERR_HIP; }
+    const int64_t n = plan.rows * D;
+    if (!rc && launch_copy_f32((const float*)d->x, w.hF, n, s)) rc = SVT_ERR_HIP;
+    if (!rc) {
+      const EncRun x{e, e->cfg, plan, w, s};
+      rc = positional_conv(x);
+    }
+    if (!rc && launch_copy_f32(w.preF, (float*)d->out, n, s)) rc = SVT_ERR_HIP;
+  } else {
+    SVT_HIP(hipSetDevice(e->device));
+    if (step == 2) {
+      rc = launch_relpos_table(e->rel_embed.as<float>(), H, d->T, c.rel_pos_buckets, c.rel_pos_max_distance, (float*)d->out, s);
+    } else {
+      const EncLayerW& L = e->layers[d->layer];
+      rc = launch_relpos_gate(storage_prec(c.precision), d->x, (int64_t)d->B * d->T, d->T, H, D / H, L.g_wab.as<float>(), L.g_bab.as<float>(),
+                              L.g_const.as<float>(), (float*)d->out, s);
+    }
+  }
+  if (rc && rc != SVT_ERR_HIP) rc = SVT_ERR_INVALID;   // a launcher's own refusal
+  if (hipStreamSynchronize(s) != hipSuccess && !rc) { set_error("svt_debug_encoder_step: hipStreamSynchronize"); rc = SVT_ERR_HIP; }
+  return rc;
 }
 
 }  // extern "C"

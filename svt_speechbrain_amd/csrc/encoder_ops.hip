@@ -117,17 +117,22 @@ __global__ void posconv_gather_bf16x8_kernel(const float* h, int B, int T, int D
   }
 }
 }  // namespace
+int g_glue_kernel_id = 0;  // svt_debug_set key 45 (query): the kernel the last launch of the encoder's glue chose (include/svt_mi355.h lists the ids)
 int launch_posconv_gather(int prec, const float* h, int B, int T, int D, int G, int kp, int Tp, void* out, hipStream_t s, const float* sc,
                           const float* sh) {
   const int64_t n = (int64_t)B * Tp * D;
-  if (prec && (D / G) % 8 == 0 && aligned(15, h, out))
+  if (prec && (D / G) % 8 == 0 && aligned(15, h, out)) {
     hipLaunchKernelGGL(posconv_gather_bf16x8_kernel, dim3(grid_for(n / 8)), dim3(256), 0, s, h, B, T, D, G, kp, Tp, (bf16_t*)out, sc, sh);
-  else if (prec)
+    g_glue_kernel_id = 13;
+  } else if (prec) {
     hipLaunchKernelGGL((posconv_gather_kernel<bf16_t>), dim3(grid_for(n)), dim3(256), 0, s, h, B, T, D, G, kp, Tp,
                        (bf16_t*)out, sc, sh);
-  else
+    g_glue_kernel_id = 12;
+  } else {
     hipLaunchKernelGGL((posconv_gather_kernel<float>), dim3(grid_for(n)), dim3(256), 0, s, h, B, T, D, G, kp, Tp,
                        (float*)out, sc, sh);
+    g_glue_kernel_id = 11;
+  }
   SVT_LAUNCH_CHECK();
   return 0;
 }
@@ -165,6 +170,7 @@ int launch_posconv_scatter_add(const float* h, const void* y, int B, int T, int 
   const int64_t n = (int64_t)B * T * (D / 8);
   if (y_f32) hipLaunchKernelGGL((posconv_scatter_add_kernel<float>), dim3(grid_for(n)), dim3(256), 0, s, h, (const float*)y, B, T, D, G, P, Tq, pre);
   else hipLaunchKernelGGL((posconv_scatter_add_kernel<bf16_t>), dim3(grid_for(n)), dim3(256), 0, s, h, (const bf16_t*)y, B, T, D, G, P, Tq, pre);
+  g_glue_kernel_id = y_f32 ? 21 : 22;
   SVT_LAUNCH_CHECK();
   return 0;
 }
@@ -315,6 +321,7 @@ __global__ void relpos_table_kernel(const float* embed, int H, int T, int num_bu
 int launch_relpos_table(const float* embed, int H, int T, int num_buckets, int max_distance, float* pb, hipStream_t s) {
   const int n = (2 * T - 1) * H;
   hipLaunchKernelGGL(relpos_table_kernel, dim3((n + 255) / 256), dim3(256), 0, s, embed, H, T, num_buckets, max_distance, pb);
+  g_glue_kernel_id = 30;
   SVT_LAUNCH_CHECK();
   return 0;
 }
@@ -394,11 +401,13 @@ int launch_relpos_gate(int prec, const void* u, int64_t rows, int T, int H, int 
     const dim3 grid((unsigned)((threads + 255) / 256));
     if (prec) hipLaunchKernelGGL(relpos_gate_vec_kernel<bf16_t>, grid, dim3(256), 0, s, (const bf16_t*)u, n, T, H, dh, wab, bab, cst, gate);
     else hipLaunchKernelGGL(relpos_gate_vec_kernel<float>, grid, dim3(256), 0, s, (const float*)u, n, T, H, dh, wab, bab, cst, gate);
+    g_glue_kernel_id = prec ? 42 : 41;
     SVT_LAUNCH_CHECK();
     return 0;
   }
   if (prec) hipLaunchKernelGGL(relpos_gate_kernel<bf16_t>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (const bf16_t*)u, rows, T, H, dh, wab, bab, cst, gate);
   else hipLaunchKernelGGL(relpos_gate_kernel<float>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (const float*)u, rows, T, H, dh, wab, bab, cst, gate);
+  g_glue_kernel_id = prec ? 44 : 43;
   SVT_LAUNCH_CHECK();
   return 0;
 }

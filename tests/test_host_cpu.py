@@ -649,6 +649,24 @@ def test_video_step_descriptor_has_the_layout_the_header_declares(tmp_path):
     assert declared == fields, (declared, fields)
 
 
+def test_encoder_step_descriptor_has_the_layout_the_header_declares(tmp_path):
+    """svt_debug_encoder_desc as gcc lays it out from include/svt_mi355.h against _lib.EncoderStepDescC: size and the offset of every field."""
+    import subprocess
+    fields = [f for f, _ in _lib.EncoderStepDescC._fields_]
+    src = tmp_path / "desc.c"
+    src.write_text('#include <stdio.h>\n#include "svt_mi355.h"\nint main(void) {\n  printf("%zu", sizeof(svt_debug_encoder_desc));\n' +
+                   "".join(f'  printf(" %zu", offsetof(svt_debug_encoder_desc, {f}));\n' for f in fields) + "  return 0;\n}\n")
+    exe = str(tmp_path / "desc")
+    r = subprocess.run(["gcc", "-std=c11", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(src), "-o", exe], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    got = [int(v) for v in subprocess.run([exe], capture_output=True, text=True, check=True).stdout.split()]
+    assert got == [ctypes.sizeof(_lib.EncoderStepDescC)] + [getattr(_lib.EncoderStepDescC, f).offset for f in fields]
+    hdr = open(os.path.join(ROOT, "include", "svt_mi355.h")).read()
+    body = hdr[hdr.index("typedef struct svt_debug_encoder_desc {"):hdr.index("} svt_debug_encoder_desc;")]
+    declared = re.findall(r"[\s,*](\w+)(?=[,;])", body)
+    assert declared == fields, (declared, fields)
+
+
 # ---- round-2 advisor findings: every way the weights can change must reach every device object ----
 def test_state_loaded_through_a_parent_module_is_normalised_and_invalidates():
     """``Brain.modules`` is an ``nn.ModuleDict`` and ``Checkpointer`` may load through it: nn.Module recursion never calls
