@@ -815,6 +815,52 @@ typedef struct svt_debug_attention_dropout_desc {
   uint64_t e0;
 } svt_debug_attention_dropout_desc;
 int svt_debug_attention_dropout(const svt_debug_attention_dropout_desc* d, int device, void* stream);
+/* The fused attention in both directions on caller buffers (csrc/attention_bf16.hip, attention_drop.hip, attention_bwd.hip), for a
+ * caller that trains through it (svt_speechbrain_amd/attention.py wraps the pair in a torch.autograd.Function).  All tensors are in the
+ * build's 16-bit operand type; precision must be SVT_PREC_BF16 and head_dim 64.  Rows: q at q + (b*t + i)*ldq + h*head_dim, k / v with
+ * ldkv, o with ldo, d_o (the gradient of o; `do` is a C keyword) with lddo, dq with lddq, dk / dv with lddkv (element strides, multiples
+ * of 8; every pointer 16-byte aligned).  dq / dk / dv have row strides of their own so that the three can land in one packed
+ * (batch*t, 3*heads*head_dim) buffer, the dY operand of a packed q|k|v projection's backward.
+ *   o = (keep * s * softmax(scale q k^T)) v, s = float(1 / (1 - p)), keep = svt_dropout's mask of site 2 in `layer` at (seed, step),
+ *   element e0 + ((b*heads + h)*t + i)*t + j (HF eager order: softmax -> dropout -> . v).  p == 0: no mask is drawn, the plain kernels.
+ * svt_attention_forward reads q, k, v and writes o (d_o, dq, dk, dv are ignored): launch_flash_attention at p == 0,
+ * launch_flash_attention_dropout at p > 0.  svt_attention_backward reads q, k, v, o (as the forward stored it), d_o and writes dq, dk, dv:
+ * three launches (row log-sum-exp and delta_i = d_o_i . o_i into the workspace, then dq, then dk and dv), deterministic -- no atomics, two
+ * calls give the same bytes -- and without any (batch, heads, t, t) tensor.  workspace convention of svt_amt_objective_grad (workspace_dev
+ * NULL: the size is stored in *workspace_bytes and nothing else happens).  Refused with SVT_ERR_INVALID and a message, nothing launched:
+ * a struct_size other than the structure's, a precision other than SVT_PREC_BF16, head_dim other than 64 (the forward: 64 or 128), p
+ * outside [0, 1), strides that are no multiples of 8, misaligned pointers.  svt_debug_set(46, 0) says which form the last backward ran. */
+typedef struct svt_attention_desc {
+  int32_t struct_size;
+  int32_t precision;
+  const void* q;
+  const void* k;
+  const void* v;
+  void* o;
+  const void* d_o;
+  void* dq;
+  void* dk;
+  void* dv;
+  int64_t ldq;
+  int64_t ldkv;
+  int64_t ldo;
+  int64_t lddo;
+  int64_t lddq;
+  int64_t lddkv;
+  int32_t batch;
+  int32_t t;
+  int32_t heads;
+  int32_t head_dim;
+  float scale;
+  uint32_t step;
+  double p;
+  uint64_t seed;
+  int32_t layer;
+  int32_t reserved;
+  uint64_t e0;
+} svt_attention_desc;
+int svt_attention_forward(const svt_attention_desc* d, int device, void* stream);
+int svt_attention_backward(const svt_attention_desc* d, void* workspace_dev, size_t* workspace_bytes, int device, void* stream);
 /* The score-matrix attention alone (tests/test_gpu_attention_scores.py): what every attention outside the fused kernels' reach runs --
  * the fp32 parity mode, 16-bit head sizes other than 64 / 128, WavLM's biased attention at head size 128 or 2 t - 1 > 8192, WavLM in the
  * split-operand modes.  Two batched products (scale q k^T into fp32 scores with rows padded to a multiple of 8 keys, P V) around the
@@ -915,8 +961,11 @@ int svt_debug_rca_attn_bwd(int32_t precision, const void* qkv, const void* qc, c
  * relpos_gate_vec_kernel<float>, 42 = <16-bit>, 43 = relpos_gate_kernel<float> (one thread per head: head sizes whose eighth is no power of
  * two), 44 = <16-bit>; a whole positional conv 1000 * form + 100 * gather + 10 * scatter with form 1 = plain (one grouped product with the
  * residual in its epilogue), 2 = multi-frame, 3 = the data2vec stack, gather 1 .. 3 and scatter 0 (none) .. 2 the last digits above; key 39
- * names the product's kernel (tests/test_gpu_encoder_glue.py asserts the id of every case).
- * Returns 0 (keys 24, 31: the count; keys 38, 39, 40, 41, 42, 43, 44, 45: the id), SVT_ERR_INVALID for an unknown key or a value a key does not accept (21, 28, 30, 37 above). */
+ * names the product's kernel (tests/test_gpu_encoder_glue.py asserts the id of every case), 46 = query: returns which form the last
+ * attention backward of this process launched (value ignored; 0 = none yet; csrc/attention_bwd.hip): 1 = plain (attn_bwd_prep_kernel,
+ * attn_bwd_dq_kernel<false>, attn_bwd_dkv_kernel<false>), 2 = masked (attn_bwd_prep_kernel, attn_bwd_dq_kernel<true>,
+ * attn_bwd_dkv_kernel<true>: p > 0) (tests/test_gpu_attention_backward.py asserts the id of every case).
+ * Returns 0 (keys 24, 31: the count; keys 38, 39, 40, 41, 42, 43, 44, 45, 46: the id), SVT_ERR_INVALID for an unknown key or a value a key does not accept (21, 28, 30, 37 above). */
 int svt_debug_set(int key, int value);
 
 /* ---- test hook: ONE step of a finalized lip front-end on caller-supplied device buffers; tests/test_gpu_video_kernels.py ----

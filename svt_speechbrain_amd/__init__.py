@@ -32,6 +32,8 @@ from .audio_io import info, load, save, read_audio, write_audio  # noqa: F401
 from .dataio import read_utterance  # noqa: F401
 from . import training  # noqa: F401
 from .training import Adadelta, Adam, AdamW, LinearProbe, FusionTrainer, VideoProbe  # noqa: F401
+from . import attention  # noqa: F401
+from .attention import fused_attention, FusedSelfAttention  # noqa: F401
 
 __all__ = ["EncoderConfig", "PRESETS", "config_from_source", "HuggingFaceWav2Vec2", "Linear", "FusionRCA", "Fbank",
            "decode_frames", "frame2note", "frames2note", "frames2note_batch", "frames_to_info", "ctc_greedy_decode", "filter_ctc_output", "AMTForward",
@@ -42,4 +44,4 @@ __all__ = ["EncoderConfig", "PRESETS", "config_from_source", "HuggingFaceWav2Vec
            "babble_split", "noise_pools", "natural_pools", "babble_pools", "noisy_wav_path", "NoiseSweep",
            "Resample", "SpeedPerturb", "resample_table", "resample_to_mono",
            "notch_filter", "drop_filter", "DropFreq", "DropChunk", "TimeDomainSpecAugment",
-           "audio_io", "info", "load", "save", "read_audio", "write_audio", "read_utterance"]
+           "fused_attention", "FusedSelfAttention", "audio_io", "info", "load", "save", "read_audio", "write_audio", "read_utterance"]

@@ -121,6 +121,22 @@ class AttentionDropoutDescC(C.Structure):
     ]
 
 
+class AttentionDescC(C.Structure):
+    """svt_attention_desc: the fused attention in both directions on caller buffers (svt_attention_forward / svt_attention_backward);
+    d_o is the gradient of o (``do`` is a keyword in C)."""
+    _fields_ = [
+        ("struct_size", C.c_int32), ("precision", C.c_int32),
+        ("q", C.c_void_p), ("k", C.c_void_p), ("v", C.c_void_p), ("o", C.c_void_p),
+        ("d_o", C.c_void_p), ("dq", C.c_void_p), ("dk", C.c_void_p), ("dv", C.c_void_p),
+        ("ldq", C.c_int64), ("ldkv", C.c_int64), ("ldo", C.c_int64), ("lddo", C.c_int64), ("lddq", C.c_int64), ("lddkv", C.c_int64),
+        ("batch", C.c_int32), ("t", C.c_int32), ("heads", C.c_int32), ("head_dim", C.c_int32),
+        ("scale", C.c_float), ("step", C.c_uint32),
+        ("p", C.c_double), ("seed", C.c_uint64),
+        ("layer", C.c_int32), ("reserved", C.c_int32),
+        ("e0", C.c_uint64),
+    ]
+
+
 class DropoutDescC(C.Structure):
     """svt_debug_dropout_desc: one launch of a dropout kernel (svt_debug_dropout); form 0 / 1 / 2, device pointers."""
     _fields_ = [
@@ -239,6 +255,8 @@ SYMBOLS = {
     "svt_encoder_set_dropout": (C.c_int, [_P, C.POINTER(DropoutC)]),
     "svt_debug_dropout": (C.c_int, [C.POINTER(DropoutDescC), C.c_int, _P]),
     "svt_debug_attention_dropout": (C.c_int, [C.POINTER(AttentionDropoutDescC), C.c_int, _P]),
+    "svt_attention_forward": (C.c_int, [C.POINTER(AttentionDescC), C.c_int, _P]),
+    "svt_attention_backward": (C.c_int, [C.POINTER(AttentionDescC), _P, C.POINTER(C.c_size_t), C.c_int, _P]),
     "svt_wav_parse": (C.c_int, [_P, C.c_int64, C.c_int64, C.POINTER(WavInfoC), _I64P]),
     "svt_wav_header": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int64, _P, C.c_int64, _I64P]),
     "svt_pcm_decode": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int64, _P, C.c_int64, C.c_int32, C.c_int, _P]),

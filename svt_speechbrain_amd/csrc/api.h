@@ -92,6 +92,25 @@ int launch_attention(const AttnArgs& a, const AttnBufs& ab, hipStream_t s);
 // the buffers `plan` names, in the order S, P, Vt, pl_qkv, pl_q; the rest null.  es: esize of the storage type
 AttnBufs carve_attention(Carver& cv, const AttnPlan& plan, size_t B, size_t H, size_t T, size_t dh, size_t es);
 
+// The backward of one fused attention (attention_bwd.hip): dQ, dK, dV from q, k, v, the saved o and dO, all in the build's 16-bit operand
+// type, rows addressed as AttnArgs' (q at Q + (b*T+t)*ldq + h*dh, ...); each gradient has its own row stride, so the three can land in
+// one packed (B*T, 3D) buffer.  drop: the forward's site-2 mask (null: the plain kernels), e0 its first element index.  ws: the
+// workspace, attention_backward_workspace_bytes (L and delta, (B, H, T) fp32 each).
+struct AttnBwdArgs {
+  int prec = 0;
+  const void *Q = nullptr, *K = nullptr, *V = nullptr, *O = nullptr, *dO = nullptr;
+  void *dQ = nullptr, *dK = nullptr, *dV = nullptr;
+  long ldq = 0, ldkv = 0, ldo = 0, lddo = 0, lddq = 0, lddkv = 0;
+  int B = 0, T = 0, H = 0, dh = 0; float scale = 1.f;
+  const float *gate = nullptr, *relpb = nullptr;   // a position bias is refused
+  const DropSpec* drop = nullptr; uint64_t e0 = 0;
+  void* ws = nullptr;
+};
+size_t attention_backward_workspace_bytes(int B, int H, int T);
+// refuses (set_error, nothing launched): head size other than 64, a precision other than the 16-bit one, a position bias, strides that
+// are no multiples of 8 elements, a pointer the 16-byte accesses find misaligned
+int launch_attention_backward(const AttnBwdArgs& a, hipStream_t s);
+
 // a gfx950 device of this index exists; it becomes the current device
 int check_device(int device);
 // workspace_bytes is in / out: with workspace == NULL the size the call needs is stored and nothing else happens

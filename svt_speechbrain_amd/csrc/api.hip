@@ -664,6 +664,7 @@ int svt_debug_set(int key, int value) {
   else if (key == 43) return g_vstep_kernel_id;
   else if (key == 44) return g_dropout_kernel_id;
   else if (key == 45) return g_glue_kernel_id;
+  else if (key == 46) return g_attn_bwd_id;
   else { set_error("svt_debug_set: unknown key"); return SVT_ERR_INVALID; }
   return SVT_OK;
 }

@@ -579,4 +579,52 @@ int svt_clip_adam_step(int32_t n_tensors, float* const* params, float* const* gr
   return SVT_OK;
 }
 
+// svt_attention_forward / svt_attention_backward: the checks both share; fills `spec` when p > 0
+static int attention_desc_check(const char* who, const svt_attention_desc* d, bool backward, DropSpec* spec) {
+  auto refuse = [who](const char* why) { set_error(std::string(who) + ": " + why); return SVT_ERR_INVALID; };
+  if (!d) return refuse("null descriptor");
+  if (d->struct_size != (int32_t)sizeof(svt_attention_desc)) return refuse("struct_size");
+  if (!d->q || !d->k || !d->v || !d->o) return refuse("null argument");
+  if (backward && (!d->d_o || !d->dq || !d->dk || !d->dv)) return refuse("null argument");
+  if (d->batch < 1 || d->t < 1 || d->heads < 1) return refuse("batch, t and heads must be positive");
+  if (d->precision != SVT_PREC_BF16) return refuse("precision must be SVT_PREC_BF16 (the build's 16-bit operand type)");
+  if (backward ? d->head_dim != 64 : (d->head_dim != 64 && d->head_dim != 128))
+    return refuse(backward ? "head_dim must be 64" : "head_dim must be 64 or 128");
+  if (!(d->p >= 0.0 && d->p < 1.0)) return refuse("p must lie in [0, 1)");
+  if (d->layer < 0 || d->layer > 0xFFFFFF) return refuse("layer");
+  if (d->p > 0.0) *spec = make_drop_spec(d->p, d->seed, d->step, 2, d->layer);
+  return SVT_OK;
+}
+
+int svt_attention_forward(const svt_attention_desc* d, int device, void* stream) {
+  DropSpec spec;
+  if (int r = attention_desc_check("svt_attention_forward", d, false, &spec)) return r;
+  if (int r = check_device(device)) return r;
+  SVT_HIP(hipSetDevice(device));
+  const long t = d->t;
+  const int rc = d->p > 0.0
+      ? launch_flash_attention_dropout(d->q, d->ldq, t * d->ldq, d->k, d->v, d->ldkv, t * d->ldkv, d->o, d->ldo, t * d->ldo, d->batch, d->t,
+                                       d->heads, d->head_dim, d->scale, d->e0, spec, (hipStream_t)stream)
+      : launch_flash_attention(d->q, d->ldq, t * d->ldq, d->k, d->v, d->ldkv, t * d->ldkv, d->o, d->ldo, t * d->ldo, d->batch, d->t, d->heads,
+                               d->head_dim, d->scale, (hipStream_t)stream);
+  return rc ? SVT_ERR_INVALID : SVT_OK;
+}
+
+int svt_attention_backward(const svt_attention_desc* d, void* workspace, size_t* workspace_bytes, int device, void* stream) {
+  const char* who = "svt_attention_backward";
+  DropSpec spec;
+  if (int r = attention_desc_check(who, d, true, &spec)) return r;
+  bool query;
+  if (int r = ws_query(who, workspace, workspace_bytes, attention_backward_workspace_bytes(d->batch, d->heads, d->t), &query)) return r;
+  if (query) return SVT_OK;
+  if (int r = check_device(device)) return r;
+  SVT_HIP(hipSetDevice(device));
+  AttnBwdArgs a;
+  a.prec = 1; a.Q = d->q; a.K = d->k; a.V = d->v; a.O = d->o; a.dO = d->d_o; a.dQ = d->dq; a.dK = d->dk; a.dV = d->dv;
+  a.ldq = d->ldq; a.ldkv = d->ldkv; a.ldo = d->ldo; a.lddo = d->lddo; a.lddq = d->lddq; a.lddkv = d->lddkv;
+  a.B = d->batch; a.T = d->t; a.H = d->heads; a.dh = d->head_dim; a.scale = d->scale;
+  a.drop = d->p > 0.0 ? &spec : nullptr; a.e0 = d->e0; a.ws = workspace;
+  return launch_attention_backward(a, (hipStream_t)stream) ? SVT_ERR_INVALID : SVT_OK;
+}
+
 }  // extern "C"

@@ -344,6 +344,7 @@ extern int g_ln_kernel_id;  // key 40 (query): which LayerNorm kernel and instan
 extern int g_flash_wide;  // fused attention: 8-wave (256-query) workgroups for head_dim 64 (1, default) or 4-wave ones (0)
 extern int g_flash_kernel_id;  // fused attention: id of the kernel the last launch chose (attention_bf16.hip, attention_x3.hip, attention_drop.hip; svt_debug_set key 38)
 extern int g_glue_kernel_id;   // key 45 (query): which kernel the last launch of the encoder's glue chose (encoder_ops.hip; api_encoder.hip positional_conv; include/svt_mi355.h lists the ids)
+extern int g_attn_bwd_id;   // key 46 (query): which form the last attention backward launched (attention_bwd.hip): 1 plain, 2 masked
 extern int g_ffn2_ksplit;   // svt_debug_set key 36 (api_encoder.hip): FFN-2 of a small batch as a K-split small GEMM + summing LayerNorm
 // switches of the host entry points, defined beside their users; hidden like the helpers of api.h (not part of the exported symbols)
 #pragma GCC visibility push(hidden)
